@@ -21,6 +21,13 @@ Scaling modes (the line says which one ran, in `scaling`, `metric` and `config.w
 The batch is made STATIONARY before anything is timed: episode phases are staggered over the batch
 (env e starts at step (37 e) mod 100) and one untimed episode length is rolled, so every timed window --
 however short -- samples all phases of an episode incl. the merge zone and the in-kernel auto-reset.
+
+A plain run measures the headline figure only.  --full adds everything that takes runs of its own: the kernel time
+(hipGraph replay) with the roofline blocks, the interior-point QP line (value_within_tolerance / qp_fidelity_mode),
+all_outputs_per_step_fold, cpu_baseline and, with N > 1 under strong scaling, weak_scaling.
+--dump-outputs DIR writes what the last timed step returned (obs + the info dict) and the rollout metrics of the timed
+region as DIR/<name>.npy (float32 / float64; above DUMP_MAX_ENVS envs the same fixed, seeded sample of envs for every
+array; rank 0's shard with N > 1).
 """
 import argparse
 import json
@@ -39,6 +46,33 @@ QP_MODE_NOTE = {"exact": "closed-form KKT point of the shield QP: outside north_
                          "iterate, see config.tolerance",
                 "ipm": "cvxopt's interior-point iterate, the reference's own solver behaviour: inside north_star's 1e-5"}
 SHIELDS = {"mass": "cbf-cav", "hss": "cbf-avs_cint", "none": "none"}
+DUMP_MAX_ENVS = 8192  # --dump-outputs: at most 8 192 envs x 12 vehicles x 30 f64 obs features = 24 MB, all arrays < 64 MB
+
+
+def dump_outputs(path, step_result, metrics):
+    """--dump-outputs: the arrays the last timed env.step returned (obs + the info dict; uint8 flags as float32) and the
+    timed region's rollout metrics, one .npy each.  Larger batches: the same seeded sample of DUMP_MAX_ENVS envs.
+    The step outputs are bit-reproducible; the metric sums are folded across blocks with atomics (last bits may vary).
+    Every value written is finite: the library marks "no value" with a non-finite number in two outputs (mm_abi.h), and
+    the dump stores those entries as follows -- merge_percent (NaN unless the episode ended): 0 where done == 0;
+    min_headway (+inf where no controlled vehicle has anything ahead; also the metrics' min): the largest float64."""
+    import numpy as np
+    obs, _, _, info = step_result
+    arrays = dict(info, obs=obs)
+    if "merge_percent" in arrays:
+        arrays["merge_percent"] = torch.where(info["done"] != 0, info["merge_percent"], torch.zeros_like(info["merge_percent"]))
+    no_bound = lambda t: torch.nan_to_num(t, nan=float("nan"), posinf=torch.finfo(torch.float64).max)  # noqa: E731
+    if "min_headway" in arrays:
+        arrays["min_headway"] = no_bound(info["min_headway"])
+    E = obs.shape[0]
+    idx = None
+    if E > DUMP_MAX_ENVS:
+        idx = torch.randperm(E, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ENVS].sort().values.to(obs.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t in sorted(arrays.items()):
+        t = (t if idx is None else t.index_select(0, idx)).cpu()
+        np.save(os.path.join(path, name + ".npy"), (t if t.dtype == torch.float64 else t.to(torch.float32)).numpy())
+    np.save(os.path.join(path, "rollout_metrics.npy"), no_bound(metrics).cpu().numpy())
 
 
 def algorithmic_bytes_per_agent_step(env_id, N):
@@ -167,6 +201,45 @@ def workload_traffic(*a, **k):
     return None if r is None else r["bytes_per_launch"]
 
 
+def roofline_blocks(args, E, N, kern_ms, kern_how):
+    """--full: `roofline` (HBM) and `roofline_secondary` (VALU issue) of the headline workload from the kernel time that
+    measure() took after the timed region."""
+    b_alg = algorithmic_bytes_per_agent_step(args.env_id, N)
+    achieved = E * N * b_alg / (kern_ms * 1e-3) / 1e9
+    # HBM bytes per launch and VALU instructions per wave from the committed PMC passes of this workload
+    # (profiles/traffic.json: one row per profiled workload); null for a workload that was not profiled
+    wrow = workload_row(E, N, args.shield, args.env_id, args.qp_solver, args.hdv, args.traffic_density, args.pow2_groups,
+                        args.mixed_traffic)
+    traffic = None if wrow is None else wrow["bytes_per_launch"]
+    out = {"roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                        "traffic_unit": "bytes/launch: rocprofv3 PMC passes of this command, 2 x FETCH_SIZE + WRITE_SIZE (gfx950 correction), "
+                                        "committed under profiles/ (see profiles/traffic.json: source)",
+                        "alg_bytes_per_launch": E * N * b_alg,
+                        "kernel": "step_kernel" if args.qp_solver == "exact" or args.shield == "none" or E * (2 if N <= 2 else 4 if N <= 4 else 8 if N <= 8 else 16) // 64 <= 2048
+                        else "4 x step_kernel (phase form) + 3 x sweep_kernel (interior-point step above two fused waves per SIMD)",
+                        "kernel_ms": kern_ms, "alg_bytes_per_agent_step": b_alg,
+                        "kernel_ms_note": "measured AFTER the timed region: %s between ONE HIP event pair on the launch stream, / launches "
+                                          "= the kernel(s) of one mm_step + the device's dispatch gap (the rollout metrics are deferred: no "
+                                          "flush kernel per step); rocprofv3's kernel-trace average of the same command is under profiles/" % kern_how[0],
+                        "mm_steps_after_timed_region": kern_how[1]}}
+    # secondary reading (the kernel is VALU-issue bound, DESIGN.md 2): instructions from the committed
+    # SQ_INSTS_VALU pass x 4 issue cycles per wave64 instruction, against 1024 SIMDs at the 2.4 GHz peak clock
+    try:
+        row = wrow  # (the matched workload's own row: by key, not by byte count)
+        if row is None:
+            raise KeyError("workload not profiled")
+        sj = json.load(open(os.path.join(REPO, "profiles", row.get("summary", "r01/step_kernel_summary.json"))))
+        per_wave = sj["pmc_per_launch"]["SQ_INSTS_VALU"] / sj["pmc_per_launch"]["SQ_WAVES"]
+        n_valu = per_wave * (E * 8 // 64 if N <= 8 else E * 16 // 64)
+        ach = n_valu * 4 / (kern_ms * 1e-3) / 1e12
+        out["roofline_secondary"] = {"bound": "valu-issue", "achieved": ach, "peak": 1024 * 2.4e9 / 1e12, "unit": "T SIMD-cycles/s",
+                                     "frac": ach / (1024 * 2.4e9 / 1e12), "valu_insts_per_wave": per_wave}
+    except (OSError, KeyError, ValueError, ZeroDivisionError, IndexError, TypeError):
+        pass
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -203,6 +276,10 @@ def main():
     ap.add_argument("--cpu-envs", type=int, default=32768)
     ap.add_argument("--cpu-steps", type=int, default=400)
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline: kernel time + roofline, the "
+                                                         "interior-point QP line, all outputs per step, cpu_baseline, weak scaling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and the rollout metrics as DIR/<name>.npy (rank 0's shard)")
     args = ap.parse_args()
     if args.scaling is None:  # an explicit per-GPU batch size means per-GPU work is what the caller fixes
         args.scaling = "weak" if (args.envs is not None and args.total_envs is None) else "strong"
@@ -250,9 +327,10 @@ def main():
         if world > 1:
             dist.barrier(device_ids=[local]) if nccl else dist.barrier()
 
-    def measure(E, first_env, steps, warmup):
+    def measure(E, first_env, steps, warmup, dump=None):
         """One stationary batch of E envs on this rank, `steps` timed launches between barriers; returns the wall time of the
-        timed region, the mean per-launch HIP-event time, the metrics buffer, the env and its action ring."""
+        timed region, the mean per-launch HIP-event time (--full only, else None), the metrics buffer, the env and its
+        action ring.  dump: directory for the last timed step's outputs (dump_outputs)."""
         # per-agent outputs the rollout loop does not consume (SURVEY 8d counts none of them in B_alg) are not requested:
         # vehicle positions / speeds for the evaluation plots, the action mask (masking is off in v1), the crashed plane
         masking = dict(abi.default_env_config(args.env_id), **cfg).get("action_masking")  # (v0's default masks: the mask is a result)
@@ -288,13 +366,17 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for t in range(steps):
-            env.step(ring[t % 16])  # one mm_step on torch's current stream
+            last = env.step(ring[t % 16])  # one mm_step on torch's current stream
         env.flush_metrics()  # end of the rollout: fold the per-wave partials (inside the timed region)
         torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
         env.poll_errors()  # (outside the timed region) a latched check_bounds / bad action / kernel loop guard voids the measurement: raise
         metrics = metrics.clone()  # the rollout metrics of the timed region (what follows keeps accumulating into the env's buffer)
+        if dump:  # (before any further step overwrites the env's output buffers)
+            dump_outputs(dump, last, metrics)
+        if not args.full:
+            return elapsed, None, metrics, env, ring, None, skip
         # kernel time for the roofline block, AFTER the timed region: the same launches once more, captured in a hipGraph (no
         # host in the loop) and bracketed by ONE HIP event pair on the launch stream; / launches = the step kernel's duration
         # + the device-side dispatch gap.  Falls back to an eager loop between the same two events.
@@ -327,9 +409,10 @@ def main():
         env.poll_errors()
         return elapsed, kern_ms, metrics, env, ring, (how, after), skip
 
-    elapsed, kern_ms, metrics, env, ring, kern_how, skipped = measure(E, first_env, args.steps, args.warmup)
+    elapsed, kern_ms, metrics, env, ring, kern_how, skipped = measure(E, first_env, args.steps, args.warmup,
+                                                                      dump=args.dump_outputs if rank == 0 else None)
     weak_extra = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_extra:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak_extra:
         # the same kernel with BASELINE's batch on EVERY rank (per-GPU work fixed): reported beside the headline
         w_elapsed, w_kern_ms = measure(args.envs, rank * args.envs, args.steps, 2)[:2]
         wt = torch.tensor([w_elapsed], dtype=torch.float64, device=dev if nccl else "cpu")
@@ -354,29 +437,7 @@ def main():
         present = float(present[0])
     if rank == 0:
         agent_steps = float(E_total) * N * args.steps if present is None else present * args.steps
-        b_alg = algorithmic_bytes_per_agent_step(args.env_id, N)
-        achieved = E * N * b_alg / (kern_ms * 1e-3) / 1e9
-        # HBM bytes per launch and VALU instructions per wave from the committed PMC passes of this workload
-        # (profiles/traffic.json: one row per profiled workload); null for a workload that was not profiled
-        wrow = workload_row(E, N, args.shield, args.env_id, args.qp_solver, args.hdv, args.traffic_density, args.pow2_groups,
-                            args.mixed_traffic)
-        traffic = None if wrow is None else wrow["bytes_per_launch"]
-        # secondary reading (the kernel is VALU-issue bound): instructions from the committed
-        # SQ_INSTS_VALU pass x 4 issue cycles per wave64 instruction, against 1024 SIMDs at the 2.4 GHz peak clock
-        valu = None
-        try:
-            row = wrow  # (the matched workload's own row: by key, not by byte count)
-            if row is None:
-                raise KeyError("workload not profiled")
-            sj = json.load(open(os.path.join(REPO, "profiles", row.get("summary", "r01/step_kernel_summary.json"))))
-            per_wave = sj["pmc_per_launch"]["SQ_INSTS_VALU"] / sj["pmc_per_launch"]["SQ_WAVES"]
-            n_valu = per_wave * (E * 8 // 64 if N <= 8 else E * 16 // 64)
-            ach = n_valu * 4 / (kern_ms * 1e-3) / 1e12
-            valu = {"bound": "valu-issue", "achieved": ach, "peak": 1024 * 2.4e9 / 1e12, "unit": "T SIMD-cycles/s",
-                    "frac": ach / (1024 * 2.4e9 / 1e12), "valu_insts_per_wave": per_wave}
-        except (OSError, KeyError, ValueError, ZeroDivisionError, IndexError, TypeError):
-            pass
-        headline = args.shield == "mass" and not args.hdv and args.env_id.endswith("v1") and N == 8 and args.qp_solver == "exact" and not args.traffic_density
+        headline =args.shield == "mass" and not args.hdv and args.env_id.endswith("v1") and N == 8 and args.qp_solver == "exact" and not args.traffic_density
         if headline and E_total == 65536:
             # BASELINE.json's metric on its own config: 65 536 envs x 8 CAVs in total (one GPU holds the whole batch; 8 GPUs
             # under the default strong scaling are config 5 itself)
@@ -416,31 +477,19 @@ def main():
                                      "ipm": "bit-identical to the restatement of cvxopt's coneqp that answered solvers.qp while the "
                                             "reference produced the ipm_* tapes: INSIDE 1e-5; see qp_fidelity_mode for its throughput"},
                        "parallelism": "env-sharded x%d, no data-path collective" % world},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_unit": "bytes/launch: rocprofv3 PMC passes of this command, 2 x FETCH_SIZE + WRITE_SIZE (gfx950 correction), "
-                                         "committed under profiles/ (see profiles/traffic.json: source)",
-                         "alg_bytes_per_launch": E * N * b_alg,
-                         "kernel": "step_kernel" if args.qp_solver == "exact" or args.shield == "none" or E * (2 if N <= 2 else 4 if N <= 4 else 8 if N <= 8 else 16) // 64 <= 2048
-                         else "4 x step_kernel (phase form) + 3 x sweep_kernel (interior-point step above two fused waves per SIMD)",
-                         "kernel_ms": kern_ms, "alg_bytes_per_agent_step": b_alg,
-                         "kernel_ms_note": "measured AFTER the timed region: %s between ONE HIP event pair on the launch stream, / launches "
-                                           "= the kernel(s) of one mm_step + the device's dispatch gap (the rollout metrics are deferred: no "
-                                           "flush kernel per step); rocprofv3's kernel-trace average of the same command is under profiles/" % kern_how[0],
-                         "mm_steps_after_timed_region": kern_how[1]},
             "rollout_metrics": {"mean_reward": m[0] / max(m[4], 1), "crashed_episodes": m[1],
                                 "mean_speed": m[2] / max(m[4], 1), "env_steps": m[4],
                                 "mean_merge_percent": m[5] / max(m[6], 1), "episodes": m[6], "min_headway": m[7]},
         }
-        if valu is not None:
-            line["roofline_secondary"] = valu
+        if args.full:
+            line.update(roofline_blocks(args, E, N, kern_ms, kern_how))
         if args.rehearse_on_one_gpu:
             line["rehearsal"] = "all %d ranks on cuda:0, gloo collectives: NOT a scaling measurement" % world
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only
             line["cpu_baseline"] = cpu_baseline(args, args.env_id, cfg, kw)
         if weak_extra is not None:
             line["weak_scaling"] = weak_extra
-        if headline and world == 1 and not args.no_fidelity_line:
+        if args.full and headline and world == 1 and not args.no_fidelity_line:
             # the same workload on the product's DEFAULT numerics -- the shield's QP through cvxopt's interior-point iteration
             # (DESIGN.md 3), the mode inside north_star's 1e-5 -- as a peer of `value` at the top level of the line, with its own
             # roofline block below
@@ -449,7 +498,7 @@ def main():
             line["value_within_tolerance_note"] = ("qp_solver=ipm (the default of every entry point): %.3f ms per step; `value` is qp_solver=exact "
                                                    "(explicit opt-in), outside 1e-5 of the interior-point iterate" % fid["ms_per_step"])
             line["qp_fidelity_mode"] = fid
-        if headline and world == 1 and not args.all_outputs and not args.no_fidelity_line:
+        if args.full and headline and world == 1 and not args.all_outputs and not args.no_fidelity_line:
             # like-for-like with rounds 1-2 and with the reference, whose step always produces the whole info dict: every output
             # written, metrics folded behind every step
             ao = VecMergeEnv(E, N, env_id=args.env_id, config=cfg, device=dev, first_env=first_env, **kw)

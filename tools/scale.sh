@@ -12,10 +12,10 @@ NG=$(python3 -c 'import torch; print(torch.cuda.device_count())')
 for n in 1 2 4 8; do
   [ "$n" -le "$NG" ] || { echo "skip N=$n (only $NG GPUs)"; continue; }
   if [ "$n" -eq 1 ]; then
-    python3 "$R/bench.py" --gpus 1 --steps 200 --warmup 10 --scaling "$MODE" --no-cpu-baseline "$@" | tail -1 >> "$OUT"
+    python3 "$R/bench.py" --gpus 1 --steps 200 --warmup 10 --scaling "$MODE" --full --no-cpu-baseline "$@" | tail -1 >> "$OUT"
   else
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      "$R/bench.py" --gpus "$n" --steps 200 --warmup 10 --scaling "$MODE" --no-cpu-baseline "$@" | tail -1 >> "$OUT"
+      "$R/bench.py" --gpus "$n" --steps 200 --warmup 10 --scaling "$MODE" --full --no-cpu-baseline "$@" | tail -1 >> "$OUT"
   fi
   tail -1 "$OUT" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("N=%d  %.3e agent-steps/s  %.3f ms/step  (%s)" % (d["n_gpus"], d["value"], d["ms_per_step"], d["scaling"]))'
 done
