@@ -1,0 +1,52 @@
+/*
+ * mm_supervisor.h -- the reference's action-replacement safety supervisor on the device.
+ *
+ * safety_guarantee = "priority" (abstract.py:460-462 -> central_layer.py:16-178 safety_supervisor, the reference's
+ * default) rewrites the joint action before the env steps: controlled vehicles are taken in priority order, each one
+ * rolled (simulation_frequency // policy_frequency) * n_step sub-steps ahead together with its four lane neighbours on a
+ * copy of the env, and an action whose lookahead crashes is replaced by the available action with the largest safety
+ * room (abstract.py:219-280).  Exported by libmm_hip.so only; the CPU oracle has no twin of it.
+ *
+ * Scope: merge-multi-agent-v0, CAV-only and mixed traffic.  HDVs (MM_B_KIND 2, IDMVehicle) in the lookahead follow
+ * idm_controller.py (generate_actions once at its first sub-step, two draws; a crashed HDV's points alias its live
+ * position).  "dmc" and v1 are not covered (the reference's own v1 supervisor fails on IDMVehicleHist HDVs).
+ */
+#ifndef MM_SUPERVISOR_H
+#define MM_SUPERVISOR_H
+
+#include <stdint.h>
+
+#include "mm_abi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MM_SUP_PRIORITY 1 /* central_layer.py safety_supervisor(env, actions, is_priority=True) */
+
+/* Bytes of the caller-owned lookahead scratch for E envs x N slots and a horizon of n_step policy steps of sub_steps
+ * simulation steps each (simulation_frequency // policy_frequency: 3 at the default 15 / 5 Hz). */
+int32_t mm_supervise_scratch_bytes(int32_t E, int32_t N, int32_t n_step, int32_t sub_steps, uint64_t *bytes);
+
+/*
+ * new_actions = safety_supervisor(env, actions) for every env of the handle, on its CURRENT state (nothing in the state
+ * buffer changes).  actions / new_actions: DEV int32[E][N] (may not alias); slots that are absent or not controlled
+ * are copied through.  Codes outside 0..4 pass through unless the lookahead replaces them.
+ * uniforms: DEV double[E][uniform_stride] (stride >= 9 * N): the np.random.rand() values the reference would draw, in
+ *           its order -- one priority tie-breaker per controlled vehicle, in controlled order, then two per HDV
+ *           whose actions a lookahead generates, as they happen (at most N_cav + 8 N_cav <= 9 N).  NULL: the device draws
+ *           them (Philox4x32-10 keyed on the env's seed plane, MM_E_EPISODE, MM_E_STEPS and the draw index), so a
+ *           checkpoint, a sharded batch (first_env) or a graph replay draws what an unbroken run would.
+ * n_draws:  DEV int32[E] or NULL -- uniforms each env consumed.
+ * scratch:  DEV, >= mm_supervise_scratch_bytes(E, N, n_step, sub_steps), 8-byte aligned, contents irrelevant.
+ * Only enqueues work on `stream` (no allocation, no synchronisation): graph-capturable.
+ * MM_ERR_INVALID_ARG: v1 handle, unknown kind, n_step < 1, stride < 9 * N, scratch too small, NULL actions / outputs.
+ */
+int32_t mm_supervise(MMHandle h, int32_t kind, int32_t n_step, const int32_t *actions, const double *uniforms,
+                     int32_t uniform_stride, void *scratch, uint64_t scratch_bytes, int32_t *new_actions,
+                     int32_t *n_draws, MMStream stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MM_SUPERVISOR_H */

@@ -83,6 +83,19 @@ def check_supervisor(value):
             "this path: set env.config['safety_guarantee'] to 'none' or 'cbf-*' before stepping" % (value,))
 
 
+SUP_NONE, SUP_PRIORITY = 0, 1  # include/mm_supervisor.h
+
+
+def supervisor_id(value, env_kind):
+    """config["safety_guarantee"] -> the supervisor AbstractEnv.step runs (abstract.py:460-464): SUP_PRIORITY for "priority"
+    on merge-multi-agent-v0 (mm_supervise, include/mm_supervisor.h), SUP_NONE for everything without one.  "dmc" and
+    "priority" on v1 still raise NotImplementedError through check_supervisor."""
+    if value == "priority" and env_kind == ENV_V0:
+        return SUP_PRIORITY
+    check_supervisor(value)
+    return SUP_NONE
+
+
 def shield_from_safety_guarantee(value):
     """config["safety_guarantee"] -> VEHICLE-level shield id, as safe_controller.py:229-241 +
     decentral_layer.py:767-817 dispatch it ("priority" / "dmc" have none: their supervisor sits in
@@ -217,6 +230,13 @@ class CLib(object):
         for s in self.SYMBOLS:
             if s not in ("mm_abi_version", "mm_last_error"):
                 getattr(lib, s).restype = i32
+        # entry points only libmm_hip.so exports (the oracle has no twin): bound when present, absent -> None
+        self.has_supervisor = hasattr(lib, "mm_supervise")
+        if self.has_supervisor:
+            lib.mm_supervise_scratch_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(u64)]
+            lib.mm_supervise_scratch_bytes.restype = i32
+            lib.mm_supervise.argtypes = [vp, i32, i32, vp, vp, i32, vp, u64, vp, vp, vp]
+            lib.mm_supervise.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -230,6 +250,19 @@ class CLib(object):
         if rc == MM_ERR_NOT_READY:
             raise NotImplementedError(msg or "The road and vehicle must be initialized in the environment implementation")
         raise RuntimeError("mm error %d: %s" % (rc, msg))
+
+    def supervise_scratch_bytes(self, E, N, n_step, sub_steps=3):
+        """Bytes of the lookahead scratch mm_supervise needs (include/mm_supervisor.h); sub_steps =
+        simulation_frequency // policy_frequency."""
+        self.require_supervisor()
+        b = C.c_uint64()
+        self.check(self.lib.mm_supervise_scratch_bytes(E, N, n_step, sub_steps, C.byref(b)))
+        return b.value
+
+    def require_supervisor(self):
+        if not self.has_supervisor:
+            raise NotImplementedError("%s does not export mm_supervise: safety_guarantee='priority' needs the HIP library"
+                                      % os.path.basename(self.path))
 
     def state_layout(self, E, N):
         lay = MMStateLayout()

@@ -237,7 +237,20 @@ class MergeEnvCompat(object):
         b = self._b
         act = torch.ones(1, MAX_VEHICLES, dtype=torch.int32)
         act[0, :n] = torch.tensor(action, dtype=torch.int32)
-        obs, reward, done, out = b.step(act.to(b.device))
+        sup = abi.supervisor_id(self.config.get("safety_guarantee"), abi.ENV_V1 if self.env_id == "merge-multi-agent-v1" else abi.ENV_V0)
+        if sup != abi.SUP_NONE:
+            # safety_supervisor draws np.random.rand() from the global stream (central_layer.py:58): hand the device the next
+            # 9 N values, then advance the stream by exactly the number it used, so that the caller's own draws
+            # (MAPPO's np.random.choice) continue where they would in the reference
+            st = np.random.get_state()
+            u = np.random.random_sample(9 * b.N)
+            np.random.set_state(st)
+            obs, reward, done, out = b.step(act.to(b.device), uniforms=torch.as_tensor(u)[None])
+            n_used = int(b.n_draws[0])
+            if n_used > 0:
+                np.random.random_sample(n_used)
+        else:
+            obs, reward, done, out = b.step(act.to(b.device))
         b.poll_errors()  # check_bounds' ValueError (cbf.py:87-96) / an action outside 0..4, raised like the reference does
         if self.store_profile:
             self._log_profiles(b)
@@ -250,7 +263,7 @@ class MergeEnvCompat(object):
         self.vehicle_pos.append([float(p) for p in o["agents_info"][:n, 0]])
         info = {
             "speed": float(speeds[0]), "crashed": bool(o["crashed"][0]), "action": action,
-            "new_action": action, "action_mask": o["action_mask"][:n].astype(np.int64),
+            "new_action": tuple(int(a) for a in o["new_action"][:n]) if "new_action" in o else action, "action_mask": o["action_mask"][:n].astype(np.int64),
             "average_speed": float(o["average_speed"]),
             "vehicle_speed": np.array(self.vehicle_speed), "vehicle_position": np.array(self.vehicle_pos),
             "agents_dones": tuple(bool(d) for d in o["agents_dones"][:n]),

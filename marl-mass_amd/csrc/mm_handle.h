@@ -1,0 +1,19 @@
+// mm_handle.h -- the part of the library's handle that translation units other than mm_kernels.hip read.
+//
+// struct MMHandle_ (mm_kernels.hip) derives from MMHandleHead; other translation units (mm_supervisor.hip) never see the
+// full struct and reach these members only through mm_handle_head().
+#pragma once
+#include <stdint.h>
+
+#include "../../include/mm_abi.h"
+
+struct MMHandleHead {
+  MMConfig cfg;
+  int E, N, device;
+  unsigned char *state;
+  MMStateLayout lay;
+  long long first_env;
+};
+
+// defined in mm_kernels.hip; not exported from the shared library
+__attribute__((visibility("hidden"))) const MMHandleHead *mm_handle_head(MMHandle h);

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "mm_device.h"
+#include "mm_handle.h"
 #define MM_COUNTS_FN __host__ __device__ inline
 #include "../../include/mm_counts.h"
 
@@ -2846,12 +2847,7 @@ __global__ __launch_bounds__(256) void metrics_flush_kernel(double *partial, lon
 // ------------------------------------------------------------------------------------------------
 static int group_size(int N) { return N <= 2 ? 2 : (N <= 4 ? 4 : (N <= 8 ? 8 : 16)); }
 
-struct MMHandle_ {
-  MMConfig cfg;
-  int E, N, device;
-  unsigned char *state;
-  MMStateLayout lay;
-  long long first_env;
+struct MMHandle_ : MMHandleHead {  // cfg, E, N, device, state, lay, first_env: mm_handle.h
   double *metrics;          // caller's 8 doubles (mm_set_metrics_buffer) or NULL
   double *metrics_partial;  // [waves of a step launch][8], device, owned by the handle
   int metrics_deferred;     // mm_defer_metrics: the partials accumulate across launches, folded by mm_flush_metrics only
@@ -2920,6 +2916,8 @@ static long long step_launch_waves_now(const MMHandle h) {
 static uint64_t align256(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
 
 extern "C" int32_t mm_abi_version(void) { return MM_ABI_VERSION; }
+
+const MMHandleHead *mm_handle_head(MMHandle h) { return h; }
 
 extern "C" int32_t mm_state_layout(int32_t E, int32_t N, MMStateLayout *out) {
   if (!out || E <= 0 || N <= 0 || N > MM_MAX_AGENTS) return MM_ERR_INVALID_ARG;

@@ -92,11 +92,60 @@ class BatchedMergeEnv(object):
         for k, t in self.out.items():
             setattr(self._step_out, k, t.data_ptr())
         self._step_out.trace = self.trace.data_ptr() if trace else None
+        self._setup_supervisor()
         self._h = C.c_void_p()
         index = self.device.index if self.device.type == "cuda" else 0
         clib.check(clib.lib.mm_create(C.byref(self._cfg), self.E, self.N, index or 0,
                                       _ptr(self.state), lay.total_bytes, int(first_env),
                                       C.byref(self._h)))
+
+    # -- safety supervisor (safety_guarantee = "priority", include/mm_supervisor.h) ------------
+    def _setup_supervisor(self):
+        """The supervisor the config selects (_cabi.supervisor_id) and, for "priority", its lookahead scratch and output
+        buffers -- allocated here (construction / configure), never inside step().  Nothing raises here: a configuration
+        the supervisor cannot serve (dmc, v1, a library without mm_supervise) raises NotImplementedError from step() /
+        supervise()."""
+        self._sup, self._sup_err = abi.SUP_NONE, None
+        try:
+            sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)
+        except NotImplementedError:
+            return
+        if sup == abi.SUP_NONE:
+            return
+        if not self.clib.has_supervisor:
+            self._sup_err = "%s does not export mm_supervise: safety_guarantee='priority' needs the HIP library" % (
+                os.path.basename(self.clib.path),)
+            return
+        self._sup = sup
+        self.n_step = int(self.config.get("n_step", 6))
+        ratio = self._cfg.simulation_frequency // max(1, self._cfg.policy_frequency)
+        n = self.clib.supervise_scratch_bytes(self.E, self.N, self.n_step, max(1, ratio)) // 8
+        if getattr(self, "_sup_scratch", None) is None or self._sup_scratch.numel() < n:
+            self._sup_scratch = torch.empty(n, dtype=torch.float64, device=self.device)
+        if getattr(self, "new_action", None) is None:
+            self.new_action = torch.zeros(self.E, self.N, dtype=torch.int32, device=self.device)
+            self.n_draws = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+
+    def supervise(self, actions, uniforms=None):
+        """new_action = safety_supervisor(env, actions) (central_layer.py:16-178) on the current state, without stepping.
+        uniforms: optional [E, >= 9 N] float64 -- the np.random.rand() values in the reference's order; None: device Philox.
+        Returns (new_action int32 [E, N], n_draws int32 [E]) -- buffers owned by the env, rewritten by the next call."""
+        if self._sup == abi.SUP_NONE:
+            abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)  # raises for dmc / v1 priority
+            if self._sup_err:
+                raise NotImplementedError(self._sup_err)
+            raise ValueError("safety_guarantee=%r has no supervisor" % (self.config.get("safety_guarantee"),))
+        if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(self.device, torch.int32).contiguous()
+        assert actions.numel() == self.E * self.N
+        stride = 0
+        if uniforms is not None:
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float64, device=self.device).reshape(self.E, -1).contiguous()
+            stride = uniforms.shape[1]
+        self.clib.check(self.clib.lib.mm_supervise(self._h, self._sup, self.n_step, _ptr(actions), _ptr(uniforms), stride,
+                                                   _ptr(self._sup_scratch), self._sup_scratch.numel() * 8,
+                                                   _ptr(self.new_action), _ptr(self.n_draws), self._stream()), self._h)
+        return self.new_action, self.n_draws
 
     # -- configuration ------------------------------------------------------------------
     def _make_cfg(self):
@@ -115,6 +164,7 @@ class BatchedMergeEnv(object):
         self._cfg = self._make_cfg()
         self.T = int(self.config["duration"] * self.config["policy_frequency"])
         self.clib.check(self.clib.lib.mm_set_config(self._h, C.byref(self._cfg)), self._h)
+        self._setup_supervisor()
 
     def _stream(self):
         if self.device.type == "cuda":
@@ -165,17 +215,21 @@ class BatchedMergeEnv(object):
                                                  self._stream()), self._h)
         return self.obs, self.avail
 
-    def step(self, actions, obs_out=None, out=None):
+    def step(self, actions, obs_out=None, out=None, uniforms=None):
         """MergeEnv.step (merge_env_v1.py:126-166) for every env; actions int32 [E, N] in 0..4.
         obs_out: optional caller buffer (same shape / dtype / device as self.obs, contiguous) the new
         observation is written to instead of self.obs -- a rollout hands over its states[t + 1] slot.
         out: optional {key: tensor} for keys of the info dict (same shape / dtype / device as self.out[key], contiguous):
         this step writes those outputs there instead of into self.out -- a rollout hands over rewards[t], dones[t], ...
-        and saves a copy kernel per quantity and step; the returned info carries the given tensors under those keys."""
-        abi.check_supervisor(self.config.get("safety_guarantee"))
+        and saves a copy kernel per quantity and step; the returned info carries the given tensors under those keys.
+        With safety_guarantee = "priority" (v0) the joint action first goes through the supervisor (supervise()) and the env
+        steps on its result, which info["new_action"] carries (int32 [E, N]); uniforms: see supervise()."""
+        sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(self.device, torch.int32).contiguous()
         assert actions.numel() == self.E * self.N
+        if sup != abi.SUP_NONE:
+            actions, _ = self.supervise(actions, uniforms)
         obs, info = self.obs, self.out
         if obs_out is not None:
             assert obs_out.shape == self.obs.shape and obs_out.dtype == self.obs.dtype and obs_out.device == self.obs.device \
@@ -190,6 +244,9 @@ class BatchedMergeEnv(object):
             for k, t in out.items():
                 setattr(self._step_out, k, t.data_ptr())
                 info[k] = t
+        if sup != abi.SUP_NONE:
+            info = dict(info)
+            info["new_action"] = self.new_action
         try:
             self.clib.check(self.clib.lib.mm_step(self._h, _ptr(actions), C.byref(self._step_out),
                                                   self._stream()), self._h)
