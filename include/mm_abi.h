@@ -39,6 +39,8 @@ extern "C" {
 /* env_kind: which registered env the handle mirrors (merge_env_v1.py:681-689) */
 #define MM_ENV_V0 0 /* merge-multi-agent-v0: MDPVehicle, Kinematics obs (5 features, n_s = 25) */
 #define MM_ENV_V1 1 /* merge-multi-agent-v1: MDPLCVehicle, KinematicLC obs (6 features, n_s = 30) */
+#define MM_ENV_HDV_V1 2 /* merge-multi-agent-hdv-v1 (MergeEnvLCHDV, merge_env_v1.py:552-674): every vehicle an IDMVehicleHist
+                           (IDM + MOBIL), none controlled; every vehicle observes (KinematicLC, n_s = 30); no shield, no actions */
 
 /* shield: config["safety_guarantee"] after `.split("-")[1]` (safe_controller.py:241) */
 #define MM_SHIELD_NONE 0
@@ -118,7 +120,7 @@ typedef struct MMStateLayout {
  */
 typedef struct MMConfig {
   int32_t abi_version;          /* MM_ABI_VERSION */
-  int32_t env_kind;             /* MM_ENV_V0 | MM_ENV_V1 */
+  int32_t env_kind;             /* MM_ENV_V0 | MM_ENV_V1 | MM_ENV_HDV_V1 */
   int32_t shield;               /* MM_SHIELD_* ; ignored (none) for MM_ENV_V0 */
   int32_t simulation_frequency; /* 15 */
   int32_t policy_frequency;     /* 5  */
@@ -161,7 +163,9 @@ typedef struct MMConfig {
                                          {1,2,3} / {2,3,4} / CAV {4,5,6}, HDV {3,4,5} (ragged batch: unused slots are
                                          absent, MM_B_KIND = 0); N is the slot capacity and must hold the largest draw */
   int32_t mixed_traffic;        /* with traffic_density > 0: 1 = the drawn HDVs are IDM/MOBIL vehicles, 0 = they become CAVs
-                                   (config["mixed_traffic"] False / traffic_type "cav": num_CAV += num_HDV, :206-209) */
+                                   (config["mixed_traffic"] False / traffic_type "cav": num_CAV += num_HDV, :206-209),
+                                   2 = traffic_type "av", 3 = traffic_type "hdv" (MM_ENV_HDV_V1 only: every drawn vehicle an
+                                   HDV, include/mm_counts.h) */
   int32_t num_cav;              /* with traffic_density > 0: reset(num_CAV=...) override of the CAV draw, 0 = draw (:185,192,199) */
   int32_t reserved1;
 } MMConfig;
@@ -261,6 +265,10 @@ int32_t mm_observe(MMHandle h, void *obs, uint8_t *avail, MMStream stream);
 /*
  * step(): MergeEnv.step (merge_env_v1.py:126-166).  actions: DEV int32[E][N] in 0..4.
  * `out` is a HOST struct of DEV pointers.
+ * MM_ENV_HDV_V1 (MergeEnvLCHDV.step, merge_env_v1.py:604-666): `actions` is not read and may be NULL; every vehicle
+ * observes, reward is the mean _agent_reward over all vehicles, done = any vehicle crashed or steps >= T (no x < 0 clause),
+ * average_speed = traffic_speed = mean speed of all vehicles, min_headway over all vehicles (:587-602), merge_percent 100
+ * at the terminal step (n_merge = 0); agents_* / regional_rewards / action_mask are not part of its info (leave them NULL).
  */
 int32_t mm_step(MMHandle h, const int32_t *actions, const MMStepOut *out, MMStream stream);
 

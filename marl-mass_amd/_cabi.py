@@ -9,7 +9,9 @@ import os
 
 MM_ABI_VERSION = 6
 MM_MAX_AGENTS = 16
-ENV_V0, ENV_V1 = 0, 1
+ENV_V0, ENV_V1, ENV_HDV_V1 = 0, 1, 2
+ENV_IDS = {"merge-multi-agent-v0": ENV_V0, "merge-multi-agent-v1": ENV_V1, "merge-multi-agent-hdv-v1": ENV_HDV_V1}
+MIXED_CAV, MIXED_MIXED, MIXED_AV, MIXED_HDV = 0, 1, 2, 3  # MMConfig.mixed_traffic count codes (include/mm_counts.h)
 SHIELD_NONE, SHIELD_HSS, SHIELD_MASS = 0, 1, 2
 
 # plane indices (keep in sync with include/mm_abi.h; checked by tests/test_abi.py)
@@ -89,17 +91,23 @@ SUP_NONE, SUP_PRIORITY = 0, 1  # include/mm_supervisor.h
 def supervisor_id(value, env_kind):
     """config["safety_guarantee"] -> the supervisor AbstractEnv.step runs (abstract.py:460-464): SUP_PRIORITY for "priority"
     on merge-multi-agent-v0 (mm_supervise, include/mm_supervisor.h), SUP_NONE for everything without one.  "dmc" and
-    "priority" on v1 still raise NotImplementedError through check_supervisor."""
+    "priority" on v1 still raise NotImplementedError through check_supervisor.  merge-multi-agent-hdv-v1 runs none whatever
+    the setting: MergeEnvLCHDV.step never calls a supervisor (merge_env_v1.py:604-666)."""
+    if env_kind == ENV_HDV_V1:
+        return SUP_NONE
     if value == "priority" and env_kind == ENV_V0:
         return SUP_PRIORITY
     check_supervisor(value)
     return SUP_NONE
 
 
-def shield_from_safety_guarantee(value):
+def shield_from_safety_guarantee(value, env_kind=None):
     """config["safety_guarantee"] -> VEHICLE-level shield id, as safe_controller.py:229-241 +
     decentral_layer.py:767-817 dispatch it ("priority" / "dmc" have none: their supervisor sits in
-    AbstractEnv.step, see check_supervisor).  Unknown "cbf-*" types raise ValueError like safety_layer does."""
+    AbstractEnv.step, see check_supervisor).  Unknown "cbf-*" types raise ValueError like safety_layer does.
+    env_kind ENV_HDV_V1: none whatever the setting (no controlled vehicle carries a shield)."""
+    if env_kind == ENV_HDV_V1:
+        return SHIELD_NONE
     if value in (None, "none") or value in SUPERVISED or "cbf-" not in value:
         return SHIELD_NONE
     kind = value.split("-")[1]
@@ -122,9 +130,25 @@ def default_env_config(env_id):
     if env_id == "merge-multi-agent-v1":
         cfg.update({"action_masking": False, "lateral_control": "steer", "traffic_type": "cav",
                     "agent_reward": "default"})
+    elif env_id == "merge-multi-agent-hdv-v1":  # MergeEnvLCHDV.default_config (merge_env_v1.py:556-580)
+        cfg.update({"action_masking": False, "lateral_control": "steer", "traffic_type": "hdv", "agent_reward": "default",
+                    "other_vehicles_type": "highway_env.vehicle.behavior.IDMVehicleHist"})
     elif env_id != "merge-multi-agent-v0":
-        raise ValueError("unsupported env id %r (hot path covers merge-multi-agent-v0 / -v1)" % env_id)
+        raise ValueError("unsupported env id %r (hot path covers merge-multi-agent-v0 / -v1 / -hdv-v1)" % env_id)
     return cfg
+
+
+def env_kind(env_id):
+    """Registered env id -> MMConfig.env_kind (merge_env_v1.py:681-694)."""
+    try:
+        return ENV_IDS[env_id]
+    except KeyError:
+        raise ValueError("unsupported env id %r (hot path covers merge-multi-agent-v0 / -v1 / -hdv-v1)" % (env_id,))
+
+
+def obs_features(env_id):
+    """Features per observation row: Kinematics (v0) 5, KinematicLC (v1, hdv-v1) 6 (observation.py:132,228-273)."""
+    return 5 if env_kind(env_id) == ENV_V0 else 6
 
 
 def qp_solver_id(name):
@@ -141,7 +165,7 @@ def make_config(env_id, config, cbf_eta=0.0, cbf_tau=None, auto_reset=False, obs
     """env.config dict (+ CBFType.GAMMA_B / CBFType.TAU, run_mappo.py:138-139) -> MMConfig."""
     c = MMConfig()
     c.abi_version = MM_ABI_VERSION
-    c.env_kind = ENV_V1 if env_id == "merge-multi-agent-v1" else ENV_V0
+    c.env_kind = ENV_IDS.get(env_id, ENV_V0)
     c.shield = shield_from_safety_guarantee(config.get("safety_guarantee")) if c.env_kind == ENV_V1 else SHIELD_NONE
     lat = config.get("lateral_control", "steer") if c.env_kind == ENV_V1 else "steer"
     if lat not in ("steer", "steer_vel"):  # safe_controller.py:181-184
@@ -185,6 +209,11 @@ def make_config(env_id, config, cbf_eta=0.0, cbf_tau=None, auto_reset=False, obs
             mixed = 2
         elif tt == "hdv" and draw_counts:  # no controlled vehicle at all: nothing to step or observe on this path
             raise NotImplementedError("traffic_type='hdv' (zero controlled vehicles) is not supported by the device-side count draw")
+    elif c.env_kind == ENV_HDV_V1:  # MergeEnvLCHDV: num_HDV = num_CAV + num_HDV, num_CAV = 0 (merge_env_v1.py:490-494)
+        if config.get("traffic_type", "hdv") != "hdv":
+            raise NotImplementedError("merge-multi-agent-hdv-v1 is supported with traffic_type='hdv' only")
+        mixed = MIXED_HDV
+        c.n_hdv = 0  # (every vehicle is an HDV: the library takes no separate HDV count for this env)
     c.mixed_traffic = mixed
     c.num_cav = int(num_cav)
     return c

@@ -86,8 +86,69 @@ class _Road(object):
         self.objects = [_Obstacle()]
 
 
+def draw_counts(cfg, num_CAV=0):
+    """MergeEnv._num_vehicles (merge_env_v1.py:180-211) on the GLOBAL numpy RNG."""
+    num_HDV = 0
+    lo_hi = {1: ((1, 4), (1, 4)), 2: ((2, 5), (2, 5)), 3: ((4, 7), (3, 6))}.get(cfg["traffic_density"])
+    if lo_hi:
+        if num_CAV == 0:
+            num_CAV = np.random.choice(np.arange(*lo_hi[0]), 1)[0]
+        num_HDV = np.random.choice(np.arange(*lo_hi[1]), 1)[0]
+    if cfg.get("mixed_traffic") is not None and not cfg["mixed_traffic"]:
+        num_CAV, num_HDV = num_CAV + num_HDV, 0
+    return int(num_CAV), int(num_HDV)
+
+
+def make_vehicles(num_CAV, num_HDV):
+    """Spawn draw of merge_env_v1.py:265-364 on the GLOBAL numpy RNG.  What has to match the reference is the
+    sequence of RNG calls (a MAPPO loop seeded the same way must see the same episodes and the same
+    downstream stream): per vehicle class (CAVs, then HDVs) one `choice(2)` iff the class has exactly one
+    vehicle, then `choice(free slots, k, replace=False)` for the main road and for the ramp; finally one
+    `rand(n)` for the speeds and one for the position noise, consumed in creation order (CAVs main, CAVs
+    ramp, HDVs main, HDVs ramp).  Returns x, y, speed in that order and the number of ramp CAVs."""
+    n_all = num_CAV + num_HDV
+    if n_all > MAX_VEHICLES:
+        raise ValueError("at most %d vehicles (6 + 6 spawn slots)" % MAX_VEHICLES)
+    free = {"main": [10 + 50 * k for k in range(6)], "ramp": [5 + 50 * k for k in range(6)]}
+    lane_y = {"main": 0.0, "ramp": 6.5 + 4}
+    groups = []  # (road, slots) in creation order
+    n_ramp_cav = 0
+    for cls, count in (("cav", num_CAV), ("hdv", num_HDV)):
+        on_main = count // 2 if count != 1 else np.random.choice(2)
+        split = {"main": on_main, "ramp": count - on_main}
+        if cls == "cav":
+            n_ramp_cav = split["ramp"]
+        for road in ("main", "ramp"):
+            picked = [int(p) for p in np.random.choice(free[road], split[road], replace=False)]
+            free[road] = [p for p in free[road] if p not in picked]
+            groups.append((road, picked))
+    speed = np.random.rand(n_all) * 2 + 25
+    noise = np.random.rand(n_all) * 8 - 4
+    slot = np.array([p for _, picked in groups for p in picked], dtype=np.float64)
+    y = np.array([lane_y[road] for road, picked in groups for _ in picked], dtype=np.float64)
+    return slot + noise, y, speed.astype(np.float64), int(n_ramp_cav)
+
+
+def hdv_spawn(config, seed, num_CAV=0):
+    """The spawn of merge-multi-agent-hdv-v1's reset(is_training=False, testing_seeds=seed) (abstract.py:176-187,
+    merge_env_v1.py:490-494,265-364): reseeds the global numpy / random streams like the reference and replays its draws.
+    Returns x, y, speed of the n vehicles in creation order (all HDVs, heading 0)."""
+    np.random.seed(seed)
+    random.seed(seed)
+    if config.get("traffic_type", "hdv") != "hdv":
+        raise NotImplementedError("merge-multi-agent-hdv-v1 is supported with traffic_type='hdv' only")
+    nc, nh = draw_counts(config, num_CAV)
+    x, y, v, _ = make_vehicles(0, nc + nh)
+    return x, y, v
+
+
 class MergeEnvCompat(object):
-    """gym.make("merge-multi-agent-v0" | "-v1") replacement; see module docstring."""
+    """gym.make("merge-multi-agent-v0" | "-v1" | "merge-multi-agent-hdv-v1") replacement; see module docstring.
+
+    merge-multi-agent-hdv-v1 (MergeEnvLCHDV, merge_env_v1.py:552-674): every vehicle an IDMVehicleHist, none controlled.
+    reset() returns (obs [n][30] of every road vehicle, available_actions of shape (0,)), step(None) the reference's
+    (obs [n][5][6], reward, terminal, info) with info speed / crashed of road.vehicles[0], average_speed, traffic_speed,
+    min_headway and, at the terminal step, merge_percent."""
 
     n_a = 5
     metadata = {"render.modes": []}
@@ -102,7 +163,8 @@ class MergeEnvCompat(object):
         self.config = abi.default_env_config(env_id)
         if config:
             self.config.update(config)
-        self.n_s = 30 if env_id == "merge-multi-agent-v1" else 25
+        self.hdv_env = abi.env_kind(env_id) == abi.ENV_HDV_V1
+        self.n_s = 5 * abi.obs_features(env_id)
         self.seed = self.config["seed"]
         self.ACTIONS_ALL = {"LANE_LEFT": 0, "IDLE": 1, "LANE_RIGHT": 2, "FASTER": 3, "SLOWER": 4}
         self.ends = [220, 100, 100, 1000]
@@ -127,6 +189,11 @@ class MergeEnvCompat(object):
     # -- spawn: merge_env_v1.py:180-211 (+ :476-495 for v1) -------------------------------
     def _num_vehicles(self, num_CAV=0):
         cfg = self.config
+        if self.hdv_env:  # MergeEnvLCHDV: traffic_type "hdv" (merge_env_v1.py:490-494)
+            if cfg.get("traffic_type", "hdv") != "hdv":
+                raise NotImplementedError("merge-multi-agent-hdv-v1 is supported with traffic_type='hdv' only")
+            num_CAV, num_HDV = self._draw_counts(num_CAV)
+            return 0, num_CAV + num_HDV
         if self.env_id == "merge-multi-agent-v1":
             tt = cfg.get("traffic_type", "cav")
             if tt == "mixed":
@@ -141,45 +208,10 @@ class MergeEnvCompat(object):
         return self._draw_counts(num_CAV)
 
     def _draw_counts(self, num_CAV=0):
-        cfg = self.config
-        num_HDV = 0
-        lo_hi = {1: ((1, 4), (1, 4)), 2: ((2, 5), (2, 5)), 3: ((4, 7), (3, 6))}.get(cfg["traffic_density"])
-        if lo_hi:
-            if num_CAV == 0:
-                num_CAV = np.random.choice(np.arange(*lo_hi[0]), 1)[0]
-            num_HDV = np.random.choice(np.arange(*lo_hi[1]), 1)[0]
-        if cfg.get("mixed_traffic") is not None and not cfg["mixed_traffic"]:
-            num_CAV, num_HDV = num_CAV + num_HDV, 0
-        return int(num_CAV), int(num_HDV)
+        return draw_counts(self.config, num_CAV)
 
     def _make_vehicles(self, num_CAV, num_HDV):
-        """Spawn draw of merge_env_v1.py:265-364 on the GLOBAL numpy RNG.  What has to match the reference is the
-        sequence of RNG calls (a MAPPO loop seeded the same way must see the same episodes and the same
-        downstream stream): per vehicle class (CAVs, then HDVs) one `choice(2)` iff the class has exactly one
-        vehicle, then `choice(free slots, k, replace=False)` for the main road and for the ramp; finally one
-        `rand(n)` for the speeds and one for the position noise, consumed in creation order (CAVs main, CAVs
-        ramp, HDVs main, HDVs ramp).  Returns x, y, speed in that order and the number of ramp CAVs."""
-        n_all = num_CAV + num_HDV
-        if n_all > MAX_VEHICLES:
-            raise ValueError("at most %d vehicles (6 + 6 spawn slots)" % MAX_VEHICLES)
-        free = {"main": [10 + 50 * k for k in range(6)], "ramp": [5 + 50 * k for k in range(6)]}
-        lane_y = {"main": 0.0, "ramp": 6.5 + 4}
-        groups = []  # (road, slots) in creation order
-        n_ramp_cav = 0
-        for cls, count in (("cav", num_CAV), ("hdv", num_HDV)):
-            on_main = count // 2 if count != 1 else np.random.choice(2)
-            split = {"main": on_main, "ramp": count - on_main}
-            if cls == "cav":
-                n_ramp_cav = split["ramp"]
-            for road in ("main", "ramp"):
-                picked = [int(p) for p in np.random.choice(free[road], split[road], replace=False)]
-                free[road] = [p for p in free[road] if p not in picked]
-                groups.append((road, picked))
-        speed = np.random.rand(n_all) * 2 + 25
-        noise = np.random.rand(n_all) * 8 - 4
-        slot = np.array([p for _, picked in groups for p in picked], dtype=np.float64)
-        y = np.array([lane_y[road] for road, picked in groups for _ in picked], dtype=np.float64)
-        return slot + noise, y, speed.astype(np.float64), int(n_ramp_cav)
+        return make_vehicles(num_CAV, num_HDV)
 
     def _backend(self):
         if self._b is None:
@@ -206,7 +238,8 @@ class MergeEnvCompat(object):
         self.n_merge = n_merge
         self.T = int(self.config["duration"] * self.config["policy_frequency"])
         b = self._backend()
-        b.configure(self.config, cbf_eta=CBFType.GAMMA_B, cbf_tau=CBFType.TAU, n_hdv=n_hdv, qp_solver=CBFType.QP_SOLVER)
+        b.configure(self.config, cbf_eta=CBFType.GAMMA_B, cbf_tau=CBFType.TAU, n_hdv=0 if self.hdv_env else n_hdv,
+                    qp_solver=CBFType.QP_SOLVER)
         n_all = len(x)
         self._n = n = n_cav
         pad = lambda a, fill: np.concatenate([a, np.full(MAX_VEHICLES - n_all, fill)])  # noqa: E731
@@ -220,17 +253,45 @@ class MergeEnvCompat(object):
             veh.state_hist, veh.action_hist, veh.t_step = [], [], 0.0
             veh.min_headway = 180.0 / 40.0  # PERCEPTION_DIST / MAX_SPEED (:56)
             veh._sang = 0.0
+        if self.hdv_env:  # MultiAgentObservationHDV: one row per road vehicle; no controlled vehicle, no action mask
+            return obs[0, :n_all].cpu().numpy().astype(np.float64).reshape(n_all, -1), np.asarray([])
         return (obs[0, :n].cpu().numpy().astype(np.float64).reshape(n, -1),
                 avail[0, :n].cpu().numpy().astype(np.int64))
 
     @property
     def vehicle(self):
+        if self.hdv_env:  # MergeEnvLCHDV.vehicle (merge_env_v1.py:582-585)
+            return self.road.vehicles[0] if self.road is not None and self.road.vehicles else None
         return self.controlled_vehicles[0] if self.controlled_vehicles else None
 
+    def _step_hdv(self):
+        """MergeEnvLCHDV.step (merge_env_v1.py:604-666): no action is applied, every vehicle drives IDM / MOBIL."""
+        b = self._b
+        obs, reward, done, out = b.step(None)
+        b.poll_errors()
+        if self.store_profile:
+            self._log_profiles(b)
+        self.steps += 1
+        self.time = int(b.env_i32[abi.EP["TIME"], 0])
+        n = len(self.road.vehicles)
+        o = {k: v[0].cpu().numpy() for k, v in out.items()}
+        speeds = b.f64[abi.F["SPEED"], 0, :n].cpu().numpy()
+        self.vehicle_speed.append([float(s) for s in speeds])
+        self.vehicle_pos.append([float(p) for p in b.f64[abi.F["X"], 0, :n].cpu().numpy()])
+        terminal = bool(o["done"])
+        info = {"speed": float(speeds[0]), "crashed": bool(o["crashed"][0]), "average_speed": float(o["average_speed"]),
+                "traffic_speed": float(o["traffic_speed"]), "min_headway": float(o["min_headway"])}
+        if terminal:
+            info["merge_percent"] = float(o["merge_percent"])
+        return obs[0, :n].cpu().numpy().astype(np.float64).reshape(n, 5, -1), float(o["reward"]), terminal, info
+
     def step(self, action):
-        """merge_env_v1.py:126-166 / abstract.py:443-510 -> (obs, reward, done, info)."""
+        """merge_env_v1.py:126-166 / abstract.py:443-510 -> (obs, reward, done, info).
+        merge-multi-agent-hdv-v1: step(None); an action, if given, is ignored as nothing is controlled."""
         if self.road is None or self.vehicle is None:
             raise NotImplementedError("The road and vehicle must be initialized in the environment implementation")
+        if self.hdv_env:
+            return self._step_hdv()
         n = self._n
         action = tuple(int(a) for a in action)
         assert len(action) == n
@@ -281,7 +342,7 @@ class MergeEnvCompat(object):
         T = abi.T
         tr = b.trace[:, :, 0].cpu().numpy()  # [3, planes, MAX_VEHICLES]
         dt = 1.0 / self.config["simulation_frequency"]
-        is_lc = self.env_id == "merge-multi-agent-v1"
+        is_lc = abi.env_kind(self.env_id) != abi.ENV_V0  # (hdv-v1: IDMVehicleHist profiles, as the HDVs of v1)
         steer_vel = is_lc and self.config.get("lateral_control", "steer") == "steer_vel"
         hl_name = {v: k for k, v in self.ACTIONS_ALL.items()}
         for k in range(tr.shape[0]):
@@ -334,6 +395,8 @@ class MergeEnvCompat(object):
         return cp
 
     def is_crashed(self):
+        if self.hdv_env:  # MergeEnvLCHDV.is_crashed: any road vehicle
+            return any(v.crashed for v in self.road.vehicles)
         return any(v.crashed for v in self.controlled_vehicles)
 
     def render(self, mode="human"):
@@ -344,7 +407,7 @@ class MergeEnvCompat(object):
 
 
 def make(env_id, **kw):
-    """gym.make counterpart for the two env ids on the hot path (merge_env_v1.py:681-689)."""
+    """gym.make counterpart for the env ids on the hot path (merge_env_v1.py:681-694)."""
     return MergeEnvCompat(env_id, **kw)
 
 

@@ -100,6 +100,7 @@ MM_DEV int &sw_i(const SweepBuf &sb, int f, int a, long long e) { return sb.I[((
 //   MM_TU=3  only the MM_QP_IPM fidelity-mode step kernels (IPM = true: the general kernels with the QP solved by
 //            cvxopt's interior-point algorithm, include/mm_qp.h), same flags as TU 2.
 //   MM_TU=4 / 5  only the exact-mode / the interior-point step kernels in the 6- / 12-lane rotation layouts (kPow2 below).
+//   MM_TU=8  only the reset / step kernels of merge-multi-agent-hdv-v1 (MM_ENV_HDV_V1: every vehicle an IDM / MOBIL HDV).
 // MM_TU=0 (default) is the single-TU form used by the tuning / diagnostic builds.
 #ifndef MM_TU
 #define MM_TU 0
@@ -130,6 +131,11 @@ __device__ unsigned long long g_stamps_s[4096 * 8];  // sweep kernel: per wave {
 #define SSTAMP(k) do {} while (0)
 #define SCOUNT(k) do {} while (0)
 #endif
+
+// merge-multi-agent-hdv-v1 (MergeEnvLCHDV, merge_env_v1.py:552-674): every vehicle an IDMVehicleHist, none controlled, every
+// vehicle an observer.  Instantiated only in its own translation unit (MM_TU=8); `if constexpr` on it leaves the other kinds' code
+// as it was.
+template <int KIND> constexpr bool kIdm = KIND == MM_ENV_HDV_V1;
 
 struct Veh {
   double x, y, h, v, tspeed;
@@ -460,10 +466,17 @@ MM_DEV void init_vehicle(Veh &v) {  // kinematics.py:36-53, controller.py:35-50,
 }
 // MergeEnv._num_vehicles (merge_env_v1.py:180-211, :476-495): block 64 of the episode's stream, word 0 -> num_CAV,
 // word 1 -> num_HDV, uniform over 3 values each; traffic_density 0 keeps the given (fixed) counts
+// (hdv-v1, KIND = MM_ENV_HDV_V1: every drawn vehicle an HDV, mm_counts_hdv_from_draw)
+template <int KIND>
 MM_DEV void episode_counts(const DevCfg &c, uint64_t seed, uint32_t episode, int &n_cav, int &n_hdv) {
   if (c.traffic_density <= 0) return;
   uint32_t w[4];
   rng_block(seed, episode, 64u, w);
+  if constexpr (kIdm<KIND>) {
+    n_cav = 0;
+    n_hdv = mm_counts_hdv_from_draw(c.traffic_density, c.num_cav, (int)(((uint64_t)w[0] * 3u) >> 32), (int)(((uint64_t)w[1] * 3u) >> 32));
+    return;
+  }
   mm_counts_from_draw(c.traffic_density, c.mixed_traffic, c.num_cav, (int)(((uint64_t)w[0] * 3u) >> 32), (int)(((uint64_t)w[1] * 3u) >> 32),
                       &n_cav, &n_hdv);  // include/mm_counts.h (shared with the oracle and the configuration check)
 }
@@ -519,9 +532,11 @@ MM_DEV int spawn_vehicle(Veh &v, int a, int n_cav, int n_hdv, uint64_t seed, uin
 template <int G, int KIND, bool LEND = false>
 MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, bool valid, void *obs,
                     uint8_t *avail, float *stage = nullptr, const double *sincos_h = nullptr) {
-  constexpr int F = (KIND == MM_ENV_V1) ? 6 : 5;
+  constexpr int F = (KIND != MM_ENV_V0) ? 6 : 5;
   constexpr int S = 5 * F;
-  const bool ctrl = v.present && v.kind != 2;  // only controlled vehicles observe / have an action mask
+  // only controlled vehicles observe / have an action mask; hdv-v1: every vehicle observes (MultiAgentObservationHDV,
+  // observation.py:430-442) and none acts (reset's available_actions has shape (0,), abstract.py:200-207)
+  const bool ctrl = kIdm<KIND> ? v.present : (v.present && v.kind != 2);
   // the wave's LDS scratch: first the mailbox of the neighbour gather (5 doubles per lane), then the float32 row staging
   float *sw;
   if constexpr (LEND) {
@@ -543,7 +558,7 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
     // loop as 4 x 5 select chains (one v_cndmask pair per double, partner and row: 280 of them at G = 8).
     double *mb = (double *)sw;
     mb[0 * 64 + lane] = v.x; mb[1 * 64 + lane] = v.y; mb[2 * 64 + lane] = vx; mb[3 * 64 + lane] = vy;
-    if (KIND == MM_ENV_V1) mb[4 * 64 + lane] = v.h;
+    if (KIND != MM_ENV_V0) mb[4 * 64 + lane] = v.h;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -586,7 +601,7 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
       const int pl = plane_rt<G>(lane, a, sel[q]);  // (no row: my own column, masked below)
       row[q][0] = mb[0 * 64 + pl] - v.x; row[q][1] = mb[1 * 64 + pl] - v.y;
       row[q][2] = mb[2 * 64 + pl] - vx; row[q][3] = mb[3 * 64 + pl] - vy;
-      if (KIND == MM_ENV_V1) {
+      if (KIND != MM_ENV_V0) {
         double ph = mb[4 * 64 + pl];
         if (c.steer_vel) {  // MDPLCVehicle.to_dict under "steer_vel" (safe_controller.py:75-81):
           const int pkind = shfl_i(v.kind, pl);  // a CAV neighbour's heading is relative to the observer's
@@ -647,7 +662,7 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
   // action mask: with masking on, the reference's `[[0]*n_a]*n` aliases every row (abstract.py:202,475)
   // so each agent gets the OR over all agents; with masking off every action is available.
   unsigned bits = 0x1F;
-  if (c.action_masking) {
+  if (!kIdm<KIND> && c.action_masking) {
     unsigned mine = 0;
     if (ctrl) {
       mine = 1u << 1;
@@ -663,7 +678,7 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
   }
   if (valid && avail) {
 #pragma unroll
-    for (int k = 0; k < 5; k++) avail[i * 5 + k] = ctrl ? (uint8_t)((bits >> k) & 1u) : (uint8_t)0;
+    for (int k = 0; k < 5; k++) avail[i * 5 + k] = (!kIdm<KIND> && ctrl) ? (uint8_t)((bits >> k) & 1u) : (uint8_t)0;
   }
 }
 
@@ -1473,8 +1488,10 @@ template <int G, int KIND, int SHIELD, bool MIXED, bool IPM = false, bool TRACE 
 #endif
 __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_waves<G, SHIELD, MIXED>(IPM))) void step_kernel(DevCfg c, DevState st, const int32_t *__restrict__ actions,
                                                    MMStepOut out, double *metrics, SweepBuf sb, int kb) {
-  constexpr bool LC = (KIND == MM_ENV_V1);
+  constexpr bool IDM = kIdm<KIND>;  // hdv-v1: IDMVehicleHist everywhere (log_step histories as in v1 mixed traffic)
+  constexpr bool LC = (KIND == MM_ENV_V1) || IDM;
   constexpr bool SHIELDED = LC && (SHIELD != MM_SHIELD_NONE);
+  static_assert(!IDM || (MIXED && SHIELD == MM_SHIELD_NONE && !IPM && !SPLIT), "hdv-v1: general unshielded kernels only");
   constexpr bool MASS = (SHIELD == MM_SHIELD_MASS);
   static_assert(!IPM || SHIELDED, "the IPM mode lives in shielded kernels");
   static_assert(!SPLIT || IPM, "the split form exists for the interior-point kernels");
@@ -1519,9 +1536,13 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     // n_merge / episode are only needed by the epilogue: loaded there, not held across the sub-steps
   }
   if (!MIXED && v.kind == 2) v.kind = 1;  // CAV-only kernels: the host guarantees there are no HDVs
+  if (IDM && v.present) v.kind = 2;        // hdv-v1: whatever the planes say, every vehicle is an HDV
   const bool hdv = MIXED && v.kind == 2;
-  const bool ctrl = v.present && !hdv;  // controlled vehicle (MDPVehicle / MDPLCVehicle)
-  int action = (valid && ctrl) ? actions[i] : 1;
+  // controlled vehicle (MDPVehicle / MDPLCVehicle); hdv-v1: every vehicle, so that the observation, the rewards, the speeds
+  // and the headway below run over road.vehicles (MergeEnvLCHDV.step, merge_env_v1.py:604-666) -- it reads no action
+  const bool ctrl = IDM ? v.present : (v.present && !hdv);
+  const bool ctrl_x = IDM ? false : ctrl;  // vehicles whose x < 0 ends the episode (hdv-v1: none, :671-674)
+  int action = (!IDM && valid && ctrl) ? actions[i] : 1;  // (hdv-v1: step(None), actions may be NULL)
   if ((unsigned)action > 4u) {  // self.actions[action]: KeyError in the reference (action.py:194-196) -> latched, acts as IDLE
     if (!SPLIT || kb == 0) atomicOr(c.err, MM_LATCH_BAD_ACTION);
     action = 1;
@@ -1570,7 +1591,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   if constexpr (kRoomy) { s_cold[C_CPSI][tid] = cpsi; s_cold[C_GVX][tid] = v.gvx; }
   auto CPSI = [&]() -> double { if constexpr (kRoomy) return s_cold[C_CPSI][tid]; else return cpsi; };
   auto GVX = [&]() -> double { if constexpr (kRoomy) return s_cold[C_GVX][tid]; else return v.gvx; };
-  bool env_active = n_ctrl > 0;
+  bool env_active = IDM ? n_veh > 0 : n_ctrl > 0;
   if constexpr (SPLIT) {
     if (kb > 0) env_active = e < st.E && sb.envf[e] != 0;
   }
@@ -2355,7 +2376,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if (!SHIELDED) t[MM_T_QP_ROWS * A] = 0;  // the other QP planes keep the NaN fill
     }
     // _is_terminal (merge_env_v1.py:168-172) breaks the sub-step loop (abstract.py:530)
-    const bool term = group_ballot<G>(ctrl && (v.crashed || v.x < 0), gb) != 0 || steps >= c.T;
+    // hdv-v1: any road vehicle crashed, no x < 0 clause (merge_env_v1.py:671-674)
+    bool term;
+    if constexpr (IDM) term = group_ballot<G>(v.present && v.crashed, gb) != 0 || steps >= c.T;
+    else term = group_ballot<G>(ctrl && (v.crashed || v.x < 0), gb) != 0 || steps >= c.T;
     if (term) env_active = false;
     }  // tail
   }
@@ -2383,7 +2407,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   const bool env_ok = n_ctrl > 0;
   const unsigned crashed_bits = group_ballot<G>(ctrl && v.crashed, gb);
   const bool done = env_ok && (crashed_bits != 0 || steps >= c.T ||
-                               group_ballot<G>(ctrl && v.x < 0, gb) != 0);
+                               group_ballot<G>(ctrl_x && v.x < 0, gb) != 0);
   const int nl = v.present ? next_lane(v.lane, v.x, v.y) : 0;
   // surrounding_vehicles lane sets (road.py:315-342), as bit sets over lane ids
   const unsigned allow_tbl[6] = {
@@ -2552,7 +2576,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     memset(&nv, 0, sizeof nv);
     int nm = 0;
     int nc = n_ctrl, nh = n_veh - n_ctrl;  // fixed counts: the env keeps its own composition
-    episode_counts(c, seed, (uint32_t)episode, nc, nh);
+    if constexpr (IDM) { nc = 0; nh = n_veh; }  // (hdv-v1: all of them HDVs)
+    episode_counts<KIND>(c, seed, (uint32_t)episode, nc, nh);
     const bool spawn = valid && (c.traffic_density > 0 ? a < nc + nh : v.present);
     if (spawn) nm = spawn_vehicle(nv, a, nc, nh, seed, (uint32_t)episode);
     if (c.traffic_density > 0 && valid) {  // ragged batch: the slot's occupancy changes with the episode
@@ -2616,6 +2641,7 @@ __global__ __launch_bounds__(256) void reset_kernel(DevCfg c, DevState st, int m
   const bool selected = e < st.E && mode != 2 && (!env_mask || env_mask[e]);
   Veh v;
   load_veh(st, i, valid, v);
+  if (kIdm<KIND> && v.present) v.kind = 2;  // hdv-v1: every vehicle an HDV
   if (selected) {
     int steps = 0, time = 0, n_merge = 0, episode = st.I[MM_E_EPISODE * st.E + e];
     if (mode == 0) {
@@ -2623,7 +2649,8 @@ __global__ __launch_bounds__(256) void reset_kernel(DevCfg c, DevState st, int m
       const uint64_t seed = seeds_in ? seeds_in[e] : st.seeds[e];
       int nm = 0;
       int nc = st.N - c.n_hdv, nh = c.n_hdv;
-      episode_counts(c, seed, (uint32_t)episode, nc, nh);
+      if (kIdm<KIND>) { nc = 0; nh = st.N; }  // hdv-v1 with fixed counts: N HDVs
+      episode_counts<KIND>(c, seed, (uint32_t)episode, nc, nh);
       if (valid) {
         if (a < nc + nh) nm = spawn_vehicle(v, a, nc, nh, seed, (uint32_t)episode);
         else {  // unused slot of a ragged batch (a slot that empties reads zero in every plane)
@@ -2638,6 +2665,7 @@ __global__ __launch_bounds__(256) void reset_kernel(DevCfg c, DevState st, int m
       episode += 1;
     } else {
       if (valid && v.present) init_vehicle(v);
+      if (kIdm<KIND> && valid && v.present) st.B[MM_B_KIND * st.A + i] = 2;
       n_merge = __popc(group_ballot<G>(valid && v.kind == 1 && (v.lane == MM_LANE_JK0 || v.lane == MM_LANE_KB0), gb));
     }
     if (valid && v.present) store_veh(st, i, v, true);
@@ -2863,7 +2891,7 @@ struct MMHandle_ : MMHandleHead {  // cfg, E, N, device, state, lay, first_env: 
   char err[256];
 };
 static bool needs_general(const MMHandle_ *h) {  // HDVs can appear, or steer_vel lateral control: the kernels that carry IDM / MOBIL
-  return h->cfg.n_hdv > 0 || (h->cfg.traffic_density > 0 && h->cfg.mixed_traffic != 0) ||
+  return h->cfg.env_kind == MM_ENV_HDV_V1 || h->cfg.n_hdv > 0 || (h->cfg.traffic_density > 0 && h->cfg.mixed_traffic != 0) ||
          (h->cfg.env_kind == MM_ENV_V1 && h->cfg.lateral_control == MM_LATERAL_STEER_VEL);
 }
 // The interior-point mode of a CAV-only shielded batch steps as phase kernels + sweep kernels (SweepBuf above) once the
@@ -2932,12 +2960,17 @@ extern "C" int32_t mm_state_layout(int32_t E, int32_t N, MMStateLayout *out) {
 
 static int check_cfg(const MMConfig *c, int N, char *err) {
   if (!c || c->abi_version != MM_ABI_VERSION) { snprintf(err, 256, "ABI version mismatch"); return MM_ERR_INVALID_ARG; }
-  if (c->env_kind != MM_ENV_V0 && c->env_kind != MM_ENV_V1) { snprintf(err, 256, "unknown env_kind %d", c->env_kind); return MM_ERR_INVALID_ARG; }
+  if (c->env_kind != MM_ENV_V0 && c->env_kind != MM_ENV_V1 && c->env_kind != MM_ENV_HDV_V1) { snprintf(err, 256, "unknown env_kind %d", c->env_kind); return MM_ERR_INVALID_ARG; }
+  if (c->env_kind == MM_ENV_HDV_V1) {  // MergeEnvLCHDV: no controlled vehicle, so nothing a shield or a CAV setting could act on
+    if (c->shield != MM_SHIELD_NONE) { snprintf(err, 256, "merge-multi-agent-hdv-v1 has no controlled vehicle: shield must be none, got %d", c->shield); return MM_ERR_INVALID_ARG; }
+    if (c->lateral_control != MM_LATERAL_STEER) { snprintf(err, 256, "merge-multi-agent-hdv-v1 has no controlled vehicle: lateral_control must be steer"); return MM_ERR_INVALID_ARG; }
+    if (c->n_hdv != 0) { snprintf(err, 256, "merge-multi-agent-hdv-v1: every vehicle is an HDV, n_hdv must be 0 (got %d)", c->n_hdv); return MM_ERR_INVALID_ARG; }
+  }
   if (c->shield < MM_SHIELD_NONE || c->shield > MM_SHIELD_MASS) { snprintf(err, 256, "Undefined safety_type:%d", c->shield); return MM_ERR_INVALID_ARG; }
   if (c->policy_frequency <= 0 || c->simulation_frequency < c->policy_frequency ||
       c->simulation_frequency / c->policy_frequency > 3) { snprintf(err, 256, "unsupported frequencies"); return MM_ERR_INVALID_ARG; }
   if (N > 12) { snprintf(err, 256, "N=%d exceeds the 6+6 spawn slots", N); return MM_ERR_INVALID_ARG; }
-  if (c->n_hdv < 0 || c->n_hdv >= N) { snprintf(err, 256, "n_hdv=%d must leave at least one controlled vehicle of N=%d", c->n_hdv, N); return MM_ERR_INVALID_ARG; }
+  if (c->env_kind != MM_ENV_HDV_V1 && (c->n_hdv < 0 || c->n_hdv >= N)) { snprintf(err, 256, "n_hdv=%d must leave at least one controlled vehicle of N=%d", c->n_hdv, N); return MM_ERR_INVALID_ARG; }
   if (c->qp_solver != MM_QP_EXACT && c->qp_solver != MM_QP_IPM) { snprintf(err, 256, "unknown qp_solver %d", c->qp_solver); return MM_ERR_INVALID_ARG; }
   // every vehicle composition this configuration can produce -- fixed counts, or any per-episode draw incl. the
   // reset(num_CAV=k) override -- must fit the N slots and the six spawn points per road (the reference raises from
@@ -3150,7 +3183,10 @@ static DevState dev_state(const MMHandle h) {
   s.A = (long long)h->E * h->N; s.E = h->E; s.N = h->N;
   return s;
 }
-#if MM_TU <= 1
+// merge-multi-agent-hdv-v1: reset and step kernels of their own translation unit (MM_TU=8, mm_idm.o)
+void mm_launch_reset_idm(MMHandle h, int mode, const uint8_t *mask, const uint64_t *seeds, void *obs, uint8_t *avail, hipStream_t s);
+void mm_launch_step_idm(MMHandle h, int g, const MMStepOut *out, hipStream_t s);
+#if MM_TU <= 1 || MM_TU == 8
 template <int G, int KIND>
 static void launch_reset_t(MMHandle h, int mode, const uint8_t *mask, const uint64_t *seeds, void *obs,
                            uint8_t *avail, hipStream_t s) {
@@ -3159,6 +3195,8 @@ static void launch_reset_t(MMHandle h, int mode, const uint8_t *mask, const uint
   hipLaunchKernelGGL((reset_kernel<G, KIND>), dim3(grid), dim3(256), 0, s, dev_cfg(h), dev_state(h), mode, mask,
                      seeds, obs, avail);
 }
+#endif
+#if MM_TU <= 1
 template <int G>
 static void launch_reset_g(MMHandle h, int mode, const uint8_t *mask, const uint64_t *seeds, void *obs,
                            uint8_t *avail, hipStream_t s) {
@@ -3168,6 +3206,8 @@ static void launch_reset_g(MMHandle h, int mode, const uint8_t *mask, const uint
 static int launch_reset(MMHandle h, int mode, const uint8_t *mask, const uint64_t *seeds, void *obs,
                         uint8_t *avail, MMStream stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (h->cfg.env_kind == MM_ENV_HDV_V1) mm_launch_reset_idm(h, mode, mask, seeds, obs, avail, s);
+  else
 #ifdef MM_ONLY_G
   launch_reset_g<MM_ONLY_G>(h, mode, mask, seeds, obs, avail, s);
 #else
@@ -3334,7 +3374,27 @@ void mm_launch_step_lanes(MMHandle h, int g, const int32_t *actions, const MMSte
 #endif
 }
 #endif
-#if MM_TU == 4 || MM_TU == 5 || MM_TU == 6 || MM_TU == 7
+#if MM_TU == 0 || MM_TU == 8
+// merge-multi-agent-hdv-v1 (MergeEnvLCHDV): the general unshielded kernels with every vehicle an IDM / MOBIL observer; the
+// step reads no actions.  Power-of-two groups for the reset (like every kind), the step's layouts as step_group() picks them.
+void mm_launch_reset_idm(MMHandle h, int mode, const uint8_t *mask, const uint64_t *seeds, void *obs, uint8_t *avail, hipStream_t s) {
+  switch (group_size(h->N)) {
+    case 2: launch_reset_t<2, MM_ENV_HDV_V1>(h, mode, mask, seeds, obs, avail, s); break;
+    case 4: launch_reset_t<4, MM_ENV_HDV_V1>(h, mode, mask, seeds, obs, avail, s); break;
+    case 8: launch_reset_t<8, MM_ENV_HDV_V1>(h, mode, mask, seeds, obs, avail, s); break;
+    default: launch_reset_t<16, MM_ENV_HDV_V1>(h, mode, mask, seeds, obs, avail, s); break;
+  }
+}
+void mm_launch_step_idm(MMHandle h, int g, const MMStepOut *out, hipStream_t s) {
+  switch (g) {
+#define MM_IDM_CASE(GG) case GG: launch_step_t<GG, MM_ENV_HDV_V1, MM_SHIELD_NONE, true>(h, nullptr, out, s); break;
+    MM_IDM_CASE(2) MM_IDM_CASE(4) MM_IDM_CASE(6) MM_IDM_CASE(8) MM_IDM_CASE(12) MM_IDM_CASE(16)
+#undef MM_IDM_CASE
+    default: break;
+  }
+}
+#endif
+#if MM_TU == 4 || MM_TU == 5 || MM_TU == 6 || MM_TU == 7 || MM_TU == 8
 #elif MM_TU == 2
 void mm_launch_step_general(MMHandle h, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
   switch (group_size(h->N)) {
@@ -3381,14 +3441,16 @@ static void launch_step_g(MMHandle h, const int32_t *actions, const MMStepOut *o
 }
 
 extern "C" int32_t mm_step(MMHandle h, const int32_t *actions, const MMStepOut *out, MMStream stream) {
-  if (!h || !actions || !out) return MM_ERR_INVALID_ARG;
+  if (!h || !out || (!actions && h->cfg.env_kind != MM_ENV_HDV_V1)) return MM_ERR_INVALID_ARG;  // (hdv-v1: step(None))
   hipStream_t s = (hipStream_t)stream;
   if (out->trace) {
     // NaN = "sub-step did not run"; 0xFF bytes are a NaN pattern
     hipError_t rc = hipMemsetAsync(out->trace, 0xFF, (size_t)3 * MM_T_COUNT * h->E * h->N * sizeof(double), s);
     if (rc != hipSuccess) return hip_fail(h, rc, "trace memset");
   }
-  if (steps_split(h)) {  // interior-point mode, CAV-only: phase kernels + sweep kernels (SweepBuf)
+  if (h->cfg.env_kind == MM_ENV_HDV_V1) {  // every vehicle an IDM / MOBIL HDV (mm_idm.o)
+    mm_launch_step_idm(h, step_group(h), out, s);
+  } else if (steps_split(h)) {  // interior-point mode, CAV-only: phase kernels + sweep kernels (SweepBuf)
     if (!h->sweep_mem) { snprintf(h->err, sizeof h->err, "mm_step: the hand-off planes of the split interior-point step are missing"); return MM_ERR_DEVICE; }
     mm_launch_step_split(h, step_group(h), actions, out, s);
   } else

@@ -298,3 +298,69 @@ class DeviceRollout(object):
             # the sampler's counter as well (the evaluation's own act() calls advanced it): with a stochastic actor the
             # training rollouts after an evaluation are then the ones a twin that never evaluated draws
             self._sample_counter.copy_(saved_counter)
+
+
+def idm_evaluation(env, seeds):
+    """eval_idm.py:70-160 (idm_evaluation of merge-multi-agent-hdv-v1) for a batch of episodes at once.
+
+    env: a VecMergeEnv of merge-multi-agent-hdv-v1 with one env per seed (E == len(seeds)); every env is spawned from the
+    reference's own draws of reset(is_training=False, testing_seeds=seed) (compat.hdv_spawn, the global numpy stream) and
+    then stepped with step(None) until every episode has ended.  Returns eval_idm.py's ext_info, one entry per seed:
+    steps, avg_speeds, crash_count (any road vehicle crashed, MergeEnvLCHDV.is_crashed), min_headways (max(0, min) over the
+    episode), traffic_speeds, merge_percents -- and step_time, which here is the DEVICE time of one batched step of all E
+    episodes (seconds, the same value for every entry), not the host time of one env.step."""
+    import numpy as np
+    from .compat import hdv_spawn, MAX_VEHICLES
+
+    if env.kind != abi.ENV_HDV_V1:
+        raise ValueError("idm_evaluation runs merge-multi-agent-hdv-v1, got %r" % (env.env_id,))
+    E, N = env.E, env.N
+    if len(seeds) != E:
+        raise ValueError("one env per seed: E = %d, %d seeds" % (E, len(seeds)))
+    x = np.full((E, N), np.nan)
+    y, v = np.zeros((E, N)), np.zeros((E, N))
+    for e, s in enumerate(seeds):
+        xe, ye, ve = hdv_spawn(env.config, int(s))
+        if len(xe) > min(N, MAX_VEHICLES):
+            raise ValueError("seed %s spawns %d vehicles, the batch has %d slots per env" % (s, len(xe), N))
+        x[e, :len(xe)], y[e, :len(xe)], v[e, :len(xe)] = xe, ye, ve
+    dev = env.device
+    env.configure(auto_reset=False)
+    env.set_kinematics(x, y, np.zeros((E, N)), v, n_merge=np.zeros(E, dtype=np.int32), kind=np.where(np.isnan(x), 0, 2))
+    f64 = torch.float64
+    alive = torch.ones(E, dtype=torch.bool, device=dev)
+    steps = torch.zeros(E, dtype=torch.int64, device=dev)
+    avg, traffic = torch.zeros(E, dtype=f64, device=dev), torch.zeros(E, dtype=f64, device=dev)
+    min_hw = torch.full((E,), float("inf"), dtype=f64, device=dev)
+    crashed = torch.zeros(E, dtype=torch.bool, device=dev)
+    merge = torch.full((E,), float("nan"), dtype=f64, device=dev)
+    timed = dev.type == "cuda"
+    if timed:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+    n_steps = 0
+    for n_steps in range(1, env.T + 1):  # every episode ends by steps >= T at the latest
+        _, _, done, info = env.step(None)
+        steps += alive.long()
+        avg += torch.where(alive, info["average_speed"], 0.0)
+        traffic += torch.where(alive, info["traffic_speed"], 0.0)
+        min_hw = torch.where(alive, torch.clamp(torch.minimum(min_hw, info["min_headway"]), min=0.0), min_hw)
+        end = alive & done.bool()
+        crashed |= end & info["crashed"].bool().any(dim=1)
+        merge = torch.where(end, info["merge_percent"], merge)
+        alive &= ~done.bool()
+        if n_steps % 20 == 0 and not bool(alive.any()):
+            break
+    if timed:
+        t1.record()
+        t1.synchronize()
+        step_time = t0.elapsed_time(t1) / 1000.0 / n_steps
+    else:
+        step_time = float("nan")
+    env.poll_errors()
+    st = steps.cpu().numpy()
+    return {"steps": [int(s) for s in st], "avg_speeds": list((avg.cpu().numpy() / st).astype(float)),
+            "crash_count": [bool(c) for c in crashed.cpu().numpy()], "step_time": [step_time] * E,
+            "min_headways": list(min_hw.cpu().numpy().astype(float)),
+            "traffic_speeds": list((traffic.cpu().numpy() / st).astype(float)),
+            "merge_percents": list(merge.cpu().numpy().astype(float))}

@@ -46,7 +46,8 @@ class BatchedMergeEnv(object):
         # draw_counts: every (re)spawn draws its vehicle counts as MergeEnv._num_vehicles does (config["traffic_density"]
         # 1..3, config["mixed_traffic"] / "traffic_type"); N is then the slot capacity of a ragged batch
         self.draw_counts, self.num_cav = bool(draw_counts), int(num_cav)
-        self.n_f = 6 if env_id == "merge-multi-agent-v1" else 5
+        self.kind = abi.env_kind(env_id)
+        self.n_f = abi.obs_features(env_id)
         self.n_s = 5 * self.n_f  # merge_env_v1.py:28 / :413
         self._cfg = self._make_cfg()
         self.T = int(self.config["duration"] * self.config["policy_frequency"])
@@ -76,15 +77,22 @@ class BatchedMergeEnv(object):
             "traffic_speed": z(self.E), "min_headway": z(self.E), "merge_percent": z(self.E),
             "action_mask": z(self.E, self.N, 5, dtype=torch.uint8),
         }
+        if self.kind == abi.ENV_HDV_V1:
+            # MergeEnvLCHDV.step's info (merge_env_v1.py:604-666): speed / crashed of vehicle 0 (here: crashed of every slot),
+            # average_speed, traffic_speed, min_headway, merge_percent -- no agents_*, regional_rewards or action_mask; nothing
+            # is controlled, so no action mask either (reset's available_actions has shape (0,)): avail stays empty
+            for k in ("agents_rewards", "regional_rewards", "agents_dones", "agents_info", "action_mask"):
+                del self.out[k]
+            self.avail = z(self.E, self.N, 0, dtype=torch.uint8)
         # skip_outputs: per-agent planes a caller does not consume -- "agents_info" (24 B/agent), "action_mask" (5 B), "crashed"
         # (1 B): the kernel does not write an output whose MMStepOut pointer is NULL (mm_abi.h); step()'s info dict then has
         # no such key.  The reference's info always carries them, so the default (and MergeEnvCompat) keeps everything.
         for k in skip_outputs:
             if k not in ("agents_info", "action_mask", "crashed"):
                 raise ValueError("only agents_info / action_mask / crashed may be skipped, got %r" % (k,))
-            if k == "action_mask" and self.config.get("action_masking"):
+            if k == "action_mask" and self.config.get("action_masking") and self.kind != abi.ENV_HDV_V1:
                 raise ValueError("action_masking is on: the mask is part of the step's result")
-            del self.out[k]
+            self.out.pop(k, None)
         self.trace = z(3, len(abi.T_PLANES), self.E, self.N) if trace else None
         self.metrics = None
         self._step_out = abi.MMStepOut()  # (zero-initialised: a skipped output stays NULL)
@@ -172,6 +180,9 @@ class BatchedMergeEnv(object):
         return None
 
     # -- Env API --------------------------------------------------------------------------
+    def _avail_ptr(self):
+        return None if self.kind == abi.ENV_HDV_V1 else _ptr(self.avail)  # (hdv-v1: no action mask)
+
     def reset(self, env_mask=None, seeds=None):
         """AbstractEnv.reset (abstract.py:176-209) with the device RNG, for all / masked envs."""
         if env_mask is not None:
@@ -179,12 +190,12 @@ class BatchedMergeEnv(object):
         if seeds is not None:
             seeds = seeds.to(self.device, torch.int64).contiguous()
         self.clib.check(self.clib.lib.mm_reset(self._h, _ptr(env_mask), _ptr(seeds), _ptr(self.obs),
-                                               _ptr(self.avail), self._stream()), self._h)
+                                               self._avail_ptr(), self._stream()), self._h)
         return self.obs, self.avail
 
     def set_kinematics(self, x, y, heading, speed, n_merge=None, env_mask=None, kind=None):
         """Host-provided spawn (numpy-compatible reset, fixtures): [E,N] tensors; NaN x = absent.
-        kind: optional [E,N] with 1 = controlled CAV, 2 = HDV (CAVs first)."""
+        kind: optional [E,N] with 1 = controlled CAV, 2 = HDV (CAVs first); merge-multi-agent-hdv-v1: 2 only."""
         dev = self.device
         x = torch.as_tensor(x, dtype=torch.float64, device=dev).view(self.E, self.N)
         present = ~torch.isnan(x)
@@ -200,6 +211,9 @@ class BatchedMergeEnv(object):
             # the kernels that carry IDM / MOBIL run when HDVs can exist (the library's needs_general()): a fixed HDV count, a
             # count draw with mixed / "av" traffic, or steer_vel lateral control
             general = self.n_hdv > 0 or self._cfg.lateral_control != 0 or (self._cfg.traffic_density > 0 and self._cfg.mixed_traffic != 0)
+            if self.kind == abi.ENV_HDV_V1 and bool((k8 == 1).any()):
+                raise ValueError("merge-multi-agent-hdv-v1 has no controlled vehicle: kind must be 2 (HDV) for every vehicle")
+            general = general or self.kind == abi.ENV_HDV_V1
             if not general and bool((k8 == 2).any()):
                 # the CAV-only kernels would drive such a vehicle as a CAV from actions[i]
                 raise ValueError("HDVs (kind == 2) in the spawn need mixed traffic: configure(n_hdv=...) > 0 first")
@@ -211,7 +225,7 @@ class BatchedMergeEnv(object):
         return self.observe()
 
     def observe(self):
-        self.clib.check(self.clib.lib.mm_observe(self._h, _ptr(self.obs), _ptr(self.avail),
+        self.clib.check(self.clib.lib.mm_observe(self._h, _ptr(self.obs), self._avail_ptr(),
                                                  self._stream()), self._h)
         return self.obs, self.avail
 
@@ -223,11 +237,15 @@ class BatchedMergeEnv(object):
         this step writes those outputs there instead of into self.out -- a rollout hands over rewards[t], dones[t], ...
         and saves a copy kernel per quantity and step; the returned info carries the given tensors under those keys.
         With safety_guarantee = "priority" (v0) the joint action first goes through the supervisor (supervise()) and the env
-        steps on its result, which info["new_action"] carries (int32 [E, N]); uniforms: see supervise()."""
+        steps on its result, which info["new_action"] carries (int32 [E, N]); uniforms: see supervise().
+        merge-multi-agent-hdv-v1 (MergeEnvLCHDV.step, merge_env_v1.py:604-666): nothing is controlled, step(None) is the call and
+        actions, if given, are ignored; info holds crashed [E, N], average_speed, traffic_speed, min_headway, merge_percent."""
         sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)
-        if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
+        if self.kind == abi.ENV_HDV_V1:
+            actions = None
+        elif actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(self.device, torch.int32).contiguous()
-        assert actions.numel() == self.E * self.N
+        assert actions is None or actions.numel() == self.E * self.N
         if sup != abi.SUP_NONE:
             actions, _ = self.supervise(actions, uniforms)
         obs, info = self.obs, self.out
