@@ -266,6 +266,11 @@ class CLib(object):
             lib.mm_supervise_scratch_bytes.restype = i32
             lib.mm_supervise.argtypes = [vp, i32, i32, vp, vp, i32, vp, u64, vp, vp, vp]
             lib.mm_supervise.restype = i32
+        # MAPPO_GI's shared actor-critic + sample in one launch (include/mm_policy_gi.h), also libmm_hip.so only
+        self.has_policy_gi = hasattr(lib, "mm_policy_gi_act")
+        if self.has_policy_gi:
+            lib.mm_policy_gi_act.argtypes = [vp, i64, i32] + [vp] * 12 + [i32, i32, u64, vp, vp, vp, vp, vp]
+            lib.mm_policy_gi_act.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -291,6 +296,11 @@ class CLib(object):
     def require_supervisor(self):
         if not self.has_supervisor:
             raise NotImplementedError("%s does not export mm_supervise: safety_guarantee='priority' needs the HIP library"
+                                      % os.path.basename(self.path))
+
+    def require_policy_gi(self):
+        if not self.has_policy_gi:
+            raise NotImplementedError("%s does not export mm_policy_gi_act: the fused shared actor-critic needs the HIP library"
                                       % os.path.basename(self.path))
 
     def state_layout(self, E, N):

@@ -17,7 +17,9 @@ bookkeeping) + bootstrap + discounting -- into one hipGraph on first use and rep
 the graph exactly as they do eagerly).
 
 Networks mirror marl/single_agent/Model_common.py:5-41 (state -> 128 -> 128 -> n_a, log-softmax;
-critic takes the one-hot action after the first layer).
+critic takes the one-hot action after the first layer) and, for MAPPO_GI with shared_network = True,
+marl/single_agent/Model_gi.py:137-216 (ActorCriticNetwork: split first layer, shared trunk, actor and
+critic heads; fused on the device as `mm_policy_gi_act`, include/mm_policy_gi.h).
 """
 import torch
 from torch import nn
@@ -55,6 +57,59 @@ class CriticNetwork(nn.Module):
         return self.fc3(out)
 
 
+# Model_gi.py:170-199: the state split reads columns 0..24 as five 5-column blocks, whatever the row width (on
+# merge-multi-agent-v1, 6 columns per row, it straddles rows and never reads columns 25..29 -- the reference's behaviour)
+SPLIT_COLS = ([5 * b for b in range(5)],
+              [5 * b + c for b in range(5) for c in (1, 2)],
+              [5 * b + c for b in range(5) for c in (3, 4)])
+
+
+class ActorCriticNetwork(nn.Module):
+    """Model_gi.py:137-216, MAPPO_GI's network with shared_network = True (marl/mappo_gi.py:138-146 builds it with
+    state_split=True).  Parameter names are the reference's, so `load_state_dict(checkpoint["model_state_dict"])` of a
+    MAPPO_GI checkpoint loads."""
+
+    def __init__(self, state_dim, action_dim, hidden_size, critic_output_size=1, state_split=False):
+        super().__init__()
+        self.state_split = state_split
+        if state_split:
+            self.fc11 = nn.Linear(5, hidden_size // 4)
+            self.fc12 = nn.Linear(10, hidden_size // 2)
+            self.fc13 = nn.Linear(10, hidden_size // 2)
+            self.fc2 = nn.Linear(hidden_size // 4 + hidden_size // 2 + hidden_size // 2, hidden_size)
+        else:
+            self.fc1 = nn.Linear(state_dim, hidden_size)
+            self.fc2 = nn.Linear(hidden_size, hidden_size)
+        self.actor_linear = nn.Linear(hidden_size, action_dim)
+        self.critic_linear = nn.Linear(hidden_size, critic_output_size)
+        for k, cols in enumerate(SPLIT_COLS):
+            self.register_buffer("_split%d" % (k + 1), torch.tensor(cols, dtype=torch.long), persistent=False)
+
+    def split(self, state):
+        """(state1, state2, state3) of Model_gi.py:170-199."""
+        return tuple(state.index_select(1, idx) for idx in (self._split1, self._split2, self._split3))
+
+    def trunk(self, state):
+        if self.state_split:
+            s1, s2, s3 = self.split(state)
+            out = torch.cat([torch.relu(self.fc11(s1)), torch.relu(self.fc12(s2)), torch.relu(self.fc13(s3))], 1)
+        else:
+            out = torch.relu(self.fc1(state))
+        return torch.relu(self.fc2(out))
+
+    def forward(self, state, action_mask=None, out_type="p"):
+        """out_type "p": log-softmax of the actor head (invalid actions at -1e8, then log_softmax(logits + 1e-8), when a
+        mask is given); anything else: the critic head (Model_gi.py:205-216)."""
+        out = self.trunk(state)
+        if out_type != "p":
+            return self.critic_linear(out)
+        logits = self.actor_linear(out)
+        if action_mask is None:
+            return torch.log_softmax(logits, dim=1)
+        logits = logits.masked_fill(action_mask == 0, -1e8)
+        return torch.log_softmax(logits + 1e-8, dim=1)
+
+
 def discount_rewards(rewards, dones, final_value, gamma):
     """`_discount_reward` (marl/mappo.py:364-370) over a batch.
 
@@ -78,17 +133,31 @@ class DeviceRollout(object):
     def __init__(self, env, actor, critic=None, roll_out_n_steps=100, reward_gamma=0.99, reward_scale=20.0,
                  reward_type="regionalR", generator=None, use_graph=False, sample_seed=0, fused_policy=True):
         assert reward_type in ("regionalR", "global_R")  # marl/mappo.py:39
+        # shared mode (MAPPO_GI, shared_network = True): one ActorCriticNetwork is the actor (out_type "p") and the
+        # critic (out_type "v"); pass it as `actor`, with critic None or the same module
+        self.shared = isinstance(actor, ActorCriticNetwork)
+        if self.shared:
+            if critic is not None and critic is not actor:
+                raise ValueError("an ActorCriticNetwork is its own critic: pass critic=None or the same module")
+            critic = None
         self.env, self.actor, self.critic = env, actor, critic
         self.T, self.gamma, self.reward_scale, self.reward_type = roll_out_n_steps, reward_gamma, reward_scale, reward_type
         self.generator = generator
         self.n_a = env.n_a
         self.sample_seed = int(sample_seed) & 0xFFFFFFFFFFFFFFFF
-        # fused actor + sampling launch for the reference's ActorNetwork (hidden 128); anything else goes
-        # through the module's own forward
-        self.fused_policy = bool(fused_policy) and type(actor) is ActorNetwork and actor.fc2.weight.shape[0] == 128 \
-            and next(actor.parameters()).dtype == torch.float32
         self.obs, _ = env.reset()
         self.obs = self.obs.clone()
+        # fused actor + sampling launch for the reference's ActorNetwork (hidden 128), and for its state-split
+        # ActorCriticNetwork (hidden 128) on the device; anything else goes through the module's own forward
+        f32 = next(actor.parameters()).dtype == torch.float32
+        if self.shared:
+            # mm_policy_gi_act is a HIP-library entry (the CPU oracle has no twin: there the module is the CPU form)
+            self.fused_policy = bool(fused_policy) and type(actor) is ActorCriticNetwork and actor.state_split and f32 \
+                and actor.fc2.weight.shape[0] == 128 and self.obs.device.type == "cuda"
+            if self.fused_policy:
+                env.clib.require_policy_gi()
+        else:
+            self.fused_policy = bool(fused_policy) and type(actor) is ActorNetwork and actor.fc2.weight.shape[0] == 128 and f32
         self._sample_counter = torch.zeros(1, dtype=torch.int64, device=self.obs.device)  # advanced by mm_sample_actions
         self.use_graph = bool(use_graph)
         if self.use_graph:
@@ -120,8 +189,28 @@ class DeviceRollout(object):
             return self._act(obs, out.view(-1))
         return self._act(obs, None)
 
+    def _policy_gi(self, obs, actions, value):
+        """One mm_policy_gi_act launch on the env's stream (include/mm_policy_gi.h).  actions: int32 [E*N] or None
+        (value-only: the sampler's counter is untouched); value: float32 [E*N] or None."""
+        a, clib = self.actor, self.env.clib
+        E, N, S = obs.shape
+        ptr = lambda t: t.detach().contiguous().data_ptr()  # noqa: E731  (nn.Linear parameters are contiguous)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        clib.check(clib.lib.mm_policy_gi_act(obs.contiguous().data_ptr(), E * N, S, ptr(a.fc11.weight), ptr(a.fc11.bias),
+                                             ptr(a.fc12.weight), ptr(a.fc12.bias), ptr(a.fc13.weight), ptr(a.fc13.bias),
+                                             ptr(a.fc2.weight), ptr(a.fc2.bias), ptr(a.actor_linear.weight),
+                                             ptr(a.actor_linear.bias), ptr(a.critic_linear.weight), ptr(a.critic_linear.bias),
+                                             a.fc2.weight.shape[0], self.n_a, self.sample_seed,
+                                             self._sample_counter.data_ptr() if actions is not None else None, opt(actions),
+                                             None, opt(value), self.env._stream()))
+
     def _act(self, obs, dst):
         E, N, S = obs.shape
+        if self.generator is None and self.fused_policy and self.shared and obs.dtype == torch.float32:
+            # shared actor-critic forward + sampling in ONE launch (mm_policy_gi_act)
+            actions = dst if dst is not None else torch.empty(E * N, dtype=torch.int32, device=obs.device)
+            self._policy_gi(obs, actions, None)
+            return actions.view(E, N)
         if self.generator is None and self.fused_policy and type(self.actor) is ActorNetwork and obs.dtype == torch.float32:
             # actor forward + sampling in ONE launch (mm_policy_act: f32 MFMA, activations in registers)
             a, clib = self.actor, self.env.clib
@@ -213,7 +302,18 @@ class DeviceRollout(object):
         self.obs = obs.clone()
         # bootstrap value for envs still mid-episode (marl/mappo.py:147-150); 0 where the last step ended one
         final_value = torch.zeros(E, N, dtype=torch.float64, device=dev)
-        if self.critic is not None:
+        if self.shared:
+            # MAPPO_GI.action(final_state) then .value (marl/mappo_gi.py:371-395): the final actions are drawn (the stream
+            # advances as in act()) but the shared critic does not read them
+            if self.generator is None and self.fused_policy and obs.dtype == torch.float32:
+                fa = torch.empty(E * N, dtype=torch.int32, device=dev)
+                val = torch.empty(E * N, dtype=torch.float32, device=dev)
+                self._policy_gi(obs, fa, val)  # draw + value in one launch
+            else:
+                self.act(obs)
+                val = self.actor(obs.reshape(E * N, S).float(), out_type="v")
+            final_value = torch.where(dones[-1].bool().unsqueeze(-1), final_value, val.view(E, N).double())
+        elif self.critic is not None:
             fa = self.act(obs)
             # (not F.one_hot: its device-side range asserts do not survive hipGraph capture)
             one_hot = (fa.unsqueeze(-1) == torch.arange(self.n_a, device=dev, dtype=fa.dtype)).float()
