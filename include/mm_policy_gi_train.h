@@ -1,0 +1,80 @@
+/*
+ * mm_policy_gi_train.h -- loss and full parameter gradient of MAPPO_GI's shared actor-critic (shared_network = True).
+ *
+ * The network is the one of include/mm_policy_gi.h (Model_gi.ActorCriticNetwork(state_split=True), hidden 128); the
+ * objective is the shared branch of MAPPO_GI.train() (marl/mappo_gi.py:305-339) for ONE batch of samples:
+ *
+ *   logp_j  = log_softmax(actor_linear(trunk(obs_j)))[action_j]         value_j = critic_linear(trunk(obs_j))
+ *   r_j     = exp(logp_j - old_logp_j)                                  c_j = clip(r_j, 1 - clip_param, 1 + clip_param)
+ *   critic  = (1 / B) sum_j l(value_j - returns_j)       l(d) = d^2 (MM_GI_CRITIC_MSE) | smooth_l1, beta = 1 (MM_GI_CRITIC_HUBER)
+ *   actor   = one of two forms, chosen by adv_sums:
+ *     adv_sums != NULL  the reference's own arithmetic.  There `ratio` is [B] and `advantages = returns - values.detach()`
+ *                       is [B, 1], so `ratio * advantages` broadcasts to [B, B] and the loss is
+ *                       -mean_{i,j} min(r_j A_i, c_j A_i) = -(1 / B^2) sum_j [S+ min(r_j, c_j) + S- max(r_j, c_j)],
+ *                       S+ = sum of the non-negative A_i, S- = sum of the negative A_i: adv_sums = DEV float[2] {S+, S-}
+ *                       (the caller gets them from a value-only mm_policy_gi_act pass and two reductions).
+ *     adv_sums == NULL  textbook PPO-clip: -(1 / B) sum_j min(r_j A_j, c_j A_j), A_j = returns_j - value_j with value_j
+ *                       from this launch's own forward, detached.
+ *   loss = actor + critic; its gradient reaches the shared trunk from both heads.
+ * B is the number of valid samples (valid == NULL: n).  d min(r, c)/dr is 1 for r <= 1 + clip_param and 0 above,
+ * d max(r, c)/dr is 1 for r >= 1 - clip_param and 0 below: what torch.autograd returns off the two clip edges.
+ *
+ * Three kernels after a small preparation launch: A, the per-sample forward + backward on f32 MFMA (activations and their
+ * gradients go to `scratch` in [sample][feature] order); B, the weight-gradient contractions over the sample dimension,
+ * split over workgroups that each write one partial block; C, the fold of the partial blocks in a fixed order.  No
+ * floating-point atomics anywhere: two calls on the same inputs give bit-identical outputs.  Only enqueues work on
+ * `stream` (no allocation, no synchronisation): graph-capturable.
+ *
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_gi_train.hip), like mm_policy_gi_act: no oracle twin, not
+ * part of include/mm_abi.h's symbol list or version.  torch.autograd on rollout.ActorCriticNetwork is the CPU form.
+ */
+#ifndef MM_POLICY_GI_TRAIN_H
+#define MM_POLICY_GI_TRAIN_H
+
+#include <stdint.h>
+
+#include "mm_abi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MM_GI_CRITIC_MSE 0
+#define MM_GI_CRITIC_HUBER 1
+
+/* The twelve parameter tensors of the network (or their gradients), torch nn.Linear layout [out][in], float32, DEV:
+ *   W11 [32][5], b11 [32]; W12 [64][10], b12 [64]; W13 [64][10], b13 [64]; W2 [128][160], b2 [128];
+ *   Wa [n_a][128], ba [n_a]; Wc [1][128], bc [1]. */
+typedef struct MMGiParams {
+  float *W11, *b11, *W12, *b12, *W13, *b13, *W2, *b2, *Wa, *ba, *Wc, *bc;
+} MMGiParams;
+
+/* Bytes of scratch mm_policy_gi_train needs for n samples (n >= 0). */
+int32_t mm_policy_gi_train_scratch_bytes(int64_t n, uint64_t *bytes);
+
+/*
+ * obs: DEV float, sample j's row at obs + j * obs_stride (floats; >= n_s), 25 <= n_s <= 32 (columns 0..24 are read).
+ * actions: DEV int32, sample j at actions[j * act_stride]; a value outside 0..n_a-1 is the caller's error and is clamped.
+ * returns: DEV float, sample j at returns[j * ret_stride].   old_logp: DEV float[n], the target network's log-probability of
+ * the taken action.   valid: optional DEV uint8[n]; samples with valid[j] == 0 contribute nothing and are not counted in B
+ * (their obs / actions / returns / old_logp are not read).
+ * weights: the network's parameters (read only).   hidden must be 128; 1 <= n_a <= 8.
+ * grads: the twelve gradients, WRITTEN (not accumulated).   loss: DEV float[3] = actor loss, critic loss, their sum.
+ * logp_taken / value / ratio: optional DEV float[n] diagnostics (0 where valid[j] == 0).
+ * scratch: DEV, scratch_bytes >= mm_policy_gi_train_scratch_bytes(n), 16-byte aligned; contents are undefined afterwards.
+ * n == 0 or no valid sample: gradients and losses are written as zeros.  n is limited to 2^31 - 1 (B is a 32-bit count).
+ * The scratch is 2 496 bytes per sample plus up to 56 MB of partial blocks and is not chunked: 1.27 GiB at 524 288 samples;
+ * a caller with more samples than it can afford scratch for splits the batch itself (one optimiser step per part).
+ * MM_ERR_INVALID_ARG: a NULL input, weight or output pointer, n < 0, n_s outside 25..32, obs_stride < n_s, hidden != 128,
+ *   n > 2^31 - 1, n_a outside 1..8, critic_loss not one of the two, clip_param < 0, scratch NULL / too small / misaligned.
+ */
+int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                           int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                           const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a, float clip_param,
+                           int32_t critic_loss, const float *adv_sums, const MMGiParams *grads, float *loss, float *logp_taken,
+                           float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MM_POLICY_GI_TRAIN_H */

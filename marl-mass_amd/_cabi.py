@@ -70,6 +70,15 @@ class MMStepOut(C.Structure):
         "trace")]
 
 
+GI_PARAMS = ("W11", "b11", "W12", "b12", "W13", "b13", "W2", "b2", "Wa", "ba", "Wc", "bc")
+GI_CRITIC_LOSS = {"mse": 0, "huber": 1}  # MM_GI_CRITIC_* (include/mm_policy_gi_train.h)
+
+
+class MMGiParams(C.Structure):
+    """The twelve parameter (or gradient) pointers of the shared actor-critic (include/mm_policy_gi_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in GI_PARAMS]
+
+
 SUPERVISED = ("priority", "dmc")
 
 
@@ -271,6 +280,15 @@ class CLib(object):
         if self.has_policy_gi:
             lib.mm_policy_gi_act.argtypes = [vp, i64, i32] + [vp] * 12 + [i32, i32, u64, vp, vp, vp, vp, vp]
             lib.mm_policy_gi_act.restype = i32
+        # the shared actor-critic's loss + parameter gradient (include/mm_policy_gi_train.h), also libmm_hip.so only
+        self.has_policy_gi_train = hasattr(lib, "mm_policy_gi_train")
+        if self.has_policy_gi_train:
+            f32 = C.c_float
+            lib.mm_policy_gi_train_scratch_bytes.argtypes = [i64, C.POINTER(u64)]
+            lib.mm_policy_gi_train_scratch_bytes.restype = i32
+            lib.mm_policy_gi_train.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, vp, C.POINTER(MMGiParams), i32, i32, f32,
+                                               i32, vp, C.POINTER(MMGiParams), vp, vp, vp, vp, vp, u64, vp]
+            lib.mm_policy_gi_train.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -302,6 +320,18 @@ class CLib(object):
         if not self.has_policy_gi:
             raise NotImplementedError("%s does not export mm_policy_gi_act: the fused shared actor-critic needs the HIP library"
                                       % os.path.basename(self.path))
+
+    def require_policy_gi_train(self):
+        if not self.has_policy_gi_train:
+            raise NotImplementedError("%s does not export mm_policy_gi_train: the shared actor-critic's gradient needs the HIP "
+                                      "library" % os.path.basename(self.path))
+
+    def policy_gi_train_scratch_bytes(self, n):
+        """Bytes of scratch mm_policy_gi_train needs for n samples (include/mm_policy_gi_train.h)."""
+        self.require_policy_gi_train()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_gi_train_scratch_bytes(n, C.byref(b)))
+        return b.value
 
     def state_layout(self, E, N):
         lay = MMStateLayout()

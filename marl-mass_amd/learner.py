@@ -1,0 +1,193 @@
+"""The learner of MAPPO_GI with shared_network = True on the device: `MAPPO_GI.train()` (marl/mappo_gi.py:232-352, the shared
+branch :305-352) with the loss and the full parameter gradient taken by one library call (`mm_policy_gi_train`,
+include/mm_policy_gi_train.h) instead of torch autograd.
+
+What stays torch: the optimiser arithmetic (RMSprop / Adam on 22 982 parameters), `clip_grad_norm_` and the soft target
+update -- a few launches on 90 KB.  What the library does: the network forward on every sample, the PPO-clip and critic
+losses, and the backward into all twelve parameter tensors, deterministically (no floating-point atomics).
+
+The reference's actor loss is kept literally.  There `ratio` has shape [B] and `advantages = returns - values.detach()` has
+shape [B, 1], so `ratio * advantages` broadcasts to [B, B]: every sample's ratio is weighted by EVERY sample's advantage,
+-mean_{i,j} min(r_j A_i, clip(r_j) A_i) = -(1 / B^2) sum_j [S+ min(r_j, c_j) + S- max(r_j, c_j)] with S+ / S- the sums of the
+non-negative / negative advantages.  `form="reference"` computes exactly that (it is what the reference's checkpoints were
+trained with, and tests/golden/gi_train_*.npz pin it to the reference's own run); `form="flat"` is textbook per-sample
+PPO-clip on all B * N samples in one optimiser step.
+"""
+import copy
+import ctypes as C
+
+import torch
+
+from . import _cabi as abi
+from .rollout import ActorCriticNetwork
+
+PARAM_ORDER = ("fc11", "fc12", "fc13", "fc2", "actor_linear", "critic_linear")  # MMGiParams' order: weight, bias of each
+
+
+def _params(net):
+    out = []
+    for name in PARAM_ORDER:
+        m = getattr(net, name)
+        out += [m.weight, m.bias]
+    return out
+
+
+class SharedPPOLearner(object):
+    """`MAPPO_GI(shared_network=True)`'s policy / policy_target / policy_optimizer and its train(); defaults are
+    MAPPO_GI.__init__'s (marl/mappo_gi.py:28-57).  `policy` is a rollout.ActorCriticNetwork(state_split=True), hidden 128,
+    float32, on the device -- typically the module a DeviceRollout acts with, so the next rollout uses the updated weights."""
+
+    def __init__(self, policy, clib, lr=1e-4, optimizer_type="rmsprop", clip_param=0.2, critic_loss="mse", max_grad_norm=0.5,
+                 target_tau=1.0, target_update_steps=5):
+        if type(policy) is not ActorCriticNetwork or not policy.state_split or policy.fc2.weight.shape[0] != 128:
+            raise ValueError("SharedPPOLearner needs rollout.ActorCriticNetwork(state_split=True) with hidden size 128")
+        p0 = policy.fc2.weight
+        if p0.dtype != torch.float32 or p0.device.type != "cuda":
+            raise ValueError("SharedPPOLearner needs a float32 policy on the device")
+        if critic_loss not in abi.GI_CRITIC_LOSS:
+            raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
+        clib.require_policy_gi()
+        clib.require_policy_gi_train()
+        self.policy, self.clib = policy, clib
+        self.policy_target = copy.deepcopy(policy)
+        if optimizer_type == "adam":
+            self.optimizer = torch.optim.Adam(policy.parameters(), lr=lr)
+        elif optimizer_type == "rmsprop":
+            self.optimizer = torch.optim.RMSprop(policy.parameters(), lr=lr)
+        else:
+            raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
+        self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
+        self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
+        self.n_a = policy.actor_linear.weight.shape[0]
+        self.device = p0.device
+        for p in policy.parameters():  # the library writes the gradients straight into .grad
+            if p.grad is None or not p.grad.is_contiguous():
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        self._scratch = None
+
+    # -- plumbing ----------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ensure_scratch(self, n):
+        need = self.clib.policy_gi_train_scratch_bytes(n)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
+        return self._scratch
+
+    def _act(self, net, obs, logp=None, value=None):
+        """Value-only mm_policy_gi_act of `net` on contiguous obs [n, S] (nothing sampled)."""
+        n, S = obs.shape
+        w = [p.detach().data_ptr() for p in _params(net)]
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_gi_act(obs.data_ptr(), n, S, *w, 128, self.n_a, 0, None, None, opt(logp), opt(value),
+                                                       self._stream()))
+
+    def old_log_probs(self, obs, actions):
+        """policy_target's log-probability of the taken actions (marl/mappo_gi.py:317-322).  obs [n, S], actions [n]."""
+        obs = obs.contiguous()
+        logp = torch.empty(obs.shape[0], self.n_a, dtype=torch.float32, device=self.device)
+        if obs.shape[0]:
+            self._act(self.policy_target, obs, logp=logp)
+        return logp.gather(1, actions.long().clamp(0, self.n_a - 1).unsqueeze(1)).squeeze(1)
+
+    def advantage_sums(self, obs, returns, valid=None):
+        """[S+, S-] of advantages = returns - policy(obs, "v").detach() (:313-314), float32 [2] on the device."""
+        obs = obs.contiguous()
+        value = torch.empty(obs.shape[0], dtype=torch.float32, device=self.device)
+        if obs.shape[0]:
+            self._act(self.policy, obs, value=value)
+        adv = returns - value
+        if valid is not None:
+            adv = torch.where(valid.bool(), adv, torch.zeros_like(adv))
+        return torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, diagnostics=False):
+        """The bare launch: writes d(actor_loss + critic_loss)/d(parameter) into every policy parameter's .grad and returns
+        the float32 [3] tensor (actor loss, critic loss, their sum); with diagnostics also (logp_taken, value, ratio) [n].
+        obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns float32 [n] (any stride),
+        old_logp float32 [n], valid uint8 / bool [n] or None.  adv_sums: float32 [2] (S+, S-) for the reference's [B, B]
+        objective, None for per-sample PPO-clip (see the module docstring).  Only enqueues work: no host synchronisation."""
+        n, S = obs.shape
+        if obs.dtype != torch.float32 or (n and obs.stride(1) != 1):
+            raise ValueError("obs must be float32 [n, S] with contiguous rows")
+        if actions.dtype != torch.int32 or returns.dtype != torch.float32 or actions.dim() != 1 or returns.dim() != 1:
+            raise ValueError("actions must be int32 [n] and returns float32 [n]")
+        if actions.shape[0] != n or returns.shape[0] != n or old_logp.shape[0] != n:
+            raise ValueError("obs, actions, returns and old_logp must have the same length")
+        old_logp = old_logp.to(torch.float32).contiguous()
+        if valid is not None:
+            valid = valid.to(torch.uint8).contiguous()
+        if adv_sums is not None:
+            adv_sums = adv_sums.to(torch.float32).contiguous()
+        W, G = abi.MMGiParams(), abi.MMGiParams()
+        for name, p in zip(abi.GI_PARAMS, _params(self.policy)):
+            if p.grad is None or not p.grad.is_contiguous():
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            setattr(W, name, p.detach().data_ptr())
+            setattr(G, name, p.grad.data_ptr())
+        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        diag = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3)] if diagnostics else [None] * 3
+        scratch = self._ensure_scratch(n)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_gi_train(
+            obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
+            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), C.byref(W), self.policy.fc2.weight.shape[0], self.n_a,
+            self.clip_param, abi.GI_CRITIC_LOSS[self.critic_loss], opt(adv_sums), C.byref(G), loss.data_ptr(), opt(diag[0]),
+            opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream()))
+        return (loss, tuple(diag)) if diagnostics else loss
+
+    # -- MAPPO_GI.train() ----------------------------------------------------------------------
+    def _step(self, n_episodes):
+        if self.max_grad_norm is not None:
+            torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        self.optimizer.step()
+        if n_episodes % self.target_update_steps == 0 and n_episodes > 0:  # _soft_update_target (:348-352, :545-547)
+            with torch.no_grad():
+                for t, s in zip(self.policy_target.parameters(), self.policy.parameters()):
+                    t.copy_((1.0 - self.target_tau) * t + self.target_tau * s)
+
+    @torch.no_grad()
+    def train(self, states, actions=None, returns=None, n_episodes=0, form="reference", valid=None):
+        """One call of MAPPO_GI.train() on a batch.
+
+        states [B, N, S] (or [T, E, N, S]: B = T * E), actions [B, N], returns [B, N]; or `DeviceRollout.interact()`'s dict
+        as the first argument.  form "reference": for agent_id in order, one optimiser step on the B samples of that agent
+        with the reference's [B, B] objective -- N sequential steps, the target's log-probabilities and the advantages taken
+        with the parameters as they are at that step, as the reference does.  form "flat": ONE optimiser step on all B * N
+        samples with the per-sample PPO-clip objective; `valid` [B, N] masks the empty slots of ragged batches (kind == 0).
+        The soft update of the target runs after each optimiser step when n_episodes % target_update_steps == 0 and
+        n_episodes > 0.  Returns the list of float32 [3] loss tensors (one per optimiser step); nothing is synchronised."""
+        if isinstance(states, dict):
+            states, actions, returns = states["states"], states["actions"], states["returns"]
+        N, S = states.shape[-2], states.shape[-1]
+        states = states.reshape(-1, N, S)
+        if states.dtype != torch.float32:
+            states = states.float()
+        actions = actions.reshape(-1, N)
+        if actions.dtype != torch.int32:
+            actions = actions.to(torch.int32)
+        returns = returns.reshape(-1, N)
+        if returns.dtype != torch.float32:
+            returns = returns.float()  # (DeviceRollout's returns are float64: converted once)
+        if valid is not None:
+            valid = valid.reshape(-1, N).to(torch.uint8)
+        losses = []
+        if form == "reference":
+            for agent_id in range(N):
+                obs, act, ret = states[:, agent_id, :], actions[:, agent_id], returns[:, agent_id]
+                v = None if valid is None else valid[:, agent_id]
+                dense = obs.contiguous()
+                old = self.old_log_probs(dense, act)
+                sums = self.advantage_sums(dense, ret, v)
+                losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, adv_sums=sums))
+                self._step(n_episodes)
+        elif form == "flat":
+            obs, act, ret = states.reshape(-1, S), actions.reshape(-1), returns.reshape(-1)
+            v = None if valid is None else valid.reshape(-1)
+            old = self.old_log_probs(obs, act)
+            losses.append(self.loss_and_grad(obs, act, ret, old, valid=v))
+            self._step(n_episodes)
+        else:
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        return losses
