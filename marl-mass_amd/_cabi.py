@@ -79,6 +79,15 @@ class MMGiParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in GI_PARAMS]
 
 
+MLP_PARAMS = ("W1", "b1", "W2", "b2", "W3", "b3")
+PT_CRITIC_LOSS = {"mse": 0, "huber": 1}  # MM_PT_CRITIC_* (include/mm_policy_train.h)
+
+
+class MMMlpParams(C.Structure):
+    """The six parameter (or gradient) pointers of MAPPO's actor or critic (include/mm_policy_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in MLP_PARAMS]
+
+
 SUPERVISED = ("priority", "dmc")
 
 
@@ -289,6 +298,18 @@ class CLib(object):
             lib.mm_policy_gi_train.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, vp, C.POINTER(MMGiParams), i32, i32, f32,
                                                i32, vp, C.POINTER(MMGiParams), vp, vp, vp, vp, vp, u64, vp]
             lib.mm_policy_gi_train.restype = i32
+        # MAPPO's separate actor + critic: loss + gradients and the forward-only evaluation (include/mm_policy_train.h),
+        # also libmm_hip.so only
+        self.has_policy_train = hasattr(lib, "mm_policy_train")
+        if self.has_policy_train:
+            f32, pp = C.c_float, C.POINTER(MMMlpParams)
+            lib.mm_policy_eval.argtypes = [vp, i64, i64, i32, vp, i64, vp, pp, pp, i32, i32, vp, vp, vp]
+            lib.mm_policy_eval.restype = i32
+            lib.mm_policy_train_scratch_bytes.argtypes = [i64, C.POINTER(u64)]
+            lib.mm_policy_train_scratch_bytes.restype = i32
+            lib.mm_policy_train.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, vp, pp, pp, i32, i32, f32, i32, vp, vp, pp, pp,
+                                            vp, vp, vp, vp, vp, u64, vp]
+            lib.mm_policy_train.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -331,6 +352,18 @@ class CLib(object):
         self.require_policy_gi_train()
         b = C.c_uint64()
         self.check(self.lib.mm_policy_gi_train_scratch_bytes(n, C.byref(b)))
+        return b.value
+
+    def require_policy_train(self):
+        if not self.has_policy_train:
+            raise NotImplementedError("%s does not export mm_policy_train: the separate actor's and critic's gradients need the "
+                                      "HIP library" % os.path.basename(self.path))
+
+    def policy_train_scratch_bytes(self, n):
+        """Bytes of scratch mm_policy_train needs for n samples (include/mm_policy_train.h)."""
+        self.require_policy_train()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_train_scratch_bytes(n, C.byref(b)))
         return b.value
 
     def state_layout(self, E, N):

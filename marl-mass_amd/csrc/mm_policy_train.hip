@@ -1,0 +1,676 @@
+// mm_policy_train.hip -- loss and parameter gradient of MAPPO's separate actor and critic (include/mm_policy_train.h), and the
+// forward-only mm_policy_eval.
+//
+// The shape is mm_policy_gi_train.hip's: every layer transposed, H_out^T [feature x sample] = W . H_in^T, one wave per 32
+// samples, v_mfma_f32_32x32x2_f32; an accumulator tile -- sample on the lane, lane (j, h) holding feature
+// row(r, h) = (r & 3) + 8 (r >> 2) + 4 h in register r -- is directly the B operand of the next layer.  Both networks are
+// "n_s -> 128 -> 128 -> head", so ONE kernel template serves them (kCritic) and, without the backward, mm_policy_eval (!kTrain).
+//
+//   prep      W2[:, :128]^T of each given network in MFMA A-fragment order into the scratch (64 KB each), and B = the number
+//             of valid samples.
+//   kernel A  per sample: fc1 (K = n_s padded to 32: 16 k-steps x 4 tiles), fc2 (K = 128: 64 k-steps x 4 tiles), the head on
+//             the VALU (<= 8 rows), then the loss terms and dlogit / dvalue; dz2 = W3^T dhead . [h2 > 0] on the VALU;
+//             dz1 = (W2[:, :128]^T dz2) . [h1 > 0] as a second 128 x 128 MFMA contraction whose A operand comes from the
+//             fragment array `prep` wrote (global, L2 resident: reading transposed fragments out of the one staged LDS copy
+//             would put the 64 lanes of a read on 8 banks -- the trap recorded in mm_policy_gi_train.hip).
+//             The critic's fc2 has K = 128 + n_a with a one-hot block: in the forward that block is a column gather,
+//             z2 = b2 + W2[:, 128 + a_j] + W2[:, :128] h1, added where the accumulator is initialised, out of an [8][128]
+//             LDS table (rows padded to 136 floats: lanes with different actions land on different banks); in the backward
+//             dW2[:, 128 + a] = sum_j dz2_j [a_j = a] is a fifth column tile of kernel B whose B operand is the one-hot row
+//             rebuilt from the action kept in the sample's head row.  No gradient flows into the one-hot input.
+//             Stores h1, dz1, h2, dz2 (128 each), dhead (16: the actor's dlogit 0..7 | the critic's dvalue in column 0 and
+//             the clamped action, as a float, in column 15) and x (32: the observation, zeros past n_s) per sample in
+//             [sample][feature] order, gradient rows of masked / out-of-range samples as exact zeros, and one loss partial
+//             per 32 samples in fp64.
+//   kernel B  contractions over the sample dimension, the sample index as the MFMA k dimension, both operands coalesced row
+//             reads of the scratch: dW2 = dz2^T [h1 | one_hot] (4 x 4 or 4 x 5 tiles), dW3 = dhead^T h2 (4 tiles), dW1 =
+//             dz1^T x (4 tiles), bias sums on the VALU from the A operands.  5 waves per workgroup: wave w < 4 owns output
+//             rows 32 w .. 32 w + 31 of dW2 and columns of the head tile, wave 4 the first layer.  Each workgroup contracts one
+//             contiguous slice of samples and writes one partial block.
+//   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
+//             torch layout; the loss partials folded by one workgroup in a fixed tree.
+// The actor's three kernels run first, then the critic's over the same scratch (stream order).
+#include "mm_device.h"
+#include "../../include/mm_policy_train.h"
+
+namespace mm {
+namespace pt {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kHidden = 128;
+constexpr int kCat = 160;        // row pitch of the dW2 partial: 128 + the one-hot tile
+constexpr int kOhPitch = 136;    // row pitch of the one-hot column table in LDS
+constexpr int kThreadsA = 512;   // 8 waves = 2 per SIMD
+constexpr int kThreadsB = 320;   // 5 waves
+constexpr int kMaxSlices = 512;  // workgroups of kernel B = partial blocks (2 per CU)
+constexpr int kUnrollB = 4;      // k-steps of kernel B whose loads are issued together
+static_assert(32 % (2 * kUnrollB) == 0, "kernel B walks a slice of whole 32-sample tiles in blocks of 2 * kUnrollB rows");
+constexpr int kDh = 16, kXs = 32;
+constexpr int kActCol = 15;  // column of the head row that carries the critic's action
+
+// scratch layout, in floats
+constexpr long long kHdr = 64;                   // [0] (int) B
+constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network: [out tile 4][k chunk 4][group 4][lane 64] float4
+// partial block of one kernel-B workgroup, in floats
+constexpr int kPW2 = 0;                      // [128][160]
+constexpr int kPHd = kPW2 + kHidden * kCat;  // [16][128]
+constexpr int kPW1 = kPHd + 16 * kHidden;    // [128][32]
+constexpr int kPb2 = kPW1 + kHidden * 32;    // [128]
+constexpr int kPbh = kPb2 + kHidden;         // [16]
+constexpr int kPb1 = kPbh + 16;              // [128]
+constexpr int kPartial = kPb1 + kHidden;     // 26 896
+
+struct Layout {
+  long long n_pad, ntiles;
+  long long frag, h1, dz1, h2, dz2, dh, xs, lossp, part, total;  // offsets in floats
+  int slices;
+  long long slice_rows;
+};
+
+static Layout layout(long long n) {
+  Layout L;
+  L.ntiles = (n + 31) / 32;
+  L.n_pad = L.ntiles * 32;
+  L.frag = kHdr;  // actor's, then the critic's
+  L.h1 = L.frag + 2 * kFrag;
+  L.dz1 = L.h1 + L.n_pad * kHidden;
+  L.h2 = L.dz1 + L.n_pad * kHidden;
+  L.dz2 = L.h2 + L.n_pad * kHidden;
+  L.dh = L.dz2 + L.n_pad * kHidden;
+  L.xs = L.dh + L.n_pad * kDh;
+  L.lossp = L.xs + L.n_pad * kXs;  // double[ntiles]
+  L.part = L.lossp + 2 * L.ntiles;
+  // slices of whole 32-sample tiles; at least 2 tiles per slice
+  long long tiles_per = (L.ntiles + kMaxSlices - 1) / kMaxSlices;
+  if (tiles_per < 2) tiles_per = 2;
+  L.slices = (int)((L.ntiles + tiles_per - 1) / tiles_per);
+  if (L.slices < 1) L.slices = 1;
+  L.slice_rows = tiles_per * 32;
+  L.total = L.part + (long long)L.slices * kPartial;
+  return L;
+}
+
+MM_DEV int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// ---- prep: W2[:, :128]^T fragments of the given networks + the count of valid samples (integer atomics: order-independent)
+__global__ __launch_bounds__(256) void policy_train_prep_kernel(const float *__restrict__ W2a, const float *__restrict__ W2c, int k2c,
+                                                                float4 *__restrict__ frag, const uint8_t *__restrict__ valid,
+                                                                long long n, int *__restrict__ count) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < 2 * 4096) {
+    const bool crit = t >= 4096;
+    const float *W2 = crit ? W2c : W2a;
+    const int k2 = crit ? k2c : kHidden;
+    if (W2) {
+      const int l = t & 63, g = (t >> 6) & 3, m = (t >> 8) & 3, mt = (t >> 10) & 3;
+      const int i = l & 31, h = l >> 5;
+      float w[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) w[u] = W2[(32 * m + frag_row(4 * g + u, h)) * k2 + 32 * mt + i];
+      frag[t] = make_float4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  if (!count) return;
+  if (valid) {
+    int c = 0;
+    for (long long k = t; k < n; k += (long long)gridDim.x * 256) c += valid[k] != 0;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+  } else if (t == 0) {
+    *count = (int)n;
+  }
+}
+
+struct SampleArgs {
+  const float *obs;
+  long long obs_stride, n;
+  int n_s;
+  const int32_t *actions;
+  long long act_stride;
+  const float *returns;
+  long long ret_stride;
+  const float *old_logp;
+  const uint8_t *valid;
+  MMMlpParams w;
+  int n_a;
+  float clip_param;
+  int huber;
+  const float *adv_sums, *advantages;
+  const int *count;
+  const float4 *frag;
+  float *s_h1, *s_dz1, *s_h2, *s_dz2, *s_dh, *s_xs;
+  double *lossp;
+  float *out0, *out1;  // actor: logp_taken, ratio; critic: value, unused
+};
+
+// ---- kernel A
+template <bool kCritic, bool kTrain>
+__global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const SampleArgs p) {
+  __shared__ float4 sW1[4][4][64];   // [out tile][k-step / 4][lane]: 16 KB
+  __shared__ float4 sW2[4][16][64];  // [out tile][k-step / 4][lane]: 64 KB
+  __shared__ __attribute__((aligned(16))) float sWh[8][kHidden];  // head rows (zero past the head's width): 4 KB
+  __shared__ __attribute__((aligned(16))) float sOh[kCritic ? 8 : 1][kOhPitch];  // critic: fc2's one-hot columns, [action][feature]
+  __shared__ __attribute__((aligned(16))) float sB1[kHidden], sB2[kHidden];
+  __shared__ float sBh[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 31, h = lane >> 5;
+  const int n_s = p.n_s, n_a = p.n_a;
+  const int k2 = kCritic ? kHidden + n_a : kHidden;  // fc2's row length
+  const int n_out = kCritic ? 1 : n_a;
+  for (int t = tid; t < 4 * 4 * 64; t += kThreadsA) {
+    const int l = t & 63, q = (t >> 6) & 3, m = t >> 8;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int k = 2 * (4 * q + u) + (l >> 5);
+      v[u] = k < n_s ? p.w.W1[(32 * m + (l & 31)) * n_s + k] : 0.0f;
+    }
+    sW1[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int t = tid; t < 4 * 16 * 64; t += kThreadsA) {
+    const int l = t & 63, q = (t >> 6) & 15, m = t >> 10;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int s = 4 * q + u;
+      v[u] = p.w.W2[(32 * m + (l & 31)) * k2 + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
+    }
+    sW2[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int t = tid; t < 8 * kHidden; t += kThreadsA) {
+    const int o = t / kHidden, c = t % kHidden;
+    sWh[o][c] = o < n_out ? p.w.W3[o * kHidden + c] : 0.0f;
+    if constexpr (kCritic) sOh[o][c] = o < n_a ? p.w.W2[c * k2 + kHidden + o] : 0.0f;
+  }
+  if (tid < kHidden) {
+    sB1[tid] = p.w.b1[tid];
+    sB2[tid] = p.w.b2[tid];
+  }
+  if (tid < 8) sBh[tid] = tid < n_out ? p.w.b3[tid] : 0.0f;
+  __syncthreads();
+  int nb = 0;
+  if (kTrain) nb = *p.count;
+  const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
+  const bool ref_form = p.adv_sums != nullptr;
+  // reference form: S+ and S- are large and nearly cancel while every sample inside the clip band is weighted by their SUM, so
+  // the three possible weights are formed once in fp64 (the sum before the rounding, not after)
+  const double sp_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[0] : 0.0;
+  const double sn_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[1] : 0.0;
+  const double inv_b_d = nb > 0 ? 1.0 / (double)nb : 0.0;
+  const float ref_wp = (float)(sp_d * inv_b_d), ref_wn = (float)(sn_d * inv_b_d), ref_wb = (float)((sp_d + sn_d) * inv_b_d);
+  const float lo = 1.0f - p.clip_param, hi = 1.0f + p.clip_param;
+  const long long n = p.n, ntiles = (n + 31) / 32;
+  constexpr int kWaves = kThreadsA / 64;
+  for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
+    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (policy_gi_kernel's note)
+    const long long ag = tile * 32 + j;
+    bool live = ag < n;
+    if (live && p.valid) live = p.valid[ag] != 0;
+    const float *row = p.obs + (live ? ag : 0) * p.obs_stride;
+    int act = live ? p.actions[ag * p.act_stride] : 0;
+    act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
+    float x[16];
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+      const int k = 2 * s + h;
+      x[s] = (live && k < n_s) ? row[k] : 0.0f;
+    }
+    if (kTrain) {  // x row of the scratch: columns 16 h .. 16 h + 15, zeros past n_s and for a masked sample
+      float4 *dst = reinterpret_cast<float4 *>(p.s_xs + ag * kXs + 16 * h);
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const int c = 16 * h + 4 * g + u;
+          v[u] = (live && c < n_s) ? row[c] : 0.0f;
+        }
+        dst[g] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+    f32x16 h1[4], h2[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      f32x16 acc;
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        const float4 b = *reinterpret_cast<const float4 *>(&sB1[32 * m + 8 * g + 4 * h]);
+        acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const float4 a = sW1[m][q][lane];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, x[4 * q + 0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, x[4 * q + 1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, x[4 * q + 2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, x[4 * q + 3], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; r++) h1[m][r] = fmaxf(acc[r], 0.0f);
+      if (kTrain) {
+        float4 *dst = reinterpret_cast<float4 *>(p.s_h1 + ag * kHidden + 32 * m + 4 * h);
+#pragma unroll
+        for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h1[m][4 * g], h1[m][4 * g + 1], h1[m][4 * g + 2], h1[m][4 * g + 3]);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      f32x16 acc;
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        float4 b = *reinterpret_cast<const float4 *>(&sB2[32 * m + 8 * g + 4 * h]);
+        if constexpr (kCritic) {  // the one-hot block of fc2: column 128 + act
+          const float4 o = *reinterpret_cast<const float4 *>(&sOh[act][32 * m + 8 * g + 4 * h]);
+          b.x += o.x; b.y += o.y; b.z += o.z; b.w += o.w;
+        }
+        acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const float4 a = sW2[m][4 * c + q][lane];
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[c][4 * q + 0], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[c][4 * q + 1], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[c][4 * q + 2], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[c][4 * q + 3], acc, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; r++) h2[m][r] = fmaxf(acc[r], 0.0f);
+      if (kTrain) {
+        float4 *dst = reinterpret_cast<float4 *>(p.s_h2 + ag * kHidden + 32 * m + 4 * h);
+#pragma unroll
+        for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
+      }
+    }
+    // ---- head, the objective's per-sample terms, dhead (both lane halves compute the same numbers)
+    float dhead[8];
+    double t_loss = 0.0;
+    if (kCritic) {
+      float v = 0.0f;
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[0][32 * m + frag_row(r, h)], v);
+      v = v + __shfl_xor(v, 32, 64) + sBh[0];
+      if (h == 0 && ag < n && p.out0) p.out0[ag] = live ? v : 0.0f;
+      if (!kTrain) continue;
+      const float ret = live ? p.returns[ag * p.ret_stride] : 0.0f;
+      const float d = v - ret;
+      float t_critic, dv;
+      if (p.huber) {
+        const float ad = fabsf(d);
+        t_critic = ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
+        dv = ad < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
+      } else {
+        t_critic = d * d;
+        dv = 2.0f * d;
+      }
+      t_loss = (double)t_critic;
+      dhead[0] = live ? dv * inv_b : 0.0f;
+#pragma unroll
+      for (int o = 1; o < 8; o++) dhead[o] = 0.0f;
+    } else {
+      float logit[8];
+#pragma unroll
+      for (int o = 0; o < 8; o++) {
+        float s = 0.0f;
+        if (o < n_a) {
+#pragma unroll
+          for (int m = 0; m < 4; m++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) s = fmaf(h2[m][r], sWh[o][32 * m + frag_row(r, h)], s);
+        }
+        s = s + __shfl_xor(s, 32, 64);
+        logit[o] = o < n_a ? s + sBh[o] : -INFINITY;
+      }
+      float mx = logit[0];
+#pragma unroll
+      for (int o = 1; o < 8; o++) mx = fmaxf(mx, logit[o]);
+      float se = 0.0f;
+#pragma unroll
+      for (int o = 0; o < 8; o++) se += (o < n_a) ? expf(logit[o] - mx) : 0.0f;
+      const float lse = mx + logf(se);
+      float lp_a = 0.0f;
+#pragma unroll
+      for (int o = 0; o < 8; o++) lp_a = (o == act) ? logit[o] - lse : lp_a;
+      if (!kTrain) {
+        if (h == 0 && ag < n && p.out0) p.out0[ag] = live ? lp_a : 0.0f;
+        continue;
+      }
+      const float olp = live ? p.old_logp[ag] : 0.0f;
+      const float r = expf(lp_a - olp);
+      const float c = fminf(fmaxf(r, lo), hi);
+      // actor loss = -(1 / B^2) sum_j [S+ min(r, c) + S- max(r, c)] (reference form) or -(1 / B) sum_j [A+ min + A- max]
+      float wsel;  // the weight that reaches d / dr: the positive one up to 1 + clip, the negative one from 1 - clip
+      if (ref_form) {
+        t_loss = sp_d * (double)fminf(r, c) + sn_d * (double)fmaxf(r, c);
+        wsel = r > hi ? ref_wn : (r < lo ? ref_wp : ref_wb);
+      } else {
+        const float adv = live ? p.advantages[ag] : 0.0f;
+        const float wp = fmaxf(adv, 0.0f), wn = fminf(adv, 0.0f);  // one of them is zero
+        t_loss = (double)wp * (double)fminf(r, c) + (double)wn * (double)fmaxf(r, c);
+        wsel = (r <= hi ? wp : 0.0f) + (r >= lo ? wn : 0.0f);
+      }
+      const float g_lp = live ? -inv_b * wsel * r : 0.0f;  // d loss / d logp_taken
+#pragma unroll
+      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? g_lp * ((o == act ? 1.0f : 0.0f) - expf(logit[o] - lse)) : 0.0f;
+      if (h == 0 && ag < n) {
+        if (p.out0) p.out0[ag] = live ? lp_a : 0.0f;
+        if (p.out1) p.out1[ag] = live ? r : 0.0f;
+      }
+    }
+    {
+      float4 *dst = reinterpret_cast<float4 *>(p.s_dh + ag * kDh + 8 * h);
+      if (h == 0) {
+        dst[0] = make_float4(dhead[0], dhead[1], dhead[2], dhead[3]);
+        dst[1] = make_float4(dhead[4], dhead[5], dhead[6], dhead[7]);
+      } else {
+        dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        dst[1] = make_float4(0.0f, 0.0f, 0.0f, kCritic ? (float)act : 0.0f);  // column kActCol
+      }
+    }
+    // loss partial of this tile: lanes of half 0, fixed butterfly
+    {
+      double pl = (live && h == 0) ? t_loss : 0.0;
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) pl += __shfl_xor(pl, o, 64);
+      if (lane == 0) p.lossp[tile] = pl;
+    }
+    // ---- dz2 = (W3^T dhead) . [h2 > 0], in accumulator form (reuses h2's registers)
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        // the lane's features 32 m + 8 g + 4 h .. + 3 are contiguous in a head row: one ds_read_b128 per row.  Rows past
+        // the head's width are zero in sWh and their dhead is zero, so all rows are summed without a branch.
+        const int f = 32 * m + 8 * g + 4 * h;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+        for (int o = 0; o < (kCritic ? 1 : 8); o++) {
+          const float4 wa = *reinterpret_cast<const float4 *>(&sWh[o][f]);
+          s0 = fmaf(dhead[o], wa.x, s0);
+          s1 = fmaf(dhead[o], wa.y, s1);
+          s2 = fmaf(dhead[o], wa.z, s2);
+          s3 = fmaf(dhead[o], wa.w, s3);
+        }
+        h2[m][4 * g + 0] = h2[m][4 * g + 0] > 0.0f ? s0 : 0.0f;
+        h2[m][4 * g + 1] = h2[m][4 * g + 1] > 0.0f ? s1 : 0.0f;
+        h2[m][4 * g + 2] = h2[m][4 * g + 2] > 0.0f ? s2 : 0.0f;
+        h2[m][4 * g + 3] = h2[m][4 * g + 3] > 0.0f ? s3 : 0.0f;
+      }
+      float4 *dst = reinterpret_cast<float4 *>(p.s_dz2 + ag * kHidden + 32 * m + 4 * h);
+#pragma unroll
+      for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
+    }
+    // ---- dz1 = (W2[:, :128]^T dz2) . [h1 > 0]: 4 output tiles x 64 k-steps, A fragments from global memory
+    unsigned vlane = (unsigned)lane;
+    asm volatile("" : "+v"(vlane));  // opaque per tile: the 64 fragment addresses are formed where they are used, not hoisted
+#pragma unroll
+    for (int mt = 0; mt < 4; mt++) {
+      f32x16 acc;
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) acc[rr] = 0.0f;
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+          const float4 a = (p.frag + ((mt * 4 + m) * 4 + g) * 64)[vlane];  // uniform base + one per-lane offset
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h2[m][4 * g + 0], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h2[m][4 * g + 1], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h2[m][4 * g + 2], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h2[m][4 * g + 3], acc, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        float4 *dst = reinterpret_cast<float4 *>(p.s_dz1 + ag * kHidden + 32 * mt + 4 * h);
+        dst[2 * g] = make_float4(h1[mt][4 * g] > 0.0f ? acc[4 * g] : 0.0f, h1[mt][4 * g + 1] > 0.0f ? acc[4 * g + 1] : 0.0f,
+                                 h1[mt][4 * g + 2] > 0.0f ? acc[4 * g + 2] : 0.0f, h1[mt][4 * g + 3] > 0.0f ? acc[4 * g + 3] : 0.0f);
+      }
+    }
+  }
+}
+
+// ---- kernel B: one workgroup = one slice of samples [row0, row1), rows are whole 32-sample tiles inside n_pad
+template <bool kCritic>
+__global__ __launch_bounds__(kThreadsB) void policy_train_wgrad_kernel(
+    const float *__restrict__ s_h1, const float *__restrict__ s_dz1, const float *__restrict__ s_h2, const float *__restrict__ s_dz2,
+    const float *__restrict__ s_dh, const float *__restrict__ s_xs, long long n_pad, long long slice_rows, float *__restrict__ part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 31, kh = lane >> 5;
+  const long long row0 = (long long)blockIdx.x * slice_rows;
+  long long row1 = row0 + slice_rows;
+  if (row1 > n_pad) row1 = n_pad;
+  float *out = part + (long long)blockIdx.x * kPartial;
+  constexpr int kTiles2 = kCritic ? 5 : 4;
+  if (wave < 4) {
+    const int mf = wave;
+    f32x16 acc[kTiles2], acch;
+#pragma unroll
+    for (int c = 0; c < kTiles2; c++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acch[r] = 0.0f;
+    double bs2 = 0.0, bsh = 0.0;  // bias sums in fp64: one add per k-step, no rounding of a 10^3-term running sum
+    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)  // (a slice is a whole number of 32-sample tiles)
+#pragma unroll
+    for (int u = 0; u < kUnrollB; u++) {
+      const long long row = rb + 2 * u;
+      const float a2 = s_dz2[row * kHidden + 32 * mf + i];
+      const float ah = i < kDh ? s_dh[row * kDh + i] : 0.0f;
+      const float bh = s_h2[row * kHidden + 32 * mf + i];
+      float b1[kTiles2];
+#pragma unroll
+      for (int c = 0; c < 4; c++) b1[c] = s_h1[row * kHidden + 32 * c + i];
+      if (kCritic) b1[kTiles2 - 1] = (float)i == s_dh[row * kDh + kActCol] ? 1.0f : 0.0f;  // one_hot(action) row
+#pragma unroll
+      for (int c = 0; c < kTiles2; c++) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b1[c], acc[c], 0, 0, 0);
+      acch = __builtin_amdgcn_mfma_f32_32x32x2f32(ah, bh, acch, 0, 0, 0);
+      bs2 += (double)a2;
+      bsh += (double)ah;
+    }
+    // accumulator register r of lane (j = i, h = kh): output row frag_row(r, kh), column j
+#pragma unroll
+    for (int c = 0; c < kTiles2; c++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) out[kPW2 + (32 * mf + frag_row(r, kh)) * kCat + 32 * c + i] = acc[c][r];
+#pragma unroll
+    for (int r = 0; r < 8; r++) out[kPHd + frag_row(r, kh) * kHidden + 32 * mf + i] = acch[r];  // rows 0..15
+    bs2 += __shfl_xor(bs2, 32, 64);
+    bsh += __shfl_xor(bsh, 32, 64);
+    if (kh == 0) {
+      out[kPb2 + 32 * mf + i] = (float)bs2;
+      if (mf == 0 && i < kDh) out[kPbh + i] = (float)bsh;
+    }
+  } else {
+    f32x16 acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
+    double bs1[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)
+#pragma unroll
+    for (int u = 0; u < kUnrollB; u++) {
+      const long long row = rb + 2 * u;
+      const float bx = s_xs[row * kXs + i];
+      float a1[4];
+#pragma unroll
+      for (int c = 0; c < 4; c++) a1[c] = s_dz1[row * kHidden + 32 * c + i];
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], bx, acc[c], 0, 0, 0);
+        bs1[c] += (double)a1[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) out[kPW1 + (32 * c + frag_row(r, kh)) * 32 + i] = acc[c][r];
+      const double s = bs1[c] + __shfl_xor(bs1[c], 32, 64);
+      if (kh == 0) out[kPb1 + 32 * c + i] = (float)s;
+    }
+  }
+}
+
+// ---- kernel C: gradient element t = sum over the partial blocks in workgroup order; the last workgroup folds the loss
+MM_DEV float fold(const float *__restrict__ part, int slices, int off) {
+  double s = 0.0;
+#pragma unroll 8
+  for (int g = 0; g < slices; g++) s += (double)part[(long long)g * kPartial + off];
+  return (float)s;
+}
+
+static int fold_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
+
+// loss_mode 0: sum / B (critic); 1: -sum / B (actor, per-sample form); 2: -sum / B^2 (actor, reference form)
+__global__ __launch_bounds__(256) void policy_train_fold_kernel(const float *__restrict__ part, int slices, int n_s, int k2, int n_out,
+                                                                MMMlpParams gr, const double *__restrict__ lossp, long long ntiles,
+                                                                const int *__restrict__ count, int loss_mode, float *__restrict__ loss) {
+  if (blockIdx.x == gridDim.x - 1) {
+    __shared__ double sa[256];
+    double pa = 0.0;
+    for (long long t = threadIdx.x; t < ntiles; t += 256) pa += lossp[t];
+    sa[threadIdx.x] = pa;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+      if ((int)threadIdx.x < o) sa[threadIdx.x] += sa[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const int nb = *count;
+      const double inv = nb > 0 ? 1.0 / (double)nb : 0.0;
+      *loss = (float)(loss_mode == 0 ? sa[0] * inv : (loss_mode == 1 ? -sa[0] * inv : -sa[0] * inv * inv));
+    }
+    return;
+  }
+  int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < kHidden * n_s) { const int o = t / n_s, k = t % n_s; gr.W1[t] = fold(part, slices, kPW1 + o * 32 + k); return; }
+  t -= kHidden * n_s;
+  if (t < kHidden) { gr.b1[t] = fold(part, slices, kPb1 + t); return; }
+  t -= kHidden;
+  if (t < kHidden * k2) { const int o = t / k2, k = t % k2; gr.W2[t] = fold(part, slices, kPW2 + o * kCat + k); return; }
+  t -= kHidden * k2;
+  if (t < kHidden) { gr.b2[t] = fold(part, slices, kPb2 + t); return; }
+  t -= kHidden;
+  if (t < n_out * kHidden) { gr.W3[t] = fold(part, slices, kPHd + t); return; }
+  t -= n_out * kHidden;
+  if (t < n_out) gr.b3[t] = fold(part, slices, kPbh + t);
+}
+
+static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
+
+static bool shape_ok(int64_t n, int32_t n_s, int32_t hidden, int32_t n_a) {
+  return n >= 0 && n <= 0x7FFFFFFF && n_s >= 25 && n_s <= 32 && hidden == kHidden && n_a >= 1 && n_a <= 8;
+}
+
+static unsigned grid_a(long long ntiles) {
+  constexpr int kW = kThreadsA / 64;
+  return (unsigned)(ntiles < kW * 256 ? (ntiles + kW - 1) / kW : 256);  // one persistent workgroup per CU
+}
+
+}  // namespace pt
+}  // namespace mm
+
+extern "C" int32_t mm_policy_eval(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                  int64_t act_stride, const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic,
+                                  int32_t hidden, int32_t n_a, float *logp_taken, float *value, MMStream stream) {
+  using namespace mm::pt;
+  if (!actor && !critic) return MM_ERR_INVALID_ARG;
+  if ((actor && !complete(actor)) || (critic && !complete(critic))) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (n == 0) return MM_OK;  // (empty outputs may be NULL)
+  if ((actor != nullptr) != (logp_taken != nullptr) || (critic != nullptr) != (value != nullptr)) return MM_ERR_INVALID_ARG;
+  if (!obs || !actions || obs_stride < n_s) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  SampleArgs a = {};
+  a.obs = obs; a.obs_stride = obs_stride; a.n = n; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride;
+  a.valid = valid; a.n_a = n_a;
+  const unsigned grid = grid_a((n + 31) / 32);
+  if (actor) {
+    a.w = *actor; a.out0 = logp_taken;
+    hipLaunchKernelGGL((policy_train_sample_kernel<false, false>), dim3(grid), dim3(kThreadsA), 0, s, a);
+  }
+  if (critic) {
+    a.w = *critic; a.out0 = value;
+    hipLaunchKernelGGL((policy_train_sample_kernel<true, false>), dim3(grid), dim3(kThreadsA), 0, s, a);
+  }
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+
+extern "C" int32_t mm_policy_train_scratch_bytes(int64_t n, uint64_t *bytes) {
+  if (n < 0 || !bytes) return MM_ERR_INVALID_ARG;
+  *bytes = (uint64_t)mm::pt::layout(n).total * 4u;
+  return MM_OK;
+}
+
+extern "C" int32_t mm_policy_train(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                   int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                   const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
+                                   int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums, const float *advantages,
+                                   const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, float *logp_taken,
+                                   float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream) {
+  using namespace mm::pt;
+  if ((!actor && !critic) || !loss) return MM_ERR_INVALID_ARG;
+  if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
+  if ((actor && (!complete(actor) || !complete(actor_grads))) || (critic && (!complete(critic) || !complete(critic_grads))))
+    return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
+  if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
+  if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int k2c = kHidden + n_a;
+  if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+  if (n == 0) {
+    for (int net = 0; net < 2; net++) {
+      const MMMlpParams *g = net ? critic_grads : actor_grads;
+      if (!g) continue;
+      const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
+      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
+      const size_t gsz[6] = {(size_t)kHidden * n_s, kHidden, (size_t)kHidden * k2, kHidden, (size_t)n_out * kHidden, (size_t)n_out};
+      for (int k = 0; k < 6; k++)
+        if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+    }
+    return MM_OK;
+  }
+  if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
+  if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;  // (n == 0: empty inputs may be NULL)
+  const Layout L = layout(n);
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *count = (int *)sc;
+  if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
+  hipLaunchKernelGGL(policy_train_prep_kernel, dim3(2 * 4096 / 256), dim3(256), 0, s, actor ? actor->W2 : nullptr,
+                     critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.frag), valid, (long long)n, count);
+  SampleArgs a = {};
+  a.obs = obs; a.obs_stride = obs_stride; a.n = n; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride;
+  a.returns = returns; a.ret_stride = ret_stride; a.old_logp = old_logp; a.valid = valid; a.n_a = n_a;
+  a.clip_param = clip_param; a.huber = critic_loss == MM_PT_CRITIC_HUBER; a.adv_sums = adv_sums; a.advantages = advantages;
+  a.count = count;
+  a.s_h1 = sc + L.h1; a.s_dz1 = sc + L.dz1; a.s_h2 = sc + L.h2; a.s_dz2 = sc + L.dz2; a.s_dh = sc + L.dh; a.s_xs = sc + L.xs;
+  a.lossp = (double *)(sc + L.lossp);
+  const unsigned grid = grid_a(L.ntiles);
+  if (actor) {
+    a.w = *actor; a.frag = (const float4 *)(sc + L.frag); a.out0 = logp_taken; a.out1 = ratio;
+    hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(L.slices), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2,
+                       a.s_dh, a.s_xs, L.n_pad, L.slice_rows, sc + L.part);
+    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, kHidden, n_a) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
+                       L.slices, (int)n_s, kHidden, (int)n_a, *actor_grads, (const double *)a.lossp, L.ntiles, (const int *)count,
+                       adv_sums ? 2 : 1, loss);
+  }
+  if (critic) {
+    a.w = *critic; a.frag = (const float4 *)(sc + L.frag + kFrag); a.out0 = value; a.out1 = nullptr;
+    hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(L.slices), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2,
+                       a.s_dh, a.s_xs, L.n_pad, L.slice_rows, sc + L.part);
+    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, k2c, 1) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
+                       L.slices, (int)n_s, k2c, 1, *critic_grads, (const double *)a.lossp, L.ntiles, (const int *)count, 0, loss + 1);
+  }
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}

@@ -1,4 +1,8 @@
-"""The learner of MAPPO_GI with shared_network = True on the device: `MAPPO_GI.train()` (marl/mappo_gi.py:232-352, the shared
+"""The learners on the device.  `PPOLearner` (below `SharedPPOLearner`) is plain MAPPO's (marl/mappo.py:161-206): separate actor
+and critic, their targets and two optimisers, with both losses and both parameter gradients taken by one library call
+(`mm_policy_train`, include/mm_policy_train.h) and the targets evaluated by `mm_policy_eval`.
+
+`SharedPPOLearner` is the learner of MAPPO_GI with shared_network = True on the device: `MAPPO_GI.train()` (marl/mappo_gi.py:232-352, the shared
 branch :305-352) with the loss and the full parameter gradient taken by one library call (`mm_policy_gi_train`,
 include/mm_policy_gi_train.h) instead of torch autograd.
 
@@ -19,7 +23,7 @@ import ctypes as C
 import torch
 
 from . import _cabi as abi
-from .rollout import ActorCriticNetwork
+from .rollout import ActorCriticNetwork, ActorNetwork, CriticNetwork
 
 PARAM_ORDER = ("fc11", "fc12", "fc13", "fc2", "actor_linear", "critic_linear")  # MMGiParams' order: weight, bias of each
 
@@ -190,4 +194,214 @@ class SharedPPOLearner(object):
             self._step(n_episodes)
         else:
             raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        return losses
+
+
+def _mlp_params(net):
+    """MMMlpParams' order: weight, bias of fc1, fc2, fc3."""
+    return [net.fc1.weight, net.fc1.bias, net.fc2.weight, net.fc2.bias, net.fc3.weight, net.fc3.bias]
+
+
+def _mlp_struct(net, grads=False):
+    st = abi.MMMlpParams()
+    for name, p in zip(abi.MLP_PARAMS, _mlp_params(net)):
+        if grads and (p.grad is None or not p.grad.is_contiguous()):
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        setattr(st, name, p.grad.data_ptr() if grads else p.detach().data_ptr())
+    return st
+
+
+class PPOLearner(object):
+    """`MAPPO`'s actor / critic / actor_target / critic_target / two optimisers and its train() (marl/mappo.py:70-95, :161-206);
+    defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, hidden 128, float32,
+    on the device -- typically the modules a DeviceRollout acts with, so the next rollout uses the updated weights.
+
+    Per agent step the reference takes the actor's loss with advantages from the CRITIC TARGET and old log-probabilities from
+    the ACTOR TARGET, then the critic's loss; the two read disjoint parameters, so one `mm_policy_train` call returns both
+    gradients from the pre-step parameters.  The soft update of both targets runs ONCE per train(), after the agent loop
+    (:203-206), not per agent step as in MAPPO_GI."""
+
+    def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
+                 critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5):
+        if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
+            raise ValueError("PPOLearner needs a rollout.ActorNetwork and a rollout.CriticNetwork")
+        n_s, n_a = actor.fc1.weight.shape[1], actor.fc3.weight.shape[0]
+        if (tuple(actor.fc1.weight.shape) != (128, n_s) or tuple(actor.fc2.weight.shape) != (128, 128)
+                or tuple(actor.fc3.weight.shape) != (n_a, 128) or tuple(critic.fc1.weight.shape) != (128, n_s)
+                or tuple(critic.fc2.weight.shape) != (128, 128 + n_a) or tuple(critic.fc3.weight.shape) != (1, 128)):
+            raise ValueError("PPOLearner needs hidden size 128 in both networks, the same state and action sizes, one critic output")
+        if not 1 <= n_a <= 8 or not 25 <= n_s <= 32:
+            raise ValueError("PPOLearner supports 25..32 state columns and 1..8 actions, got %d and %d" % (n_s, n_a))
+        for p in list(actor.parameters()) + list(critic.parameters()):
+            if p.dtype != torch.float32 or p.device.type != "cuda":
+                raise ValueError("PPOLearner needs float32 networks on the device")
+        if critic_loss not in abi.PT_CRITIC_LOSS:
+            raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
+        if optimizer_type not in ("adam", "rmsprop"):
+            raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
+        clib.require_policy_train()
+        self.actor, self.critic, self.clib = actor, critic, clib
+        self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)
+        opt = torch.optim.Adam if optimizer_type == "adam" else torch.optim.RMSprop
+        self.actor_optimizer = opt(actor.parameters(), lr=actor_lr)
+        self.critic_optimizer = opt(critic.parameters(), lr=critic_lr)
+        self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
+        self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
+        self.n_s, self.n_a = n_s, n_a
+        self.device = actor.fc1.weight.device
+        _mlp_struct(actor, grads=True)  # the library writes the gradients straight into .grad
+        _mlp_struct(critic, grads=True)
+        self._scratch = None
+
+    # -- plumbing ----------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ensure_scratch(self, n):
+        need = self.clib.policy_train_scratch_bytes(n)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
+        return self._scratch
+
+    def _check_batch(self, obs, actions):
+        n, S = obs.shape
+        if obs.dtype != torch.float32 or (n and obs.stride(1) != 1) or S != self.n_s:
+            raise ValueError("obs must be float32 [n, %d] with contiguous rows" % self.n_s)
+        if actions.dtype != torch.int32 or actions.dim() != 1 or actions.shape[0] != n:
+            raise ValueError("actions must be int32 [n]")
+        return n, S
+
+    def evaluate(self, obs, actions, actor=None, critic=None, valid=None):
+        """The bare mm_policy_eval: (logp_taken, value), float32 [n] each (None for a network that is not given), zeros in
+        masked slots.  obs [n, S] with any row stride, actions int32 [n] with any stride."""
+        n, S = self._check_batch(obs, actions)
+        if valid is not None:
+            valid = valid.to(torch.uint8).contiguous()
+        logp = torch.empty(n, dtype=torch.float32, device=self.device) if actor is not None else None
+        value = torch.empty(n, dtype=torch.float32, device=self.device) if critic is not None else None
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ref = lambda net: None if net is None else C.byref(_mlp_struct(net))  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_eval(
+            obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, opt(valid), ref(actor),
+            ref(critic), 128, self.n_a, opt(logp), opt(value), self._stream()))
+        return logp, value
+
+    def old_log_probs(self, obs, actions, valid=None):
+        """actor_target's log-probability of the taken actions (marl/mappo.py:178-179)."""
+        return self.evaluate(obs, actions, actor=self.actor_target, valid=valid)[0]
+
+    def advantages(self, obs, actions, returns, valid=None):
+        """returns - critic_target(obs, one_hot(actions)) (:173-174), float32 [n], zeros in masked slots."""
+        value = self.evaluate(obs, actions, critic=self.critic_target, valid=valid)[1]
+        return self._adv(returns, value, valid)
+
+    @staticmethod
+    def _adv(returns, value, valid):
+        adv = returns - value
+        return adv if valid is None else torch.where(valid.bool(), adv, torch.zeros_like(adv))
+
+    def advantage_sums(self, obs, actions, returns, valid=None):
+        """[S+, S-] of those advantages, float32 [2] on the device: what the reference's [B, B] objective depends on."""
+        adv = self.advantages(obs, actions, returns, valid)
+        return torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, advantages=None, diagnostics=False,
+                      networks="both"):
+        """The bare launch: writes d(actor loss)/d(actor parameter) and d(critic loss)/d(critic parameter) into every
+        parameter's .grad and returns the float32 [2] tensor (actor loss, critic loss); with diagnostics also
+        (logp_taken, value, ratio) [n].  obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns
+        float32 [n] (any stride), old_logp float32 [n], valid uint8 / bool [n] or None.  Exactly one of adv_sums -- float32
+        [2] (S+, S-): the reference's [B, B] objective -- and advantages -- float32 [n]: per-sample PPO-clip.  networks
+        "both" | "actor" | "critic": the other one's gradient and loss are left out (its .grad is not touched, its loss is 0).
+        Only enqueues work: no host synchronisation."""
+        n, S = self._check_batch(obs, actions)
+        if networks not in ("both", "actor", "critic"):
+            raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
+        if returns.dtype != torch.float32 or returns.dim() != 1 or returns.shape[0] != n or old_logp.shape[0] != n:
+            raise ValueError("returns must be float32 [n] and old_logp [n]")
+        old_logp = old_logp.to(torch.float32).contiguous()
+        if valid is not None:
+            valid = valid.to(torch.uint8).contiguous()
+        if adv_sums is not None:
+            adv_sums = adv_sums.to(torch.float32).contiguous()
+        if advantages is not None:
+            if advantages.shape[0] != n:
+                raise ValueError("advantages must be [n]")
+            advantages = advantages.to(torch.float32).contiguous()
+        with_a, with_c = networks != "critic", networks != "actor"
+        W = [_mlp_struct(self.actor) if with_a else None, _mlp_struct(self.critic) if with_c else None]
+        G = [_mlp_struct(self.actor, True) if with_a else None, _mlp_struct(self.critic, True) if with_c else None]
+        ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
+        loss = torch.empty(2, dtype=torch.float32, device=self.device)
+        new = lambda on: torch.empty(n, dtype=torch.float32, device=self.device) if (diagnostics and on) else None  # noqa: E731
+        diag = [new(with_a), new(with_c), new(with_a)]
+        scratch = self._ensure_scratch(n)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_train(
+            obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
+            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), 128, self.n_a, self.clip_param,
+            abi.PT_CRITIC_LOSS[self.critic_loss], opt(adv_sums) if with_a else None, opt(advantages) if with_a else None, ref(G[0]),
+            ref(G[1]), loss.data_ptr(), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream()))
+        return (loss, tuple(diag)) if diagnostics else loss
+
+    # -- MAPPO.train() -------------------------------------------------------------------------
+    def _step(self):
+        """clip_grad_norm_ + step, the actor's then the critic's (:186-188, :199-201): each its own norm and optimiser."""
+        for net, optimizer in ((self.actor, self.actor_optimizer), (self.critic, self.critic_optimizer)):
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm)
+            optimizer.step()
+
+    @torch.no_grad()
+    def soft_update(self):
+        """_soft_update_target of both targets: t = (1 - tau) t + tau s."""
+        for target, source in ((self.actor_target, self.actor), (self.critic_target, self.critic)):
+            for t, s in zip(target.parameters(), source.parameters()):
+                t.copy_((1.0 - self.target_tau) * t + self.target_tau * s)
+
+    @torch.no_grad()
+    def train(self, states, actions=None, returns=None, n_episodes=0, form="reference", valid=None):
+        """One call of MAPPO.train() on a batch.
+
+        states [B, N, S] (or [T, E, N, S]: B = T * E), actions [B, N], returns [B, N]; or `DeviceRollout.interact()`'s dict
+        as the first argument.  form "reference": for agent_id in order, one actor and one critic optimiser step on the B
+        samples of that agent with the reference's [B, B] actor objective -- N sequential steps, each on the parameters as
+        they then are.  form "flat": ONE step per network on all B * N samples with the per-sample PPO-clip objective;
+        `valid` [B, N] masks the empty slots of ragged batches (kind == 0).  The soft update of both targets runs once, after
+        the loop, when n_episodes % target_update_steps == 0 and n_episodes > 0.  Returns the list of float32 [2] loss tensors
+        (one per agent step); nothing is synchronised."""
+        if isinstance(states, dict):
+            states, actions, returns = states["states"], states["actions"], states["returns"]
+        N, S = states.shape[-2], states.shape[-1]
+        states = states.reshape(-1, N, S)
+        if states.dtype != torch.float32:
+            states = states.float()
+        actions = actions.reshape(-1, N)
+        if actions.dtype != torch.int32:
+            actions = actions.to(torch.int32)
+        returns = returns.reshape(-1, N)
+        if returns.dtype != torch.float32:
+            returns = returns.float()  # (DeviceRollout's returns are float64: converted once)
+        if valid is not None:
+            valid = valid.reshape(-1, N).to(torch.uint8)
+        losses = []
+        if form == "reference":
+            for agent_id in range(N):
+                obs, act, ret = states[:, agent_id, :], actions[:, agent_id], returns[:, agent_id]
+                v = None if valid is None else valid[:, agent_id].contiguous()
+                old, value = self.evaluate(obs, act, actor=self.actor_target, critic=self.critic_target, valid=v)
+                adv = self._adv(ret, value, v)
+                sums = torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
+                losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, adv_sums=sums))
+                self._step()
+        elif form == "flat":
+            obs, act, ret = states.reshape(-1, S), actions.reshape(-1), returns.reshape(-1)
+            v = None if valid is None else valid.reshape(-1)
+            old, value = self.evaluate(obs, act, actor=self.actor_target, critic=self.critic_target, valid=v)
+            losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, advantages=self._adv(ret, value, v)))
+            self._step()
+        else:
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        if n_episodes % self.target_update_steps == 0 and n_episodes > 0:
+            self.soft_update()
         return losses
