@@ -1,10 +1,8 @@
 // mm_policy_gi.hip -- MAPPO_GI's shared actor-critic fused with the action sample (include/mm_policy_gi.h).
 //
-// marl/single_agent/Model_gi.py:137-216 ActorCriticNetwork(state_split=True), hidden 128, on f32-input MFMA
-// (v_mfma_f32_32x32x2_f32: exact fp32 products and sums), laid out like policy_kernel in mm_kernels.hip: every layer is
-// computed transposed, H_out^T [feature x agent] = W [out x in] . H_in^T, one wave per 32 agents, so an accumulator tile
-// (agent on the lane, features in the 16 registers, lane (j, h) holding feature row(r, h) = (r & 3) + 8 (r >> 2) + 4 h in
-// register r) is directly the B operand of the next layer and activations never leave the register file.
+// marl/single_agent/Model_gi.py:137-216 ActorCriticNetwork(state_split=True), hidden 128, on f32-input MFMA in the transposed,
+// one-wave-per-32-agents layout that mm_policy_mfma.h describes (it is policy_kernel's in mm_kernels.hip): an accumulator tile
+// is directly the B operand of the next layer and activations never leave the register file.
 //
 //   layer 1  the three split linears as 5 block-diagonal output tiles: tile 0 = fc11 (32 outputs, K = 5 -> 3 k-steps of
 //            2), tiles 1-2 = fc12 and tiles 3-4 = fc13 (K = 10 -> 5 k-steps each).  The split gather happens while the B
@@ -15,26 +13,17 @@
 //            one conflict-free ds_read_b128 per four MFMAs).
 //   heads    actor_linear (n_a <= 8 rows) and critic_linear (1 row) as 64 FMAs per row per lane plus one cross-half add,
 //            then log-softmax (fp32), the value, and the inverse-CDF sample (fp64) of mm_sample_actions, written by h = 0.
-#include "mm_device.h"
+#include "mm_policy_mfma.h"
 #include "../../include/mm_policy_gi.h"
 
 namespace mm {
 namespace gi {
+using namespace mfma;  // kHidden = 128: fc2 outputs (Model_gi hidden_size)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kHidden = 128;               // fc2 outputs (Model_gi hidden_size)
 constexpr int kCat = 160;                  // hidden / 4 + hidden / 2 + hidden / 2
 constexpr int kL1Steps = 3 + 4 * 5;        // A fragments of layer 1: fc11 3 k-steps, 4 tiles of fc12 / fc13 x 5
 constexpr int kThreads = 512;              // 8 waves = 2 per SIMD, as policy_kernel
 constexpr uint32_t kDomain = 0x53414D50u;  // the sampler's Philox domain word (mm_sample_actions / mm_policy_act)
-
-MM_DEV int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// layer-1 fragment q -> (output tile m, k-step s)
-MM_DEV void l1_step(int q, int &m, int &s) {
-  if (q < 3) { m = 0; s = q; }
-  else { m = 1 + (q - 3) / 5; s = (q - 3) % 5; }
-}
 
 __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
     const float *__restrict__ obs, long long n, int n_s, const float *__restrict__ W11, const float *__restrict__ b11,
@@ -60,16 +49,7 @@ __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
     else w = W13[(32 * (m - 3) + (l & 31)) * 10 + k];
     sW1[q][l] = w;
   }
-  for (int t = tid; t < 4 * 20 * 64; t += kThreads) {
-    const int l = t & 63, q = (t >> 6) % 20, m = t / (20 * 64);
-    float w[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int s = 4 * q + u;  // k-step 0..79: 32-feature chunk s >> 4, step in chunk s & 15
-      w[u] = W2[(32 * m + (l & 31)) * kCat + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
-    }
-    sW2[m][q][l] = make_float4(w[0], w[1], w[2], w[3]);
-  }
+  stage_w2<20, kThreads>(sW2, W2, kCat);
   for (int t = tid; t < 9 * kHidden; t += kThreads) {
     const int o = t / kHidden, c = t % kHidden;
     sWh[o][c] = o == 8 ? Wc[c] : (o < n_a ? Wa[o * kHidden + c] : 0.0f);
@@ -85,9 +65,7 @@ __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
   const long long ntiles = (n + 31) / 32;
   constexpr int kWaves = kThreads / 64;
   for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
-    // the weight fragments are tile-invariant: keep the compiler from hoisting the LDS reads out of the persistent loop
-    // (policy_kernel's note: that costs 320 registers and spills the activations)
-    asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
     const long long ag = tile * 32 + j;
     const bool live = ag < n;
     const float *row = obs + (live ? ag : 0) * n_s;
@@ -119,40 +97,20 @@ __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
         for (int s = 0; s < 5; s++)
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW1[q0 + s][lane], m <= 2 ? x2[s] : x3[s], acc, 0, 0, 0);
       }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h1[m][r] = fmaxf(acc[r], 0.0f);
+      h1[m] = relu(acc);
     }
 #pragma unroll
     for (int m = 0; m < 4; m++) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[r] = sB2[32 * m + frag_row(r, h)];
-#pragma unroll
-      for (int c = 0; c < 5; c++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const float4 a = sW2[m][4 * c + q][lane];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[c][4 * q + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[c][4 * q + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[c][4 * q + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[c][4 * q + 3], acc, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h2[m][r] = fmaxf(acc[r], 0.0f);
+      h2[m] = relu(fc2_tile<5>(sW2[m], h1, lane, acc));
     }
     // ---- heads: actor rows 0..n_a-1, critic row 8
     float logit[8];
 #pragma unroll
     for (int o = 0; o < 8; o++) {
-      float p = 0.0f;
-      if (o < n_a) {
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-#pragma unroll
-          for (int r = 0; r < 16; r++) p = fmaf(h2[m][r], sWh[o][32 * m + frag_row(r, h)], p);
-      }
-      p = p + __shfl_xor(p, 32, 64);
+      const float p = head_dot(h2, sWh[o], h, o < n_a);
       logit[o] = o < n_a ? p + sBh[o] : -INFINITY;
     }
     float v = 0.0f;
@@ -163,12 +121,10 @@ __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
         for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[8][32 * m + frag_row(r, h)], v);
       v = v + __shfl_xor(v, 32, 64);
     }
-    float mx = logit[0];
-#pragma unroll
-    for (int o = 1; o < 8; o++) mx = fmaxf(mx, logit[o]);
+    const float mx = max8(logit);
     float se = 0.0f;
 #pragma unroll
-    for (int o = 0; o < 8; o++) se += (o < n_a) ? expf(logit[o] - mx) : 0.0f;
+    for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
     const float lse = mx + logf(se);
     if (live && h == 0) {
       if (value_out) value_out[ag] = v + sBh[8];
@@ -214,8 +170,7 @@ extern "C" int32_t mm_policy_gi_act(const float *obs, int64_t n, int32_t n_s, co
   if (n == 0) return MM_OK;
   hipStream_t s = (hipStream_t)stream;
   const long long ntiles = (n + 31) / 32;
-  constexpr int kW = kThreads / 64;
-  const unsigned grid = (unsigned)(ntiles < kW * 256 ? (ntiles + kW - 1) / kW : 256);  // one persistent workgroup per CU
+  const unsigned grid = persistent_grid(ntiles, kThreads / 64);
   hipLaunchKernelGGL(policy_gi_kernel, dim3(grid), dim3(kThreads), 0, s, obs, (long long)n, (int)n_s, W11, b11, W12, b12, W13, b13,
                      W2, b2, Wa, ba, Wc, bc, (int)n_a, seed, (const uint64_t *)counter, actions, logp, value);
   if (actions) hipLaunchKernelGGL(counter_bump_kernel, dim3(1), dim3(1), 0, s, counter);

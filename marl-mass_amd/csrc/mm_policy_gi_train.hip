@@ -1,19 +1,14 @@
 // mm_policy_gi_train.hip -- loss and parameter gradient of MAPPO_GI's shared actor-critic (include/mm_policy_gi_train.h).
 //
-// The forward is policy_gi_kernel's (mm_policy_gi.hip: every layer transposed, H_out^T [feature x sample] = W . H_in^T, one wave
-// per 32 samples, v_mfma_f32_32x32x2_f32, an accumulator tile -- sample on the lane, lane (j, h) holding feature
-// row(r, h) = (r & 3) + 8 (r >> 2) + 4 h in register r -- is directly the B operand of the next layer).  That kernel is not
-// touched; its forward is restated here.
+// The forward is policy_gi_kernel's (mm_policy_gi.hip), in the layout and from the pieces of mm_policy_mfma.h; the split gather
+// of layer 1 is restated here.
 //
 //   prep      W2^T in MFMA A-fragment order into the scratch (80 KB), and B = the number of valid samples.
 //   kernel A  per sample: forward, heads, log-softmax, ratio, the loss terms, dlogit / dvalue (VALU tail);
 //             dz2 = (Wa^T dlogit + Wc^T dvalue) . [h2 > 0] on the VALU (<= 9 rows, 64 features per lane);
 //             dz1 = (W2^T dz2) . [h1 > 0] as a second 160 x 128 MFMA contraction (5 tiles x 64 k-steps; dz2 in accumulator
-//             form is its B operand as h1 is the forward's).  The forward's W2 fragments fill 80 KB of LDS and a second
-//             80 KB for W2^T does not fit beside them; reading the transposed fragments out of the one staged copy puts
-//             the 64 lanes of a read on 8 banks (the lane's output row i only moves the address by (i & 3) floats and whole
-//             multiples of 128), so the A operand of the second contraction comes from global memory instead: 80 float4
-//             loads per lane and tile from the 80 KB fragment array `prep` wrote, L2 resident.
+//             form is its B operand as h1 is the forward's), its A operand 80 float4 loads per lane and tile
+//             from the 80 KB fragment array `prep` wrote (global, L2 resident: dz1_tile in mm_policy_mfma.h says why).
 //             Stores h1, dz1 (160), h2, dz2 (128), dhead (16: dlogit 0..7, dvalue, zeros) and x (32: columns 0..24 of the
 //             observation, zeros) per sample in [sample][feature] order, rows of masked / out-of-range samples as exact
 //             zeros in every gradient row, and one (actor, critic) loss partial per 32 samples in fp64.
@@ -24,93 +19,29 @@
 //             wave 4 the first layer.  Each workgroup contracts one contiguous slice of samples and writes one partial block.
 //   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
-#include "mm_device.h"
+#include "mm_policy_mfma.h"
 #include "../../include/mm_policy_gi_train.h"
 
 namespace mm {
 namespace gi_train {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kHidden = 128;
+using namespace mfma;
 constexpr int kCat = 160;
 constexpr int kL1Steps = 3 + 4 * 5;
 constexpr int kThreadsA = 512;  // 8 waves = 2 per SIMD, as policy_gi_kernel
 constexpr int kThreadsB = 320;  // 5 waves
-constexpr int kMaxSlices = 512;  // workgroups of kernel B = partial blocks (2 per CU)
-constexpr int kUnrollB = 4;      // k-steps of kernel B whose loads are issued together
-static_assert(32 % (2 * kUnrollB) == 0, "kernel B walks a slice of whole 32-sample tiles in blocks of 2 * kUnrollB rows");
-constexpr int kDh = 16, kXs = 32;
 
-// scratch layout, in floats
-constexpr long long kHdr = 64;                         // [0] (int) B
-constexpr long long kFrag = 5 * 4 * 4 * 64 * 4;        // W2^T fragments: [out tile 5][k chunk 4][group 4][lane 64] float4
-// partial block of one kernel-B workgroup, in floats
-constexpr int kPW2 = 0;                      // [128][160]
-constexpr int kPHd = kPW2 + kHidden * kCat;  // [16][128]: rows 0..7 dWa, row 8 dWc
-constexpr int kPW1 = kPHd + 16 * kHidden;    // [160][32]: dz1^T x, all columns
-constexpr int kPb2 = kPW1 + kCat * 32;       // [128]
-constexpr int kPbh = kPb2 + kHidden;         // [16]
-constexpr int kPb1 = kPbh + 16;              // [160]
-constexpr int kPartial = kPb1 + kCat;        // 27 952
+constexpr long long kFrag = 5 * 4 * 4 * 64 * 4;  // W2^T fragments, in floats: [out tile 5][k chunk 4][group 4][lane 64] float4
+typedef PartialBlock<5> Part;                    // the partial block of one kernel-B workgroup: 27 952 floats
 
-struct Layout {
-  long long n_pad, ntiles;
-  long long frag, h1, dz1, h2, dz2, dh, xs, lossp, part, total;  // offsets in floats
-  int slices;
-  long long slice_rows;
-};
-
-static Layout layout(long long n) {
-  Layout L;
-  L.ntiles = (n + 31) / 32;
-  L.n_pad = L.ntiles * 32;
-  L.frag = kHdr;
-  L.h1 = L.frag + kFrag;
-  L.dz1 = L.h1 + L.n_pad * kCat;
-  L.h2 = L.dz1 + L.n_pad * kCat;
-  L.dz2 = L.h2 + L.n_pad * kHidden;
-  L.dh = L.dz2 + L.n_pad * kHidden;
-  L.xs = L.dh + L.n_pad * kDh;
-  L.lossp = L.xs + L.n_pad * kXs;  // double[ntiles][2]
-  L.part = L.lossp + 4 * L.ntiles;
-  // slices of whole 32-sample tiles; at least 2 tiles per slice
-  long long tiles_per = (L.ntiles + kMaxSlices - 1) / kMaxSlices;
-  if (tiles_per < 2) tiles_per = 2;
-  L.slices = (int)((L.ntiles + tiles_per - 1) / tiles_per);
-  if (L.slices < 1) L.slices = 1;
-  L.slice_rows = tiles_per * 32;
-  L.total = L.part + (long long)L.slices * kPartial;
-  return L;
-}
-
-MM_DEV int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-MM_DEV void l1_step(int q, int &m, int &s) {
-  if (q < 3) { m = 0; s = q; }
-  else { m = 1 + (q - 3) / 5; s = (q - 3) % 5; }
-}
+static Layout layout(long long n) { return scratch_layout(n, kFrag, kCat, 2, Part::kSize); }
 
 // ---- prep: W2^T fragments + the count of valid samples (integer atomics: order-independent)
 __global__ __launch_bounds__(256) void gi_train_prep_kernel(const float *__restrict__ W2, float4 *__restrict__ frag,
                                                             const uint8_t *__restrict__ valid, long long n, int *__restrict__ count) {
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < 5 * 4 * 4 * 64) {
-    const int l = t & 63, g = (t >> 6) & 3, m = (t >> 8) & 3, mt = t >> 10;
-    const int i = l & 31, h = l >> 5;
-    float w[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) w[u] = W2[(32 * m + frag_row(4 * g + u, h)) * kCat + 32 * mt + i];
-    frag[t] = make_float4(w[0], w[1], w[2], w[3]);
-  }
-  if (valid) {
-    int c = 0;
-    for (long long k = t; k < n; k += (long long)gridDim.x * 256) c += valid[k] != 0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
-  } else if (t == 0) {
-    *count = (int)n;
-  }
+  if (t < 5 * 4 * 4 * 64) frag[t] = w2t_fragment(W2, kCat, t);
+  count_valid(valid, n, t, count);
 }
 
 // ---- kernel A
@@ -138,16 +69,7 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
     else v = w.W13[(32 * (m - 3) + (l & 31)) * 10 + k];
     sW1[q][l] = v;
   }
-  for (int t = tid; t < 4 * 20 * 64; t += kThreadsA) {
-    const int l = t & 63, q = (t >> 6) % 20, m = t / (20 * 64);
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int s = 4 * q + u;
-      v[u] = w.W2[(32 * m + (l & 31)) * kCat + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
-    }
-    sW2[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
-  }
+  stage_w2<20, kThreadsA>(sW2, w.W2, kCat);
   for (int t = tid; t < 9 * kHidden; t += kThreadsA) {
     const int o = t / kHidden, c = t % kHidden;
     sWh[o][c] = o == 8 ? w.Wc[c] : (o < n_a ? w.Wa[o * kHidden + c] : 0.0f);
@@ -161,16 +83,13 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
   const int nb = *count;
   const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
   const bool ref_form = adv_sums != nullptr;
-  // reference form: S+ and S- are large and nearly cancel while every sample inside the clip band is weighted by their SUM, so
-  // the three possible weights are formed once in fp64 (the sum before the rounding, not after)
   const double sp_d = ref_form ? (double)adv_sums[0] : 0.0, sn_d = ref_form ? (double)adv_sums[1] : 0.0;
-  const double inv_b_d = nb > 0 ? 1.0 / (double)nb : 0.0;
-  const float ref_wp = (float)(sp_d * inv_b_d), ref_wn = (float)(sn_d * inv_b_d), ref_wb = (float)((sp_d + sn_d) * inv_b_d);
+  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
   const float lo = 1.0f - clip_param, hi = 1.0f + clip_param;
   const long long ntiles = (n + 31) / 32;
   constexpr int kWaves = kThreadsA / 64;
   for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
-    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (policy_gi_kernel's note)
+    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
     const long long ag = tile * 32 + j;
     bool live = ag < n;
     if (live && valid) live = valid[ag] != 0;
@@ -216,46 +135,22 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
         for (int s = 0; s < 5; s++)
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW1[q0 + s][lane], m <= 2 ? x2[s] : x3[s], acc, 0, 0, 0);
       }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h1[m][r] = fmaxf(acc[r], 0.0f);
-      float4 *dst = reinterpret_cast<float4 *>(s_h1 + ag * kCat + 32 * m + 4 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h1[m][4 * g], h1[m][4 * g + 1], h1[m][4 * g + 2], h1[m][4 * g + 3]);
+      h1[m] = relu(acc);
+      store_tile(s_h1 + ag * kCat + 32 * m + 4 * h, h1[m]);
     }
 #pragma unroll
     for (int m = 0; m < 4; m++) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[r] = sB2[32 * m + frag_row(r, h)];
-#pragma unroll
-      for (int c = 0; c < 5; c++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const float4 a = sW2[m][4 * c + q][lane];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[c][4 * q + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[c][4 * q + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[c][4 * q + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[c][4 * q + 3], acc, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h2[m][r] = fmaxf(acc[r], 0.0f);
-      float4 *dst = reinterpret_cast<float4 *>(s_h2 + ag * kHidden + 32 * m + 4 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
+      h2[m] = relu(fc2_tile<5>(sW2[m], h1, lane, acc));
+      store_tile(s_h2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
     }
     // ---- heads
     float logit[8];
 #pragma unroll
     for (int o = 0; o < 8; o++) {
-      float p = 0.0f;
-      if (o < n_a) {
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-#pragma unroll
-          for (int r = 0; r < 16; r++) p = fmaf(h2[m][r], sWh[o][32 * m + frag_row(r, h)], p);
-      }
-      p = p + __shfl_xor(p, 32, 64);
+      const float p = head_dot(h2, sWh[o], h, o < n_a);
       logit[o] = o < n_a ? p + sBh[o] : -INFINITY;
     }
     float v = 0.0f;
@@ -264,51 +159,33 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
 #pragma unroll
       for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[8][32 * m + frag_row(r, h)], v);
     v = v + __shfl_xor(v, 32, 64) + sBh[8];
-    float mx = logit[0];
-#pragma unroll
-    for (int o = 1; o < 8; o++) mx = fmaxf(mx, logit[o]);
+    const float mx = max8(logit);
     float se = 0.0f;
 #pragma unroll
-    for (int o = 0; o < 8; o++) se += (o < n_a) ? expf(logit[o] - mx) : 0.0f;
+    for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
     const float lse = mx + logf(se);
     // ---- the objective's per-sample terms (both lane halves compute the same numbers)
     int act = live ? actions[ag * act_stride] : 0;
     act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
     const float ret = live ? returns[ag * ret_stride] : 0.0f;
     const float olp = live ? old_logp[ag] : 0.0f;
-    float lp_a = 0.0f;
-#pragma unroll
-    for (int o = 0; o < 8; o++) lp_a = (o == act) ? logit[o] - lse : lp_a;
+    const float lp_a = logp_taken(logit, lse, act);
     const float r = expf(lp_a - olp);
     const float adv = ret - v;
     const float c = fminf(fmaxf(r, lo), hi);
-    // actor loss = -(1 / B^2) sum_j [S+ min(r, c) + S- max(r, c)] (reference form) or -(1 / B) sum_j [A+ min + A- max]
     double t_actor;
-    float wsel;  // the weight that reaches d / dr: the positive one up to 1 + clip, the negative one from 1 - clip
-    if (ref_form) {
-      t_actor = sp_d * (double)fminf(r, c) + sn_d * (double)fmaxf(r, c);
-      wsel = r > hi ? ref_wn : (r < lo ? ref_wp : ref_wb);
-    } else {
-      const float wp = fmaxf(adv, 0.0f), wn = fminf(adv, 0.0f);  // one of them is zero
-      t_actor = (double)wp * (double)fminf(r, c) + (double)wn * (double)fmaxf(r, c);
-      wsel = (r <= hi ? wp : 0.0f) + (r >= lo ? wn : 0.0f);
-    }
+    float wsel;
+    if (ref_form) ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_actor, wsel);
+    else ppo_clip_flat(adv, lo, hi, r, c, t_actor, wsel);
     const float dldr = -inv_b * wsel;
     const float d = v - ret;
     float t_critic, dv;
-    if (huber) {
-      const float ad = fabsf(d);
-      t_critic = ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
-      dv = ad < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
-    } else {
-      t_critic = d * d;
-      dv = 2.0f * d;
-    }
+    critic_term(d, huber, t_critic, dv);
     dv = live ? dv * inv_b : 0.0f;
     float dlogit[8];
     const float g_lp = live ? dldr * r : 0.0f;  // d loss / d logp_taken
 #pragma unroll
-    for (int o = 0; o < 8; o++) dlogit[o] = (o < n_a) ? g_lp * ((o == act ? 1.0f : 0.0f) - expf(logit[o] - lse)) : 0.0f;
+    for (int o = 0; o < 8; o++) dlogit[o] = (o < n_a) ? mfma::dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
     {
       float4 *dst = reinterpret_cast<float4 *>(s_dh + ag * kDh + 8 * h);
       if (h == 0) {
@@ -360,29 +237,13 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
         h2[m][4 * g + 2] = h2[m][4 * g + 2] > 0.0f ? s2 : 0.0f;
         h2[m][4 * g + 3] = h2[m][4 * g + 3] > 0.0f ? s3 : 0.0f;
       }
-      float4 *dst = reinterpret_cast<float4 *>(s_dz2 + ag * kHidden + 32 * m + 4 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
+      store_tile(s_dz2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
     }
     // ---- dz1 = (W2^T dz2) . [h1 > 0]: 5 output tiles x 64 k-steps, A fragments from global memory
-    unsigned vlane = (unsigned)lane;
-    asm volatile("" : "+v"(vlane));  // opaque per tile: the 80 fragment addresses are formed where they are used, not hoisted
+    const unsigned vlane = opaque_lane(lane);
 #pragma unroll
     for (int mt = 0; mt < 5; mt++) {
-      f32x16 acc;
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) acc[rr] = 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; m++) {
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-          const float4 a = (frag + ((mt * 4 + m) * 4 + g) * 64)[vlane];  // uniform base + one per-lane offset
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h2[m][4 * g + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h2[m][4 * g + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h2[m][4 * g + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h2[m][4 * g + 3], acc, 0, 0, 0);
-        }
-      }
+      const f32x16 acc = dz1_tile(frag, mt, vlane, h2);
       // the ReLU mask of layer 1 is read back from this lane's own h1 stores (L2 / L1 hot) instead of holding h1's 80
       // registers across the heads and the second contraction
       const float4 *msk = reinterpret_cast<const float4 *>(s_h1 + ag * kCat + 32 * mt + 4 * h);
@@ -401,91 +262,13 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
 __global__ __launch_bounds__(kThreadsB) void policy_gi_train_wgrad_kernel(
     const float *__restrict__ s_h1, const float *__restrict__ s_dz1, const float *__restrict__ s_h2, const float *__restrict__ s_dz2,
     const float *__restrict__ s_dh, const float *__restrict__ s_xs, long long n_pad, long long slice_rows, float *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 31, kh = lane >> 5;
-  const long long row0 = (long long)blockIdx.x * slice_rows;
-  long long row1 = row0 + slice_rows;
-  if (row1 > n_pad) row1 = n_pad;
-  float *out = part + (long long)blockIdx.x * kPartial;
-  if (wave < 4) {
-    const int mf = wave;
-    f32x16 acc[5], acch;
-#pragma unroll
-    for (int c = 0; c < 5; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acch[r] = 0.0f;
-    double bs2 = 0.0, bsh = 0.0;  // bias sums in fp64: one add per k-step, no rounding of a 10^3-term running sum
-    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)  // (a slice is a whole number of 32-sample tiles)
-#pragma unroll
-    for (int u = 0; u < kUnrollB; u++) {
-      const long long row = rb + 2 * u;
-      const float a2 = s_dz2[row * kHidden + 32 * mf + i];
-      const float ah = i < kDh ? s_dh[row * kDh + i] : 0.0f;
-      const float bh = s_h2[row * kHidden + 32 * mf + i];
-      float b1[5];
-#pragma unroll
-      for (int c = 0; c < 5; c++) b1[c] = s_h1[row * kCat + 32 * c + i];
-#pragma unroll
-      for (int c = 0; c < 5; c++) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b1[c], acc[c], 0, 0, 0);
-      acch = __builtin_amdgcn_mfma_f32_32x32x2f32(ah, bh, acch, 0, 0, 0);
-      bs2 += (double)a2;
-      bsh += (double)ah;
-    }
-    // accumulator register r of lane (j = i, h = kh): output row frag_row(r, kh), column j
-#pragma unroll
-    for (int c = 0; c < 5; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) out[kPW2 + (32 * mf + frag_row(r, kh)) * kCat + 32 * c + i] = acc[c][r];
-#pragma unroll
-    for (int r = 0; r < 8; r++) out[kPHd + frag_row(r, kh) * kHidden + 32 * mf + i] = acch[r];  // rows 0..15
-    bs2 += __shfl_xor(bs2, 32, 64);
-    bsh += __shfl_xor(bsh, 32, 64);
-    if (kh == 0) {
-      out[kPb2 + 32 * mf + i] = (float)bs2;
-      if (mf == 0 && i < kDh) out[kPbh + i] = (float)bsh;
-    }
-  } else {
-    f32x16 acc[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
-    double bs1[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)
-#pragma unroll
-    for (int u = 0; u < kUnrollB; u++) {
-      const long long row = rb + 2 * u;
-      const float bx = s_xs[row * kXs + i];
-      float a1[5];
-#pragma unroll
-      for (int c = 0; c < 5; c++) a1[c] = s_dz1[row * kCat + 32 * c + i];
-#pragma unroll
-      for (int c = 0; c < 5; c++) {
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], bx, acc[c], 0, 0, 0);
-        bs1[c] += (double)a1[c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) out[kPW1 + (32 * c + frag_row(r, kh)) * 32 + i] = acc[c][r];
-      const double s = bs1[c] + __shfl_xor(bs1[c], 32, 64);
-      if (kh == 0) out[kPb1 + 32 * c + i] = (float)s;
-    }
-  }
+  wgrad_slice<5, false>(s_h1, s_dz1, s_h2, s_dz2, s_dh, s_xs, n_pad, slice_rows, part);
 }
 
 // ---- kernel C: gradient element t = sum over the partial blocks in workgroup order; the last workgroup folds the losses
 constexpr int kNFixed = 32 * 5 + 32 + 64 * 10 + 64 + 64 * 10 + 64 + kHidden * kCat + kHidden;  // everything before Wa
 
-MM_DEV float fold(const float *__restrict__ part, int slices, int off) {
-  double s = 0.0;
-#pragma unroll 8
-  for (int g = 0; g < slices; g++) s += (double)part[(long long)g * kPartial + off];
-  return (float)s;
-}
+MM_DEV float fold(const float *__restrict__ part, int slices, int off) { return mfma::fold<Part::kSize>(part, slices, off); }
 
 __global__ __launch_bounds__(256) void policy_gi_train_fold_kernel(const float *__restrict__ part, int slices, int n_a, MMGiParams gr,
                                                                    const double *__restrict__ lossp, long long ntiles,
@@ -493,26 +276,11 @@ __global__ __launch_bounds__(256) void policy_gi_train_fold_kernel(const float *
                                                                    float *__restrict__ loss) {
   const int nelem = kNFixed + n_a * kHidden + n_a + kHidden + 1;
   if (blockIdx.x == gridDim.x - 1) {
-    __shared__ double sa[256], sc[256];
-    double pa = 0.0, pc = 0.0;
-    for (long long t = threadIdx.x; t < ntiles; t += 256) {
-      pa += lossp[2 * t];
-      pc += lossp[2 * t + 1];
-    }
-    sa[threadIdx.x] = pa;
-    sc[threadIdx.x] = pc;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-      if ((int)threadIdx.x < o) {
-        sa[threadIdx.x] += sa[threadIdx.x + o];
-        sc[threadIdx.x] += sc[threadIdx.x + o];
-      }
-      __syncthreads();
-    }
+    __shared__ double ssum[2][256];  // actor, critic
+    loss_tree<2>(lossp, ntiles, ssum);
     if (threadIdx.x == 0) {
-      const int nb = *count;
-      const double inv = nb > 0 ? 1.0 / (double)nb : 0.0;
-      const float a = (float)(-sa[0] * inv * (ref_form ? inv : 1.0)), c = (float)(sc[0] * inv);
+      const double inv = inv_count(count);
+      const float a = (float)(-ssum[0][0] * inv * (ref_form ? inv : 1.0)), c = (float)(ssum[1][0] * inv);
       loss[0] = a;
       loss[1] = c;
       loss[2] = a + c;
@@ -521,28 +289,28 @@ __global__ __launch_bounds__(256) void policy_gi_train_fold_kernel(const float *
   }
   int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= nelem) return;
-  if (t < 160) { const int o = t / 5, k = t % 5; gr.W11[t] = fold(part, slices, kPW1 + o * 32 + 5 * k); return; }
+  if (t < 160) { const int o = t / 5, k = t % 5; gr.W11[t] = fold(part, slices, Part::kW1 + o * 32 + 5 * k); return; }
   t -= 160;
-  if (t < 32) { gr.b11[t] = fold(part, slices, kPb1 + t); return; }
+  if (t < 32) { gr.b11[t] = fold(part, slices, Part::kb1 + t); return; }
   t -= 32;
-  if (t < 640) { const int o = t / 10, k = t % 10; gr.W12[t] = fold(part, slices, kPW1 + (32 + o) * 32 + 5 * (k >> 1) + 1 + (k & 1)); return; }
+  if (t < 640) { const int o = t / 10, k = t % 10; gr.W12[t] = fold(part, slices, Part::kW1 + (32 + o) * 32 + 5 * (k >> 1) + 1 + (k & 1)); return; }
   t -= 640;
-  if (t < 64) { gr.b12[t] = fold(part, slices, kPb1 + 32 + t); return; }
+  if (t < 64) { gr.b12[t] = fold(part, slices, Part::kb1 + 32 + t); return; }
   t -= 64;
-  if (t < 640) { const int o = t / 10, k = t % 10; gr.W13[t] = fold(part, slices, kPW1 + (96 + o) * 32 + 5 * (k >> 1) + 3 + (k & 1)); return; }
+  if (t < 640) { const int o = t / 10, k = t % 10; gr.W13[t] = fold(part, slices, Part::kW1 + (96 + o) * 32 + 5 * (k >> 1) + 3 + (k & 1)); return; }
   t -= 640;
-  if (t < 64) { gr.b13[t] = fold(part, slices, kPb1 + 96 + t); return; }
+  if (t < 64) { gr.b13[t] = fold(part, slices, Part::kb1 + 96 + t); return; }
   t -= 64;
-  if (t < kHidden * kCat) { gr.W2[t] = fold(part, slices, kPW2 + t); return; }
+  if (t < kHidden * kCat) { gr.W2[t] = fold(part, slices, Part::kW2 + t); return; }
   t -= kHidden * kCat;
-  if (t < kHidden) { gr.b2[t] = fold(part, slices, kPb2 + t); return; }
+  if (t < kHidden) { gr.b2[t] = fold(part, slices, Part::kb2 + t); return; }
   t -= kHidden;
-  if (t < n_a * kHidden) { gr.Wa[t] = fold(part, slices, kPHd + t); return; }
+  if (t < n_a * kHidden) { gr.Wa[t] = fold(part, slices, Part::kHd + t); return; }
   t -= n_a * kHidden;
-  if (t < n_a) { gr.ba[t] = fold(part, slices, kPbh + t); return; }
+  if (t < n_a) { gr.ba[t] = fold(part, slices, Part::kbh + t); return; }
   t -= n_a;
-  if (t < kHidden) { gr.Wc[t] = fold(part, slices, kPHd + 8 * kHidden + t); return; }
-  gr.bc[0] = fold(part, slices, kPbh + 8);
+  if (t < kHidden) { gr.Wc[t] = fold(part, slices, Part::kHd + 8 * kHidden + t); return; }
+  gr.bc[0] = fold(part, slices, Part::kbh + 8);
 }
 
 }  // namespace gi_train
@@ -586,8 +354,7 @@ extern "C" int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int6
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
   hipLaunchKernelGGL(gi_train_prep_kernel, dim3(5 * 4 * 4 * 64 / 256), dim3(256), 0, s, W.W2, (float4 *)(sc + L.frag), valid,
                      (long long)n, count);
-  constexpr int kW = kThreadsA / 64;
-  const unsigned gridA = (unsigned)(L.ntiles < kW * 256 ? (L.ntiles + kW - 1) / kW : 256);  // one persistent workgroup per CU
+  const unsigned gridA = persistent_grid(L.ntiles, kThreadsA / 64);
   hipLaunchKernelGGL(policy_gi_train_sample_kernel, dim3(gridA), dim3(kThreadsA), 0, s, obs, (long long)obs_stride, (long long)n,
                      actions, (long long)act_stride, returns, (long long)ret_stride, old_logp, valid, W, (int)n_a, clip_param,
                      (int)(critic_loss == MM_GI_CRITIC_HUBER), adv_sums, (const int *)count, (const float4 *)(sc + L.frag),

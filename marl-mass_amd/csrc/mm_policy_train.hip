@@ -1,9 +1,7 @@
 // mm_policy_train.hip -- loss and parameter gradient of MAPPO's separate actor and critic (include/mm_policy_train.h), and the
 // forward-only mm_policy_eval.
 //
-// The shape is mm_policy_gi_train.hip's: every layer transposed, H_out^T [feature x sample] = W . H_in^T, one wave per 32
-// samples, v_mfma_f32_32x32x2_f32; an accumulator tile -- sample on the lane, lane (j, h) holding feature
-// row(r, h) = (r & 3) + 8 (r >> 2) + 4 h in register r -- is directly the B operand of the next layer.  Both networks are
+// The shape is mm_policy_gi_train.hip's, in the layout and from the pieces of mm_policy_mfma.h.  Both networks are
 // "n_s -> 128 -> 128 -> head", so ONE kernel template serves them (kCritic) and, without the backward, mm_policy_eval (!kTrain).
 //
 //   prep      W2[:, :128]^T of each given network in MFMA A-fragment order into the scratch (64 KB each), and B = the number
@@ -12,7 +10,7 @@
 //             the VALU (<= 8 rows), then the loss terms and dlogit / dvalue; dz2 = W3^T dhead . [h2 > 0] on the VALU;
 //             dz1 = (W2[:, :128]^T dz2) . [h1 > 0] as a second 128 x 128 MFMA contraction whose A operand comes from the
 //             fragment array `prep` wrote (global, L2 resident: reading transposed fragments out of the one staged LDS copy
-//             would put the 64 lanes of a read on 8 banks -- the trap recorded in mm_policy_gi_train.hip).
+//             would put the 64 lanes of a read on 8 banks -- the trap recorded at dz1_tile in mm_policy_mfma.h).
 //             The critic's fc2 has K = 128 + n_a with a one-hot block: in the forward that block is a column gather,
 //             z2 = b2 + W2[:, 128 + a_j] + W2[:, :128] h1, added where the accumulator is initialised, out of an [8][128]
 //             LDS table (rows padded to 136 floats: lanes with different actions land on different banks); in the backward
@@ -30,67 +28,22 @@
 //   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
 // The actor's three kernels run first, then the critic's over the same scratch (stream order).
-#include "mm_device.h"
+#include "mm_policy_mfma.h"
 #include "../../include/mm_policy_train.h"
 
 namespace mm {
 namespace pt {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kHidden = 128;
-constexpr int kCat = 160;        // row pitch of the dW2 partial: 128 + the one-hot tile
-constexpr int kOhPitch = 136;    // row pitch of the one-hot column table in LDS
-constexpr int kThreadsA = 512;   // 8 waves = 2 per SIMD
-constexpr int kThreadsB = 320;   // 5 waves
-constexpr int kMaxSlices = 512;  // workgroups of kernel B = partial blocks (2 per CU)
-constexpr int kUnrollB = 4;      // k-steps of kernel B whose loads are issued together
-static_assert(32 % (2 * kUnrollB) == 0, "kernel B walks a slice of whole 32-sample tiles in blocks of 2 * kUnrollB rows");
-constexpr int kDh = 16, kXs = 32;
-constexpr int kActCol = 15;  // column of the head row that carries the critic's action
+using namespace mfma;
+constexpr int kCat = kW2Pitch;  // row pitch of the dW2 partial: 128 + the one-hot tile
+constexpr int kOhPitch = 136;   // row pitch of the one-hot column table in LDS
+constexpr int kThreadsA = 512;  // 8 waves = 2 per SIMD
+constexpr int kThreadsB = 320;  // 5 waves
 
-// scratch layout, in floats
-constexpr long long kHdr = 64;                   // [0] (int) B
-constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network: [out tile 4][k chunk 4][group 4][lane 64] float4
-// partial block of one kernel-B workgroup, in floats
-constexpr int kPW2 = 0;                      // [128][160]
-constexpr int kPHd = kPW2 + kHidden * kCat;  // [16][128]
-constexpr int kPW1 = kPHd + 16 * kHidden;    // [128][32]
-constexpr int kPb2 = kPW1 + kHidden * 32;    // [128]
-constexpr int kPbh = kPb2 + kHidden;         // [16]
-constexpr int kPb1 = kPbh + 16;              // [128]
-constexpr int kPartial = kPb1 + kHidden;     // 26 896
+constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network, in floats: [out tile 4][k chunk 4][group 4][lane 64] float4
+typedef PartialBlock<4> Part;                    // the partial block of one kernel-B workgroup: 26 896 floats
 
-struct Layout {
-  long long n_pad, ntiles;
-  long long frag, h1, dz1, h2, dz2, dh, xs, lossp, part, total;  // offsets in floats
-  int slices;
-  long long slice_rows;
-};
-
-static Layout layout(long long n) {
-  Layout L;
-  L.ntiles = (n + 31) / 32;
-  L.n_pad = L.ntiles * 32;
-  L.frag = kHdr;  // actor's, then the critic's
-  L.h1 = L.frag + 2 * kFrag;
-  L.dz1 = L.h1 + L.n_pad * kHidden;
-  L.h2 = L.dz1 + L.n_pad * kHidden;
-  L.dz2 = L.h2 + L.n_pad * kHidden;
-  L.dh = L.dz2 + L.n_pad * kHidden;
-  L.xs = L.dh + L.n_pad * kDh;
-  L.lossp = L.xs + L.n_pad * kXs;  // double[ntiles]
-  L.part = L.lossp + 2 * L.ntiles;
-  // slices of whole 32-sample tiles; at least 2 tiles per slice
-  long long tiles_per = (L.ntiles + kMaxSlices - 1) / kMaxSlices;
-  if (tiles_per < 2) tiles_per = 2;
-  L.slices = (int)((L.ntiles + tiles_per - 1) / tiles_per);
-  if (L.slices < 1) L.slices = 1;
-  L.slice_rows = tiles_per * 32;
-  L.total = L.part + (long long)L.slices * kPartial;
-  return L;
-}
-
-MM_DEV int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+static Layout layout(long long n) { return scratch_layout(n, 2 * kFrag, kHidden, 1, Part::kSize); }  // (the actor's fragments, then the critic's)
 
 // ---- prep: W2[:, :128]^T fragments of the given networks + the count of valid samples (integer atomics: order-independent)
 __global__ __launch_bounds__(256) void policy_train_prep_kernel(const float *__restrict__ W2a, const float *__restrict__ W2c, int k2c,
@@ -101,25 +54,10 @@ __global__ __launch_bounds__(256) void policy_train_prep_kernel(const float *__r
     const bool crit = t >= 4096;
     const float *W2 = crit ? W2c : W2a;
     const int k2 = crit ? k2c : kHidden;
-    if (W2) {
-      const int l = t & 63, g = (t >> 6) & 3, m = (t >> 8) & 3, mt = (t >> 10) & 3;
-      const int i = l & 31, h = l >> 5;
-      float w[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) w[u] = W2[(32 * m + frag_row(4 * g + u, h)) * k2 + 32 * mt + i];
-      frag[t] = make_float4(w[0], w[1], w[2], w[3]);
-    }
+    if (W2) frag[t] = w2t_fragment(W2, k2, t & 4095);
   }
   if (!count) return;
-  if (valid) {
-    int c = 0;
-    for (long long k = t; k < n; k += (long long)gridDim.x * 256) c += valid[k] != 0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
-  } else if (t == 0) {
-    *count = (int)n;
-  }
+  count_valid(valid, n, t, count);
 }
 
 struct SampleArgs {
@@ -193,17 +131,14 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
   if (kTrain) nb = *p.count;
   const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
   const bool ref_form = p.adv_sums != nullptr;
-  // reference form: S+ and S- are large and nearly cancel while every sample inside the clip band is weighted by their SUM, so
-  // the three possible weights are formed once in fp64 (the sum before the rounding, not after)
   const double sp_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[0] : 0.0;
   const double sn_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[1] : 0.0;
-  const double inv_b_d = nb > 0 ? 1.0 / (double)nb : 0.0;
-  const float ref_wp = (float)(sp_d * inv_b_d), ref_wn = (float)(sn_d * inv_b_d), ref_wb = (float)((sp_d + sn_d) * inv_b_d);
+  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
   const float lo = 1.0f - p.clip_param, hi = 1.0f + p.clip_param;
   const long long n = p.n, ntiles = (n + 31) / 32;
   constexpr int kWaves = kThreadsA / 64;
   for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
-    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (policy_gi_kernel's note)
+    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
     const long long ag = tile * 32 + j;
     bool live = ag < n;
     if (live && p.valid) live = p.valid[ag] != 0;
@@ -239,20 +174,9 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
         acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
       }
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const float4 a = sW1[m][q][lane];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, x[4 * q + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, x[4 * q + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, x[4 * q + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, x[4 * q + 3], acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h1[m][r] = fmaxf(acc[r], 0.0f);
-      if (kTrain) {
-        float4 *dst = reinterpret_cast<float4 *>(p.s_h1 + ag * kHidden + 32 * m + 4 * h);
-#pragma unroll
-        for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h1[m][4 * g], h1[m][4 * g + 1], h1[m][4 * g + 2], h1[m][4 * g + 3]);
-      }
+      for (int q = 0; q < 4; q++) acc = mfma4(sW1[m][q][lane], x[4 * q + 0], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3], acc);
+      h1[m] = relu(acc);
+      if (kTrain) store_tile(p.s_h1 + ag * kHidden + 32 * m + 4 * h, h1[m]);
     }
 #pragma unroll
     for (int m = 0; m < 4; m++) {
@@ -266,24 +190,8 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
         }
         acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
       }
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const float4 a = sW2[m][4 * c + q][lane];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[c][4 * q + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[c][4 * q + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[c][4 * q + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[c][4 * q + 3], acc, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; r++) h2[m][r] = fmaxf(acc[r], 0.0f);
-      if (kTrain) {
-        float4 *dst = reinterpret_cast<float4 *>(p.s_h2 + ag * kHidden + 32 * m + 4 * h);
-#pragma unroll
-        for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
-      }
+      h2[m] = relu(fc2_tile<4>(sW2[m], h1, lane, acc));
+      if (kTrain) store_tile(p.s_h2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
     }
     // ---- head, the objective's per-sample terms, dhead (both lane halves compute the same numbers)
     float dhead[8];
@@ -300,14 +208,7 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
       const float ret = live ? p.returns[ag * p.ret_stride] : 0.0f;
       const float d = v - ret;
       float t_critic, dv;
-      if (p.huber) {
-        const float ad = fabsf(d);
-        t_critic = ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
-        dv = ad < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
-      } else {
-        t_critic = d * d;
-        dv = 2.0f * d;
-      }
+      critic_term(d, p.huber, t_critic, dv);
       t_loss = (double)t_critic;
       dhead[0] = live ? dv * inv_b : 0.0f;
 #pragma unroll
@@ -316,26 +217,15 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
       float logit[8];
 #pragma unroll
       for (int o = 0; o < 8; o++) {
-        float s = 0.0f;
-        if (o < n_a) {
-#pragma unroll
-          for (int m = 0; m < 4; m++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) s = fmaf(h2[m][r], sWh[o][32 * m + frag_row(r, h)], s);
-        }
-        s = s + __shfl_xor(s, 32, 64);
+        const float s = head_dot(h2, sWh[o], h, o < n_a);
         logit[o] = o < n_a ? s + sBh[o] : -INFINITY;
       }
-      float mx = logit[0];
-#pragma unroll
-      for (int o = 1; o < 8; o++) mx = fmaxf(mx, logit[o]);
+      const float mx = max8(logit);
       float se = 0.0f;
 #pragma unroll
-      for (int o = 0; o < 8; o++) se += (o < n_a) ? expf(logit[o] - mx) : 0.0f;
+      for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
       const float lse = mx + logf(se);
-      float lp_a = 0.0f;
-#pragma unroll
-      for (int o = 0; o < 8; o++) lp_a = (o == act) ? logit[o] - lse : lp_a;
+      const float lp_a = logp_taken(logit, lse, act);
       if (!kTrain) {
         if (h == 0 && ag < n && p.out0) p.out0[ag] = live ? lp_a : 0.0f;
         continue;
@@ -343,20 +233,12 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
       const float olp = live ? p.old_logp[ag] : 0.0f;
       const float r = expf(lp_a - olp);
       const float c = fminf(fmaxf(r, lo), hi);
-      // actor loss = -(1 / B^2) sum_j [S+ min(r, c) + S- max(r, c)] (reference form) or -(1 / B) sum_j [A+ min + A- max]
-      float wsel;  // the weight that reaches d / dr: the positive one up to 1 + clip, the negative one from 1 - clip
-      if (ref_form) {
-        t_loss = sp_d * (double)fminf(r, c) + sn_d * (double)fmaxf(r, c);
-        wsel = r > hi ? ref_wn : (r < lo ? ref_wp : ref_wb);
-      } else {
-        const float adv = live ? p.advantages[ag] : 0.0f;
-        const float wp = fmaxf(adv, 0.0f), wn = fminf(adv, 0.0f);  // one of them is zero
-        t_loss = (double)wp * (double)fminf(r, c) + (double)wn * (double)fmaxf(r, c);
-        wsel = (r <= hi ? wp : 0.0f) + (r >= lo ? wn : 0.0f);
-      }
+      float wsel;
+      if (ref_form) ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_loss, wsel);
+      else ppo_clip_flat(live ? p.advantages[ag] : 0.0f, lo, hi, r, c, t_loss, wsel);
       const float g_lp = live ? -inv_b * wsel * r : 0.0f;  // d loss / d logp_taken
 #pragma unroll
-      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? g_lp * ((o == act ? 1.0f : 0.0f) - expf(logit[o] - lse)) : 0.0f;
+      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
       if (h == 0 && ag < n) {
         if (p.out0) p.out0[ag] = live ? lp_a : 0.0f;
         if (p.out1) p.out1[ag] = live ? r : 0.0f;
@@ -401,29 +283,13 @@ __global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const Sa
         h2[m][4 * g + 2] = h2[m][4 * g + 2] > 0.0f ? s2 : 0.0f;
         h2[m][4 * g + 3] = h2[m][4 * g + 3] > 0.0f ? s3 : 0.0f;
       }
-      float4 *dst = reinterpret_cast<float4 *>(p.s_dz2 + ag * kHidden + 32 * m + 4 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) dst[2 * g] = make_float4(h2[m][4 * g], h2[m][4 * g + 1], h2[m][4 * g + 2], h2[m][4 * g + 3]);
+      store_tile(p.s_dz2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
     }
     // ---- dz1 = (W2[:, :128]^T dz2) . [h1 > 0]: 4 output tiles x 64 k-steps, A fragments from global memory
-    unsigned vlane = (unsigned)lane;
-    asm volatile("" : "+v"(vlane));  // opaque per tile: the 64 fragment addresses are formed where they are used, not hoisted
+    const unsigned vlane = opaque_lane(lane);
 #pragma unroll
     for (int mt = 0; mt < 4; mt++) {
-      f32x16 acc;
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) acc[rr] = 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; m++) {
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-          const float4 a = (p.frag + ((mt * 4 + m) * 4 + g) * 64)[vlane];  // uniform base + one per-lane offset
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h2[m][4 * g + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h2[m][4 * g + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h2[m][4 * g + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h2[m][4 * g + 3], acc, 0, 0, 0);
-        }
-      }
+      const f32x16 acc = dz1_tile(p.frag, mt, vlane, h2);
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         float4 *dst = reinterpret_cast<float4 *>(p.s_dz1 + ag * kHidden + 32 * mt + 4 * h);
@@ -439,91 +305,11 @@ template <bool kCritic>
 __global__ __launch_bounds__(kThreadsB) void policy_train_wgrad_kernel(
     const float *__restrict__ s_h1, const float *__restrict__ s_dz1, const float *__restrict__ s_h2, const float *__restrict__ s_dz2,
     const float *__restrict__ s_dh, const float *__restrict__ s_xs, long long n_pad, long long slice_rows, float *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 31, kh = lane >> 5;
-  const long long row0 = (long long)blockIdx.x * slice_rows;
-  long long row1 = row0 + slice_rows;
-  if (row1 > n_pad) row1 = n_pad;
-  float *out = part + (long long)blockIdx.x * kPartial;
-  constexpr int kTiles2 = kCritic ? 5 : 4;
-  if (wave < 4) {
-    const int mf = wave;
-    f32x16 acc[kTiles2], acch;
-#pragma unroll
-    for (int c = 0; c < kTiles2; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acch[r] = 0.0f;
-    double bs2 = 0.0, bsh = 0.0;  // bias sums in fp64: one add per k-step, no rounding of a 10^3-term running sum
-    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)  // (a slice is a whole number of 32-sample tiles)
-#pragma unroll
-    for (int u = 0; u < kUnrollB; u++) {
-      const long long row = rb + 2 * u;
-      const float a2 = s_dz2[row * kHidden + 32 * mf + i];
-      const float ah = i < kDh ? s_dh[row * kDh + i] : 0.0f;
-      const float bh = s_h2[row * kHidden + 32 * mf + i];
-      float b1[kTiles2];
-#pragma unroll
-      for (int c = 0; c < 4; c++) b1[c] = s_h1[row * kHidden + 32 * c + i];
-      if (kCritic) b1[kTiles2 - 1] = (float)i == s_dh[row * kDh + kActCol] ? 1.0f : 0.0f;  // one_hot(action) row
-#pragma unroll
-      for (int c = 0; c < kTiles2; c++) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b1[c], acc[c], 0, 0, 0);
-      acch = __builtin_amdgcn_mfma_f32_32x32x2f32(ah, bh, acch, 0, 0, 0);
-      bs2 += (double)a2;
-      bsh += (double)ah;
-    }
-    // accumulator register r of lane (j = i, h = kh): output row frag_row(r, kh), column j
-#pragma unroll
-    for (int c = 0; c < kTiles2; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) out[kPW2 + (32 * mf + frag_row(r, kh)) * kCat + 32 * c + i] = acc[c][r];
-#pragma unroll
-    for (int r = 0; r < 8; r++) out[kPHd + frag_row(r, kh) * kHidden + 32 * mf + i] = acch[r];  // rows 0..15
-    bs2 += __shfl_xor(bs2, 32, 64);
-    bsh += __shfl_xor(bsh, 32, 64);
-    if (kh == 0) {
-      out[kPb2 + 32 * mf + i] = (float)bs2;
-      if (mf == 0 && i < kDh) out[kPbh + i] = (float)bsh;
-    }
-  } else {
-    f32x16 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[c][r] = 0.0f;
-    double bs1[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long long rb = row0 + kh; rb < row1; rb += 2 * kUnrollB)
-#pragma unroll
-    for (int u = 0; u < kUnrollB; u++) {
-      const long long row = rb + 2 * u;
-      const float bx = s_xs[row * kXs + i];
-      float a1[4];
-#pragma unroll
-      for (int c = 0; c < 4; c++) a1[c] = s_dz1[row * kHidden + 32 * c + i];
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], bx, acc[c], 0, 0, 0);
-        bs1[c] += (double)a1[c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) out[kPW1 + (32 * c + frag_row(r, kh)) * 32 + i] = acc[c][r];
-      const double s = bs1[c] + __shfl_xor(bs1[c], 32, 64);
-      if (kh == 0) out[kPb1 + 32 * c + i] = (float)s;
-    }
-  }
+  wgrad_slice<4, kCritic>(s_h1, s_dz1, s_h2, s_dz2, s_dh, s_xs, n_pad, slice_rows, part);
 }
 
 // ---- kernel C: gradient element t = sum over the partial blocks in workgroup order; the last workgroup folds the loss
-MM_DEV float fold(const float *__restrict__ part, int slices, int off) {
-  double s = 0.0;
-#pragma unroll 8
-  for (int g = 0; g < slices; g++) s += (double)part[(long long)g * kPartial + off];
-  return (float)s;
-}
+MM_DEV float fold(const float *__restrict__ part, int slices, int off) { return mfma::fold<Part::kSize>(part, slices, off); }
 
 static int fold_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
 
@@ -532,34 +318,26 @@ __global__ __launch_bounds__(256) void policy_train_fold_kernel(const float *__r
                                                                 MMMlpParams gr, const double *__restrict__ lossp, long long ntiles,
                                                                 const int *__restrict__ count, int loss_mode, float *__restrict__ loss) {
   if (blockIdx.x == gridDim.x - 1) {
-    __shared__ double sa[256];
-    double pa = 0.0;
-    for (long long t = threadIdx.x; t < ntiles; t += 256) pa += lossp[t];
-    sa[threadIdx.x] = pa;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-      if ((int)threadIdx.x < o) sa[threadIdx.x] += sa[threadIdx.x + o];
-      __syncthreads();
-    }
+    __shared__ double ssum[1][256];
+    loss_tree<1>(lossp, ntiles, ssum);
     if (threadIdx.x == 0) {
-      const int nb = *count;
-      const double inv = nb > 0 ? 1.0 / (double)nb : 0.0;
-      *loss = (float)(loss_mode == 0 ? sa[0] * inv : (loss_mode == 1 ? -sa[0] * inv : -sa[0] * inv * inv));
+      const double inv = inv_count(count);
+      *loss = (float)(loss_mode == 0 ? ssum[0][0] * inv : (loss_mode == 1 ? -ssum[0][0] * inv : -ssum[0][0] * inv * inv));
     }
     return;
   }
   int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < kHidden * n_s) { const int o = t / n_s, k = t % n_s; gr.W1[t] = fold(part, slices, kPW1 + o * 32 + k); return; }
+  if (t < kHidden * n_s) { const int o = t / n_s, k = t % n_s; gr.W1[t] = fold(part, slices, Part::kW1 + o * 32 + k); return; }
   t -= kHidden * n_s;
-  if (t < kHidden) { gr.b1[t] = fold(part, slices, kPb1 + t); return; }
+  if (t < kHidden) { gr.b1[t] = fold(part, slices, Part::kb1 + t); return; }
   t -= kHidden;
-  if (t < kHidden * k2) { const int o = t / k2, k = t % k2; gr.W2[t] = fold(part, slices, kPW2 + o * kCat + k); return; }
+  if (t < kHidden * k2) { const int o = t / k2, k = t % k2; gr.W2[t] = fold(part, slices, Part::kW2 + o * kCat + k); return; }
   t -= kHidden * k2;
-  if (t < kHidden) { gr.b2[t] = fold(part, slices, kPb2 + t); return; }
+  if (t < kHidden) { gr.b2[t] = fold(part, slices, Part::kb2 + t); return; }
   t -= kHidden;
-  if (t < n_out * kHidden) { gr.W3[t] = fold(part, slices, kPHd + t); return; }
+  if (t < n_out * kHidden) { gr.W3[t] = fold(part, slices, Part::kHd + t); return; }
   t -= n_out * kHidden;
-  if (t < n_out) gr.b3[t] = fold(part, slices, kPbh + t);
+  if (t < n_out) gr.b3[t] = fold(part, slices, Part::kbh + t);
 }
 
 static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
@@ -568,10 +346,7 @@ static bool shape_ok(int64_t n, int32_t n_s, int32_t hidden, int32_t n_a) {
   return n >= 0 && n <= 0x7FFFFFFF && n_s >= 25 && n_s <= 32 && hidden == kHidden && n_a >= 1 && n_a <= 8;
 }
 
-static unsigned grid_a(long long ntiles) {
-  constexpr int kW = kThreadsA / 64;
-  return (unsigned)(ntiles < kW * 256 ? (ntiles + kW - 1) / kW : 256);  // one persistent workgroup per CU
-}
+static unsigned grid_a(long long ntiles) { return persistent_grid(ntiles, kThreadsA / 64); }
 
 }  // namespace pt
 }  // namespace mm

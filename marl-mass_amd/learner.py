@@ -36,7 +36,57 @@ def _params(net):
     return out
 
 
-class SharedPPOLearner(object):
+def _optimizer_class(optimizer_type):
+    if optimizer_type not in ("adam", "rmsprop"):
+        raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
+    return torch.optim.Adam if optimizer_type == "adam" else torch.optim.RMSprop
+
+
+def _ensure_grad(p):
+    """The library writes the gradients straight into .grad: a contiguous one must exist."""
+    if p.grad is None or not p.grad.is_contiguous():
+        p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+
+def _batch(states, actions, returns, valid):
+    """The preamble of both train(): `DeviceRollout.interact()`'s dict or the three tensors -> states float32 [B, N, S],
+    actions int32 [B, N], returns float32 [B, N], valid uint8 [B, N] or None, and N, S."""
+    if isinstance(states, dict):
+        states, actions, returns = states["states"], states["actions"], states["returns"]
+    N, S = states.shape[-2], states.shape[-1]
+    states = states.reshape(-1, N, S)
+    if states.dtype != torch.float32:
+        states = states.float()
+    actions = actions.reshape(-1, N)
+    if actions.dtype != torch.int32:
+        actions = actions.to(torch.int32)
+    returns = returns.reshape(-1, N)
+    if returns.dtype != torch.float32:
+        returns = returns.float()  # (DeviceRollout's returns are float64: converted once)
+    if valid is not None:
+        valid = valid.reshape(-1, N).to(torch.uint8)
+    return states, actions, returns, valid, N, S
+
+
+class _DeviceLearner(object):
+    """What both learners need around a library call: the current stream and a scratch buffer that only grows.
+    `scratch_bytes` is the library's size query of the subclass's call, n -> bytes."""
+
+    def __init__(self, clib, device, scratch_bytes):
+        self.clib, self.device = clib, device
+        self._scratch, self._scratch_bytes = None, scratch_bytes
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ensure_scratch(self, n):
+        need = self._scratch_bytes(n)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
+        return self._scratch
+
+
+class SharedPPOLearner(_DeviceLearner):
     """`MAPPO_GI(shared_network=True)`'s policy / policy_target / policy_optimizer and its train(); defaults are
     MAPPO_GI.__init__'s (marl/mappo_gi.py:28-57).  `policy` is a rollout.ActorCriticNetwork(state_split=True), hidden 128,
     float32, on the device -- typically the module a DeviceRollout acts with, so the next rollout uses the updated weights."""
@@ -52,33 +102,17 @@ class SharedPPOLearner(object):
             raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
         clib.require_policy_gi()
         clib.require_policy_gi_train()
-        self.policy, self.clib = policy, clib
+        _DeviceLearner.__init__(self, clib, p0.device, clib.policy_gi_train_scratch_bytes)
+        self.policy = policy
         self.policy_target = copy.deepcopy(policy)
-        if optimizer_type == "adam":
-            self.optimizer = torch.optim.Adam(policy.parameters(), lr=lr)
-        elif optimizer_type == "rmsprop":
-            self.optimizer = torch.optim.RMSprop(policy.parameters(), lr=lr)
-        else:
-            raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
+        self.optimizer = _optimizer_class(optimizer_type)(policy.parameters(), lr=lr)
         self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
         self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
         self.n_a = policy.actor_linear.weight.shape[0]
-        self.device = p0.device
-        for p in policy.parameters():  # the library writes the gradients straight into .grad
-            if p.grad is None or not p.grad.is_contiguous():
-                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        self._scratch = None
+        for p in policy.parameters():
+            _ensure_grad(p)
 
     # -- plumbing ----------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _ensure_scratch(self, n):
-        need = self.clib.policy_gi_train_scratch_bytes(n)
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
-        return self._scratch
-
     def _act(self, net, obs, logp=None, value=None):
         """Value-only mm_policy_gi_act of `net` on contiguous obs [n, S] (nothing sampled)."""
         n, S = obs.shape
@@ -126,8 +160,7 @@ class SharedPPOLearner(object):
             adv_sums = adv_sums.to(torch.float32).contiguous()
         W, G = abi.MMGiParams(), abi.MMGiParams()
         for name, p in zip(abi.GI_PARAMS, _params(self.policy)):
-            if p.grad is None or not p.grad.is_contiguous():
-                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            _ensure_grad(p)
             setattr(W, name, p.detach().data_ptr())
             setattr(G, name, p.grad.data_ptr())
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
@@ -162,20 +195,7 @@ class SharedPPOLearner(object):
         samples with the per-sample PPO-clip objective; `valid` [B, N] masks the empty slots of ragged batches (kind == 0).
         The soft update of the target runs after each optimiser step when n_episodes % target_update_steps == 0 and
         n_episodes > 0.  Returns the list of float32 [3] loss tensors (one per optimiser step); nothing is synchronised."""
-        if isinstance(states, dict):
-            states, actions, returns = states["states"], states["actions"], states["returns"]
-        N, S = states.shape[-2], states.shape[-1]
-        states = states.reshape(-1, N, S)
-        if states.dtype != torch.float32:
-            states = states.float()
-        actions = actions.reshape(-1, N)
-        if actions.dtype != torch.int32:
-            actions = actions.to(torch.int32)
-        returns = returns.reshape(-1, N)
-        if returns.dtype != torch.float32:
-            returns = returns.float()  # (DeviceRollout's returns are float64: converted once)
-        if valid is not None:
-            valid = valid.reshape(-1, N).to(torch.uint8)
+        states, actions, returns, valid, N, S = _batch(states, actions, returns, valid)
         losses = []
         if form == "reference":
             for agent_id in range(N):
@@ -205,13 +225,13 @@ def _mlp_params(net):
 def _mlp_struct(net, grads=False):
     st = abi.MMMlpParams()
     for name, p in zip(abi.MLP_PARAMS, _mlp_params(net)):
-        if grads and (p.grad is None or not p.grad.is_contiguous()):
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        if grads:
+            _ensure_grad(p)
         setattr(st, name, p.grad.data_ptr() if grads else p.detach().data_ptr())
     return st
 
 
-class PPOLearner(object):
+class PPOLearner(_DeviceLearner):
     """`MAPPO`'s actor / critic / actor_target / critic_target / two optimisers and its train() (marl/mappo.py:70-95, :161-206);
     defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, hidden 128, float32,
     on the device -- typically the modules a DeviceRollout acts with, so the next rollout uses the updated weights.
@@ -237,32 +257,20 @@ class PPOLearner(object):
                 raise ValueError("PPOLearner needs float32 networks on the device")
         if critic_loss not in abi.PT_CRITIC_LOSS:
             raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
-        if optimizer_type not in ("adam", "rmsprop"):
-            raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
+        opt = _optimizer_class(optimizer_type)
         clib.require_policy_train()
-        self.actor, self.critic, self.clib = actor, critic, clib
+        _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, clib.policy_train_scratch_bytes)
+        self.actor, self.critic = actor, critic
         self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)
-        opt = torch.optim.Adam if optimizer_type == "adam" else torch.optim.RMSprop
         self.actor_optimizer = opt(actor.parameters(), lr=actor_lr)
         self.critic_optimizer = opt(critic.parameters(), lr=critic_lr)
         self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
         self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
         self.n_s, self.n_a = n_s, n_a
-        self.device = actor.fc1.weight.device
-        _mlp_struct(actor, grads=True)  # the library writes the gradients straight into .grad
-        _mlp_struct(critic, grads=True)
-        self._scratch = None
+        for p in list(actor.parameters()) + list(critic.parameters()):
+            _ensure_grad(p)
 
     # -- plumbing ----------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _ensure_scratch(self, n):
-        need = self.clib.policy_train_scratch_bytes(n)
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
-        return self._scratch
-
     def _check_batch(self, obs, actions):
         n, S = obs.shape
         if obs.dtype != torch.float32 or (n and obs.stride(1) != 1) or S != self.n_s:
@@ -370,20 +378,7 @@ class PPOLearner(object):
         `valid` [B, N] masks the empty slots of ragged batches (kind == 0).  The soft update of both targets runs once, after
         the loop, when n_episodes % target_update_steps == 0 and n_episodes > 0.  Returns the list of float32 [2] loss tensors
         (one per agent step); nothing is synchronised."""
-        if isinstance(states, dict):
-            states, actions, returns = states["states"], states["actions"], states["returns"]
-        N, S = states.shape[-2], states.shape[-1]
-        states = states.reshape(-1, N, S)
-        if states.dtype != torch.float32:
-            states = states.float()
-        actions = actions.reshape(-1, N)
-        if actions.dtype != torch.int32:
-            actions = actions.to(torch.int32)
-        returns = returns.reshape(-1, N)
-        if returns.dtype != torch.float32:
-            returns = returns.float()  # (DeviceRollout's returns are float64: converted once)
-        if valid is not None:
-            valid = valid.reshape(-1, N).to(torch.uint8)
+        states, actions, returns, valid, N, S = _batch(states, actions, returns, valid)
         losses = []
         if form == "reference":
             for agent_id in range(N):
