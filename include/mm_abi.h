@@ -407,11 +407,17 @@ int32_t mm_math_eval(int32_t fn, int32_t n, const double *x, const double *x2, d
  *                  early-out boxes_may_touch, then the 9-point test), [1] the same against an Obstacle (2 x 2, heading 0) at
  *                  (x2, y2), [2] / [3] the 9-point test alone (= rotated_rectangles_intersect) for the two cases
  *   MM_GEOM_SPEED_INDEX in [n][1] speed -> out [n][1] MDPVehicle.speed_to_index
+ *   MM_GEOM_DIV    in [n][2] x, d -> out [n][4]: the division forms of marl-mass_amd/csrc/mm_div.h (device library only):
+ *                  [0] x / d through the shared correctly rounded reciprocal and its guard, [1] that reciprocal, 1 / d,
+ *                  [2] x / (int)d by the table of small-integer reciprocals where d is an integer value (NaN in the other
+ *                  rows) -- each equal to `/` -- and [3] the quotient of a lane that does not need it (no fall-back:
+ *                  equal to `/` for operands inside the guard, unspecified outside)
  */
 #define MM_GEOM_POSE 0
 #define MM_GEOM_STEER 1
 #define MM_GEOM_RECT 2
 #define MM_GEOM_SPEED_INDEX 3
+#define MM_GEOM_DIV 4
 int32_t mm_geom_eval(int32_t fn, int32_t n, const double *in, double *out, MMStream stream);
 
 #ifdef __cplusplus

@@ -60,7 +60,7 @@ class MMConfig(C.Structure):
                 ("traffic_density", C.c_int32), ("mixed_traffic", C.c_int32), ("num_cav", C.c_int32), ("reserved1", C.c_int32)]
 
 
-GEOM_POSE, GEOM_STEER, GEOM_RECT, GEOM_SPEED_INDEX = 0, 1, 2, 3  # mm_geom_eval functions (include/mm_abi.h)
+GEOM_POSE, GEOM_STEER, GEOM_RECT, GEOM_SPEED_INDEX, GEOM_DIV = 0, 1, 2, 3, 4  # mm_geom_eval functions (include/mm_abi.h; GEOM_DIV: device library only)
 
 
 class MMStepOut(C.Structure):

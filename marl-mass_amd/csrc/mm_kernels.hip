@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "mm_device.h"
+#include "mm_div.h"  // tested division forms behind MM_GEOM_DIV; no step kernel uses them
 #include "mm_handle.h"
 #define MM_COUNTS_FN __host__ __device__ inline
 #include "../../include/mm_counts.h"
@@ -2439,14 +2440,21 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     int pk = px_i<m, G>(v.present ? v.lane : 15, a);
     bool pp = pk != 15;
     if (MIXED) hdv_bits |= (px_i<m, G>((int)hdv, a) != 0) ? (1u << p) : 0u;
-    if (pp && pk == v.lane && px > v.x) { double dd = px - v.x; if (dd < hd) hd = dd; }
-    if (pp && v.lane != MM_LANE_BC1 && pk == nl && px > v.x) { double dd = px - v.x; if (dd < hd) hd = dd; }
-    const bool in_own = pp && ((allow_own >> pk) & 1u), in_side = pp && ((allow_side >> pk) & 1u);
+    // compare-and-select form like relate() / neighbour_update(): no short-circuit, so no exec-mask region per condition
+    const double dd = px - v.x;
+    const bool head = pp & (px > v.x) & ((pk == v.lane) | ((v.lane != MM_LANE_BC1) & (pk == nl)));
+    hd = (head & (dd < hd)) ? dd : hd;
+    const bool in_own = pp & (((allow_own >> pk) & 1u) != 0), in_side = pp & (((allow_side >> pk) & 1u) != 0);
+    const bool fwd = v.x <= px, back = px < v.x;
     // road.py:344-349: front = min s_v >= s (ties: later index), rear = max s_v < s (ties: earlier)
-    if (in_own && v.x <= px && (of_i < 0 || px < of_s || (px == of_s && p > of_i))) { of_s = px; of_i = p; }
-    if (in_own && px < v.x && (or_i < 0 || px > or_s || (px == or_s && p < or_i))) { or_s = px; or_i = p; }
-    if (in_side && v.x <= px && (sf_i < 0 || px < sf_s || (px == sf_s && p > sf_i))) { sf_s = px; sf_i = p; }
-    if (in_side && px < v.x && (sr_i < 0 || px > sr_s || (px == sr_s && p < sr_i))) { sr_s = px; sr_i = p; }
+    const bool t_of = in_own & fwd & ((of_i < 0) | (px < of_s) | ((px == of_s) & (p > of_i)));
+    const bool t_or = in_own & back & ((or_i < 0) | (px > or_s) | ((px == or_s) & (p < or_i)));
+    const bool t_sf = in_side & fwd & ((sf_i < 0) | (px < sf_s) | ((px == sf_s) & (p > sf_i)));
+    const bool t_sr = in_side & back & ((sr_i < 0) | (px > sr_s) | ((px == sr_s) & (p < sr_i)));
+    of_s = t_of ? px : of_s; of_i = t_of ? p : of_i;
+    or_s = t_or ? px : or_s; or_i = t_or ? p : or_i;
+    sf_s = t_sf ? px : sf_s; sf_i = t_sf ? p : sf_i;
+    sr_s = t_sr ? px : sr_s; sr_i = t_sr ? p : sr_i;
   });
   // _agent_reward merge_env_v1.py:64-89
   double local = 0;
@@ -2486,10 +2494,14 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   }
   // env-level sums in creation order (Python sum / += order)
   double rsum = 0, ssum = 0, tsum = 0;
-  for (int q = 0; q < st.N; q++) {
+  // compile-time trip count: the exchanges of all G slots are issued back to back and waited for once
+#pragma unroll
+  for (int q = 0; q < G; q++) {
     const double lr = shfl_d(local, gb + q), sp = shfl_d(v.v, gb + q);
-    if ((ctrl_bits >> q) & 1u) { rsum += lr; ssum += sp; }
-    if ((present_bits >> q) & 1u) tsum += sp;  // traffic_speed over road.vehicles (:147-151)
+    const bool in = q < st.N, cq = in & (((ctrl_bits >> q) & 1u) != 0), pq = in & (((present_bits >> q) & 1u) != 0);
+    const double r1 = rsum + lr, s1 = ssum + sp, t1 = tsum + sp;
+    rsum = cq ? r1 : rsum; ssum = cq ? s1 : ssum;
+    tsum = pq ? t1 : tsum;  // traffic_speed over road.vehicles (:147-151)
   }
   const double reward = env_ok ? rsum / n_ctrl : 0, avg_speed = env_ok ? ssum / n_ctrl : 0;
   const double traffic_speed = env_ok ? tsum / n_veh : 0;
@@ -3578,12 +3590,22 @@ __global__ void geom_kernel(int fn, int n, const double *__restrict__ in, double
     const bool full_o = rects_intersect(r[0], r[1], r[2], r[3], r[4], 2.0, 2.0, 0.0);
     o[0] = (t_v && full_v) ? 1.0 : 0.0; o[1] = (t_o && full_o) ? 1.0 : 0.0;
     o[2] = full_v ? 1.0 : 0.0; o[3] = full_o ? 1.0 : 0.0;
+  } else if (fn == MM_GEOM_DIV) {
+    const double x = in[i * 2 + 0], d = in[i * 2 + 1];
+    double *o = out + (long long)i * 4;
+    const double y = rcp_rn(d);
+    const bool ok = rcp_ok(d);
+    o[0] = div_g(x, d, y, ok);
+    o[1] = rcp_g(d, y, ok);
+    const bool integral = fabs(d) <= 1e9 && d == (double)(int)d;
+    o[2] = integral ? div_n(x, (int)d, integral) : __builtin_nan("");
+    o[3] = div_g(x, d, y, ok, false);  // a lane that does not need its quotient never sends the wave to the plain division
   } else {
     out[i] = speed_to_index(in[i]);
   }
 }
 extern "C" int32_t mm_geom_eval(int32_t fn, int32_t n, const double *in, double *out, MMStream stream) {
-  if (fn < MM_GEOM_POSE || fn > MM_GEOM_SPEED_INDEX || n <= 0 || !in || !out) return MM_ERR_INVALID_ARG;
+  if (fn < MM_GEOM_POSE || fn > MM_GEOM_DIV || n <= 0 || !in || !out) return MM_ERR_INVALID_ARG;
   hipLaunchKernelGGL(geom_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, fn, n, in, out);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
