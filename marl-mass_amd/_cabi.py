@@ -88,6 +88,20 @@ class MMMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in MLP_PARAMS]
 
 
+OPT_RMSPROP, OPT_ADAM, OPT_BLEND = 0, 1, 2  # MM_OPT_* (include/mm_opt_step.h)
+OPT_MAX_TENSORS, OPT_MAX_GROUPS = 16, 4
+
+
+class MMOptGroup(C.Structure):
+    """One network = one clipping group = one optimiser of mm_opt_step (include/mm_opt_step.h)."""
+    _fields_ = [("algo", C.c_int32), ("n_tensors", C.c_int32), ("count", C.c_int64 * OPT_MAX_TENSORS),
+                ("param", C.c_void_p * OPT_MAX_TENSORS), ("grad", C.c_void_p * OPT_MAX_TENSORS),
+                ("state1", C.c_void_p * OPT_MAX_TENSORS), ("state2", C.c_void_p * OPT_MAX_TENSORS),
+                ("target", C.c_void_p * OPT_MAX_TENSORS), ("step", C.c_void_p),
+                ("lr", C.c_double), ("alpha_or_beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("max_grad_norm", C.c_double), ("tau", C.c_double), ("soft_update", C.c_int32), ("grad_norm", C.c_void_p)]
+
+
 SUPERVISED = ("priority", "dmc")
 
 
@@ -310,6 +324,11 @@ class CLib(object):
             lib.mm_policy_train.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, vp, pp, pp, i32, i32, f32, i32, vp, vp, pp, pp,
                                             vp, vp, vp, vp, vp, u64, vp]
             lib.mm_policy_train.restype = i32
+        # clip_grad_norm_ + RMSprop / Adam + soft target update in one launch (include/mm_opt_step.h), also libmm_hip.so only
+        self.has_opt_step = hasattr(lib, "mm_opt_step")
+        if self.has_opt_step:
+            lib.mm_opt_step.argtypes = [C.POINTER(MMOptGroup), i32, vp]
+            lib.mm_opt_step.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -365,6 +384,17 @@ class CLib(object):
         b = C.c_uint64()
         self.check(self.lib.mm_policy_train_scratch_bytes(n, C.byref(b)))
         return b.value
+
+    def require_opt_step(self):
+        if not self.has_opt_step:
+            raise NotImplementedError("%s does not export mm_opt_step: the fused optimiser step needs the HIP library"
+                                      % os.path.basename(self.path))
+
+    def opt_step(self, groups, stream):
+        """mm_opt_step on a sequence of MMOptGroup (include/mm_opt_step.h); stream: the hipStream_t as c_void_p."""
+        self.require_opt_step()
+        arr = (MMOptGroup * len(groups))(*groups)
+        self.check(self.lib.mm_opt_step(arr, len(groups), stream))
 
     def state_layout(self, E, N):
         lay = MMStateLayout()

@@ -17,3 +17,7 @@ struct MMHandleHead {
 
 // defined in mm_kernels.hip; not exported from the shared library
 __attribute__((visibility("hidden"))) const MMHandleHead *mm_handle_head(MMHandle h);
+
+// sets the text that mm_last_error(NULL) returns on this thread: how an entry point without a handle (mm_opt_step) says why it
+// refused.  Defined in mm_kernels.hip; not exported from the shared library
+__attribute__((visibility("hidden"))) void mm_set_thread_error(const char *text);

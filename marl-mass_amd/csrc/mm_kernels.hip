@@ -3010,6 +3010,7 @@ static hipError_t ensure_sweep(MMHandle_ *h) {
 }
 
 static thread_local char g_create_err[256] = "null handle";  // why the last mm_create of this thread refused (there is no handle to ask)
+void mm_set_thread_error(const char *text) { snprintf(g_create_err, sizeof g_create_err, "%s", text); }  // (mm_handle.h)
 // The host-side entries that touch the runtime outside a stream (allocation, latch poll, drain) must address the handle's
 // device, but the caller's current device is the caller's: it is put back on exit (a two-GPU process polling the env of the
 // other GPU would otherwise find torch's current device changed under it).

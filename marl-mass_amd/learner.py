@@ -6,9 +6,13 @@ and critic, their targets and two optimisers, with both losses and both paramete
 branch :305-352) with the loss and the full parameter gradient taken by one library call (`mm_policy_gi_train`,
 include/mm_policy_gi_train.h) instead of torch autograd.
 
-What stays torch: the optimiser arithmetic (RMSprop / Adam on 22 982 parameters), `clip_grad_norm_` and the soft target
-update -- a few launches on 90 KB.  What the library does: the network forward on every sample, the PPO-clip and critic
-losses, and the backward into all twelve parameter tensors, deterministically (no floating-point atomics).
+What the library does: the network forward on every sample, the PPO-clip and critic losses, and the backward into all twelve
+parameter tensors, deterministically (no floating-point atomics).  The end of the agent step -- `clip_grad_norm_`, the
+optimiser arithmetic (RMSprop / Adam on 22 982 parameters) and the soft target update -- is torch by default, a few dozen
+launches on 90 KB; with `fused_step=True` it is ONE library call (`mm_opt_step`, include/mm_opt_step.h) with torch's
+arithmetic, the optimiser state in tensors the learner owns and Adam's step count on the device, which makes train()
+capturable in a graph.  The fused step reads the gradients without scaling them: `.grad` keeps what the gradient kernels
+wrote, where torch's `clip_grad_norm_` leaves the clipped gradient there.
 
 The reference's actor loss is kept literally.  There `ratio` has shape [B] and `advantages = returns - values.detach()` has
 shape [B, 1], so `ratio * advantages` broadcasts to [B, B]: every sample's ratio is weighted by EVERY sample's advantage,
@@ -40,6 +44,108 @@ def _optimizer_class(optimizer_type):
     if optimizer_type not in ("adam", "rmsprop"):
         raise ValueError("optimizer_type must be 'rmsprop' or 'adam', got %r" % (optimizer_type,))
     return torch.optim.Adam if optimizer_type == "adam" else torch.optim.RMSprop
+
+
+OPT_ALGO = {"rmsprop": abi.OPT_RMSPROP, "adam": abi.OPT_ADAM}
+_STATE_KEYS = {"rmsprop": ("square_avg",), "adam": ("exp_avg", "exp_avg_sq")}
+
+
+def optimizer_state_to_torch(optimizer_type, param_groups, step, state1, state2=None):
+    """The fused step's optimiser state -> torch.optim's own state_dict(): {"state": {i: {"step", "square_avg"} or {"step",
+    "exp_avg", "exp_avg_sq"}}, "param_groups": param_groups}.  `step` (an int: every parameter of a network has taken the same
+    number of steps) is stored as torch stores it, a float32 0-dim CPU tensor per parameter; the state tensors are cloned.  A
+    network that has taken no step has an empty "state", as a fresh torch optimiser has."""
+    keys = _STATE_KEYS[optimizer_type]
+    state = {}
+    if step > 0:
+        for i, tensors in enumerate(zip(*([state1, state2][:len(keys)]))):
+            state[i] = {"step": torch.tensor(float(step), dtype=torch.float32)}
+            state[i].update({k: t.detach().clone() for k, t in zip(keys, tensors)})
+    return {"state": state, "param_groups": copy.deepcopy(param_groups)}
+
+
+def optimizer_state_from_torch(state_dict, optimizer_type, n_params):
+    """torch.optim's state_dict() of an RMSprop / Adam with torch's defaults -> (step, state1, state2): the common step count
+    as an int and the lists of n_params state tensors (None where torch has no state yet: zeros; state2 is None for RMSprop).
+    ValueError for what the fused step does not implement (momentum, centred, amsgrad) or parameters at different steps."""
+    keys = _STATE_KEYS[optimizer_type]
+    state = state_dict["state"]
+    if sum(len(g["params"]) for g in state_dict["param_groups"]) != n_params or any(i not in range(n_params) for i in state):
+        raise ValueError("the state dict is not that of an optimiser over %d parameters" % n_params)
+    steps, out = set(), [[None] * n_params for _ in keys]
+    for i in range(n_params):
+        st = state.get(i, {})
+        extra = set(st) - set(keys) - {"step"}
+        if extra:
+            raise ValueError("optimiser state %s is not supported by the fused step" % sorted(extra))
+        if st and set(keys) - set(st):
+            raise ValueError("the state dict is not a torch.optim %s state: parameter %d lacks %s"
+                             % (optimizer_type, i, sorted(set(keys) - set(st))))
+        steps.add(int(st["step"]) if st else 0)
+        for j, k in enumerate(keys):
+            out[j][i] = st.get(k)
+    if len(steps) > 1:
+        raise ValueError("the fused step keeps one step count per network, the state dict has %s" % sorted(steps))
+    return (steps.pop() if steps else 0), out[0], (out[1] if len(keys) > 1 else None)
+
+
+class _FusedOptimizer(object):
+    """One network's optimiser for mm_opt_step: the state in tensors allocated here, once (nothing is allocated under graph
+    capture), and the MMOptGroup that points at parameters, state and targets.  Hyperparameters are read from the torch
+    optimiser's param_groups at every step (that object is kept for them and for the state-dict format; it never steps)."""
+
+    def __init__(self, optimizer_type, optimizer, params, targets, grad_norm):
+        if len(params) > abi.OPT_MAX_TENSORS:
+            raise ValueError("mm_opt_step takes at most %d tensors per network" % abi.OPT_MAX_TENSORS)
+        self.optimizer_type, self.optimizer, self.params, self.targets = optimizer_type, optimizer, params, targets
+        new = lambda p: torch.zeros_like(p, memory_format=torch.contiguous_format)  # noqa: E731
+        self.state1 = [new(p) for p in params]
+        self.state2 = [new(p) for p in params] if optimizer_type == "adam" else None
+        self.step = torch.zeros(1, dtype=torch.int32, device=params[0].device)
+        g = self.group = abi.MMOptGroup()
+        g.algo, g.n_tensors = OPT_ALGO[optimizer_type], len(params)
+        for i, (p, t) in enumerate(zip(params, targets)):
+            if not p.is_contiguous() or not t.is_contiguous():
+                raise ValueError("the fused step needs contiguous parameters")
+            g.count[i], g.param[i], g.target[i], g.state1[i] = p.numel(), p.data_ptr(), t.data_ptr(), self.state1[i].data_ptr()
+            if self.state2 is not None:
+                g.state2[i] = self.state2[i].data_ptr()
+        g.step, g.grad_norm = self.step.data_ptr(), grad_norm.data_ptr()
+
+    def fill(self, max_grad_norm, tau, soft_update):
+        """The group for one step: current hyperparameters and gradient buffers."""
+        g, h = self.group, self.optimizer.param_groups[0]
+        for i, p in enumerate(self.params):
+            _ensure_grad(p)
+            g.grad[i] = p.grad.data_ptr()
+        g.lr, g.eps = h["lr"], h["eps"]
+        if self.optimizer_type == "adam":
+            g.alpha_or_beta1, g.beta2 = h["betas"]
+        else:
+            g.alpha_or_beta1 = h["alpha"]
+        g.max_grad_norm = -1.0 if max_grad_norm is None else max_grad_norm
+        g.tau, g.soft_update = tau, int(bool(soft_update))
+        return g
+
+    def blend_group(self, tau):
+        g = abi.MMOptGroup()
+        g.algo, g.n_tensors, g.tau = abi.OPT_BLEND, self.group.n_tensors, tau
+        for i in range(g.n_tensors):
+            g.count[i], g.param[i], g.target[i] = self.group.count[i], self.group.param[i], self.group.target[i]
+        return g
+
+    def state_dict(self):
+        return optimizer_state_to_torch(self.optimizer_type, self.optimizer.state_dict()["param_groups"], int(self.step.item()),
+                                        self.state1, self.state2)
+
+    def load_state_dict(self, state_dict):
+        step, s1, s2 = optimizer_state_from_torch(state_dict, self.optimizer_type, len(self.params))
+        self.optimizer.load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})  # (the hyperparameters)
+        for mine, theirs in ((self.state1, s1), (self.state2, s2)):
+            if mine is not None:
+                for m, t in zip(mine, theirs):
+                    m.zero_() if t is None else m.copy_(t)  # (in place: the group's pointers stay valid)
+        self.step.fill_(step)
 
 
 def _ensure_grad(p):
@@ -79,6 +185,40 @@ class _DeviceLearner(object):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _init_fused(self, fused_step, optimizer_type, networks):
+        """networks: (torch optimiser, parameters, target's parameters) per network, in the order of the launch's groups.
+        Also the clipping norm's home: `last_grad_norm`, float32 [number of networks] on the device."""
+        self.fused_step = bool(fused_step)
+        self._torch_optimizers = [n[0] for n in networks]
+        self._norms = None
+        if self.fused_step:
+            self.clib.require_opt_step()
+            self._grad_norm = torch.zeros(len(networks), dtype=torch.float32, device=self.device)
+            self._fused = [_FusedOptimizer(optimizer_type, opt, list(params), list(targets), self._grad_norm[i:i + 1])
+                           for i, (opt, params, targets) in enumerate(networks)]
+
+    def _fused_launch(self, soft_update):
+        """clip + optimiser step (+ soft update) of every network: one mm_opt_step launch."""
+        self.clib.opt_step([f.fill(self.max_grad_norm, self.target_tau, soft_update) for f in self._fused], self._stream())
+
+    @property
+    def last_grad_norm(self):
+        """The total gradient norm(s) before clipping of the last optimiser step, float32 on the device, one per network
+        (fused: written by the launch; torch path: clip_grad_norm_'s return values).  None before the first step and, on
+        the torch path, without clipping."""
+        if self.fused_step:
+            return self._grad_norm
+        return None if not self._norms else torch.stack([n.to(torch.float32) for n in self._norms])
+
+    def _state_dicts(self):
+        if self.fused_step:
+            return [f.state_dict() for f in self._fused]
+        return [o.state_dict() for o in self._torch_optimizers]
+
+    def _load_state_dicts(self, state_dicts):
+        for target, sd in zip(self._fused if self.fused_step else self._torch_optimizers, state_dicts):
+            target.load_state_dict(sd)
+
     def _ensure_scratch(self, n):
         need = self._scratch_bytes(n)
         if self._scratch is None or self._scratch.numel() < need:
@@ -92,7 +232,7 @@ class SharedPPOLearner(_DeviceLearner):
     float32, on the device -- typically the module a DeviceRollout acts with, so the next rollout uses the updated weights."""
 
     def __init__(self, policy, clib, lr=1e-4, optimizer_type="rmsprop", clip_param=0.2, critic_loss="mse", max_grad_norm=0.5,
-                 target_tau=1.0, target_update_steps=5):
+                 target_tau=1.0, target_update_steps=5, fused_step=False):
         if type(policy) is not ActorCriticNetwork or not policy.state_split or policy.fc2.weight.shape[0] != 128:
             raise ValueError("SharedPPOLearner needs rollout.ActorCriticNetwork(state_split=True) with hidden size 128")
         p0 = policy.fc2.weight
@@ -111,6 +251,16 @@ class SharedPPOLearner(_DeviceLearner):
         self.n_a = policy.actor_linear.weight.shape[0]
         for p in policy.parameters():
             _ensure_grad(p)
+        # fused_step: clip + optimiser + soft update as one mm_opt_step launch (see the module docstring); self.optimizer
+        # then only holds the hyperparameters
+        self._init_fused(fused_step, optimizer_type, [(self.optimizer, _params(policy), _params(self.policy_target))])
+
+    def optimizer_state_dict(self):
+        """The optimiser's state in torch.optim's state_dict() format, whichever path steps: it loads into either."""
+        return self._state_dicts()[0]
+
+    def load_optimizer_state_dict(self, state_dict):
+        self._load_state_dicts([state_dict])
 
     # -- plumbing ----------------------------------------------------------------------------
     def _act(self, net, obs, logp=None, value=None):
@@ -176,10 +326,13 @@ class SharedPPOLearner(_DeviceLearner):
 
     # -- MAPPO_GI.train() ----------------------------------------------------------------------
     def _step(self, n_episodes):
+        soft = n_episodes % self.target_update_steps == 0 and n_episodes > 0  # _soft_update_target (:348-352, :545-547)
+        if self.fused_step:
+            return self._fused_launch(soft)
         if self.max_grad_norm is not None:
-            torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+            self._norms = [torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)]
         self.optimizer.step()
-        if n_episodes % self.target_update_steps == 0 and n_episodes > 0:  # _soft_update_target (:348-352, :545-547)
+        if soft:
             with torch.no_grad():
                 for t, s in zip(self.policy_target.parameters(), self.policy.parameters()):
                     t.copy_((1.0 - self.target_tau) * t + self.target_tau * s)
@@ -242,7 +395,10 @@ class PPOLearner(_DeviceLearner):
     (:203-206), not per agent step as in MAPPO_GI."""
 
     def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
-                 critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5):
+                 critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
+                 soft_update_every="train"):
+        if soft_update_every not in ("train", "agent_step"):
+            raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
             raise ValueError("PPOLearner needs a rollout.ActorNetwork and a rollout.CriticNetwork")
         n_s, n_a = actor.fc1.weight.shape[1], actor.fc3.weight.shape[0]
@@ -269,6 +425,21 @@ class PPOLearner(_DeviceLearner):
         self.n_s, self.n_a = n_s, n_a
         for p in list(actor.parameters()) + list(critic.parameters()):
             _ensure_grad(p)
+        # soft_update_every "train": MAPPO's, once per train(); "agent_step": MAPPO_GI's non-shared branch (marl/mappo_gi.py:
+        # 247-304: the same networks and optimisers), both targets blended after EVERY agent step of a train() that updates
+        self.soft_update_every = soft_update_every
+        # fused_step: both networks' clip + optimiser (+ soft update) as one mm_opt_step launch of two workgroups
+        self._init_fused(fused_step, optimizer_type, [
+            (self.actor_optimizer, _mlp_params(actor), _mlp_params(self.actor_target)),
+            (self.critic_optimizer, _mlp_params(critic), _mlp_params(self.critic_target))])
+
+    def optimizer_state_dict(self):
+        """{"actor_optimizer", "critic_optimizer"}: each optimiser's state in torch.optim's state_dict() format, whichever
+        path steps: it loads into either."""
+        return dict(zip(("actor_optimizer", "critic_optimizer"), self._state_dicts()))
+
+    def load_optimizer_state_dict(self, state_dict):
+        self._load_state_dicts([state_dict["actor_optimizer"], state_dict["critic_optimizer"]])
 
     # -- plumbing ----------------------------------------------------------------------------
     def _check_batch(self, obs, actions):
@@ -353,16 +524,25 @@ class PPOLearner(_DeviceLearner):
         return (loss, tuple(diag)) if diagnostics else loss
 
     # -- MAPPO.train() -------------------------------------------------------------------------
-    def _step(self):
-        """clip_grad_norm_ + step, the actor's then the critic's (:186-188, :199-201): each its own norm and optimiser."""
+    def _step(self, soft=False):
+        """clip_grad_norm_ + step, the actor's then the critic's (:186-188, :199-201): each its own norm and optimiser; then,
+        with soft, the soft update of both targets.  Fused: all of it is one launch."""
+        if self.fused_step:
+            return self._fused_launch(soft)
+        norms = []
         for net, optimizer in ((self.actor, self.actor_optimizer), (self.critic, self.critic_optimizer)):
             if self.max_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm)
+                norms.append(torch.nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm))
             optimizer.step()
+        self._norms = norms
+        if soft:
+            self.soft_update()
 
     @torch.no_grad()
     def soft_update(self):
         """_soft_update_target of both targets: t = (1 - tau) t + tau s."""
+        if self.fused_step:
+            return self.clib.opt_step([f.blend_group(self.target_tau) for f in self._fused], self._stream())
         for target, source in ((self.actor_target, self.actor), (self.critic_target, self.critic)):
             for t, s in zip(target.parameters(), source.parameters()):
                 t.copy_((1.0 - self.target_tau) * t + self.target_tau * s)
@@ -375,11 +555,16 @@ class PPOLearner(_DeviceLearner):
         as the first argument.  form "reference": for agent_id in order, one actor and one critic optimiser step on the B
         samples of that agent with the reference's [B, B] actor objective -- N sequential steps, each on the parameters as
         they then are.  form "flat": ONE step per network on all B * N samples with the per-sample PPO-clip objective;
-        `valid` [B, N] masks the empty slots of ragged batches (kind == 0).  The soft update of both targets runs once, after
-        the loop, when n_episodes % target_update_steps == 0 and n_episodes > 0.  Returns the list of float32 [2] loss tensors
-        (one per agent step); nothing is synchronised."""
+        `valid` [B, N] masks the empty slots of ragged batches (kind == 0).  The soft update of both targets runs when
+        n_episodes % target_update_steps == 0 and n_episodes > 0: once, after the loop (soft_update_every "train"; fused, it
+        rides in the launch of the last agent step) or after every agent step ("agent_step").  Returns the list of float32
+        [2] loss tensors (one per agent step); nothing is synchronised."""
         states, actions, returns, valid, N, S = _batch(states, actions, returns, valid)
         losses = []
+        update = n_episodes % self.target_update_steps == 0 and n_episodes > 0
+        every = self.soft_update_every == "agent_step"
+        # the soft update a step carries: every step's, or (fused only) the one after the loop in the last step's launch
+        carried = lambda last: update and (every or (last and self.fused_step))  # noqa: E731
         if form == "reference":
             for agent_id in range(N):
                 obs, act, ret = states[:, agent_id, :], actions[:, agent_id], returns[:, agent_id]
@@ -388,15 +573,15 @@ class PPOLearner(_DeviceLearner):
                 adv = self._adv(ret, value, v)
                 sums = torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
                 losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, adv_sums=sums))
-                self._step()
+                self._step(carried(agent_id == N - 1))
         elif form == "flat":
             obs, act, ret = states.reshape(-1, S), actions.reshape(-1), returns.reshape(-1)
             v = None if valid is None else valid.reshape(-1)
             old, value = self.evaluate(obs, act, actor=self.actor_target, critic=self.critic_target, valid=v)
             losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, advantages=self._adv(ret, value, v)))
-            self._step()
+            self._step(carried(True))
         else:
             raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
-        if n_episodes % self.target_update_steps == 0 and n_episodes > 0:
+        if update and not every and not (self.fused_step and losses):
             self.soft_update()
         return losses
