@@ -193,6 +193,20 @@ MMM_FN double mmm_atan(double x) {
   if (inv) r = MMM_PIO2_HI - (r - MMM_PIO2_LO);
   return x < 0 ? -r : r;
 }
+/* mmm_atan for |x| < 0.125 (the slope of the sine lane: at most 3.25 pi / 100 = 0.1021), bit for bit.  There mmm_atan takes
+ * inv = 0 and mmm_atan_ratio j = 0, c = 0, so t = (|x| - 0 * 1.0) / (1.0 + 0 * |x|) = |x| / 1.0 = |x| exactly and hi = lo = 0:
+ * the result is 0.0 + (pt + 0.0) = pt with pt = fma(t z, p, t) >= +0 (t = +0 gives fma(+0, p, +0) = +0, never -0), and x + 0.0
+ * = 0.0 + x = x for every x that is not -0.  No division, no breakpoint compares, no selects; a NaN stays a NaN. */
+MMM_FN double mmm_atan_small(double x) {
+  double t = fabs(x);
+  double z = t * t;
+  double p = MMM_K(mmm_t_atan, 0, MMM_A10);
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 1, MMM_A9)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 2, MMM_A8)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 3, MMM_A7)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 4, MMM_A6));
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 5, MMM_A5)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 6, MMM_A4)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 7, MMM_A3)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 8, MMM_A2));
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 9, MMM_A1));
+  double r = fma(t * z, p, t);
+  return x < 0 ? -r : r;
+}
 /* asin(x) = atan2(|x|, sqrt((1-|x|)(1+|x|))), |x| <= 1; *w_out = sqrt((1-|x|)(1+|x|)) = cos(asin x), which the bicycle
  * step reuses (sin / cos of a steering angle that IS an arcsine: no second range reduction, no polynomials) */
 MMM_FN double mmm_asin_w(double x, double *w_out) {

@@ -103,8 +103,16 @@ MM_DEV void lane_local(int l, double x, double y, double &s, double &r) {  // la
   r = y - lane_sy(l);
   if (l == MM_LANE_KB0) r = r - kSineAmp * mmm_sin(kSinePuls * s + kSinePhase);
 }
+// the sine lane's slope is at most kSineAmp * kSinePuls = 0.1021 (mmm_cos may overshoot 1 by an ulp or two): mmm_atan_small's
+// range, where it returns mmm_atan's bits without the division and the breakpoint selects
+static_assert(kSineAmp * kSinePuls * (1.0 + 0x1p-40) < 0.125, "the sine lane's heading needs the general mmm_atan");
+// SINE (here and below): the instantiation evaluates the sine lane's frame in its short forms -- mmm_atan_small, one mmm_sincos
+// per pose in closest_lane -- which return the bits of the general forms.  A compile-time choice of the kernel, because the
+// forms change its register allocation: see kSine in step_kernel
+template <bool SINE = false>
 MM_DEV double lane_heading_at(int l, double s) {  // lane.py:158-159, :204-206
-  return l == MM_LANE_KB0 ? 0.0 + mmm_atan(kSineAmp * kSinePuls * mmm_cos(kSinePuls * s + kSinePhase)) : 0.0;
+  if constexpr (SINE) return l == MM_LANE_KB0 ? 0.0 + mmm_atan_small(kSineAmp * kSinePuls * mmm_cos(kSinePuls * s + kSinePhase)) : 0.0;
+  else return l == MM_LANE_KB0 ? 0.0 + mmm_atan(kSineAmp * kSinePuls * mmm_cos(kSinePuls * s + kSinePhase)) : 0.0;
 }
 MM_DEV double lane_distance(int l, double x, double y) {  // lane.py:97-100
   double s, r;
@@ -129,6 +137,7 @@ MM_DEV bool lane_after_end(int l, double x) {  // lane.py:92-95 (longitudinal on
 // road.py:51-65 get_closest_lane_index: argmin of distance_with_heading (lane.py:102-108), first
 // minimum in insertion order.  The five straight lanes share heading 0, so |wrap(h - 0)| is
 // computed once; only kb0 needs the sine frame.
+template <bool SINE = false>
 MM_DEV int closest_lane(double x, double y, double h) {
   const double ang0 = fabs(wrap_to_pi(h - 0.0));
   int best = 0;
@@ -146,8 +155,17 @@ MM_DEV int closest_lane(double x, double y, double h) {
     // bounds it from below: skip the transcendental frame when kb0 cannot win (ties lose: last id)
     if (!((0.0 + tail) + head >= bd)) {
       double ph = kSinePuls * s + kSinePhase;
-      double r = (y - 7.25) - kSineAmp * mmm_sin(ph);
-      double lh = 0.0 + mmm_atan(kSineAmp * kSinePuls * mmm_cos(ph));
+      double sp, cp, lh;
+      if constexpr (SINE) {
+        // one reduction, both polynomials, no branch on the quadrant's parity (the compiler does not merge mmm_sin and
+        // mmm_cos of one argument by itself: each is an if / else over the two polynomials)
+        mmm_sincos(ph, &sp, &cp);
+        lh = 0.0 + mmm_atan_small(kSineAmp * kSinePuls * cp);
+      } else {
+        sp = mmm_sin(ph); cp = mmm_cos(ph);
+        lh = 0.0 + mmm_atan(kSineAmp * kSinePuls * cp);
+      }
+      double r = (y - 7.25) - kSineAmp * sp;
       double d = fabs(r) + tail + head + 1.0 * fabs(wrap_to_pi(h - lh));
       if (d < bd) { bd = d; best = MM_LANE_KB0; }
     }
@@ -172,12 +190,13 @@ MM_DEV double index_to_speed(int i) { return 10 + i * (30.0 - 10) / (5 - 1); }  
 // half_tan: 1/2 tan of the returned (clipped) angle -- what the bicycle step needs of it (beta = atan(1/2 tan delta)).  The
 // command is an arcsine, so sin / cos of it are its argument and the square root asin already formed (or the constants at
 // the +-pi/3 limit): no second range reduction, no polynomials (device arithmetic, oracle math mode 1 alike)
+template <bool SINE = false>
 MM_DEV double steering_control(double x, double y, double heading, double speed, int tl, double &half_tan) {  // :146-187
   constexpr double KP_HEADING = 1 / kTauDs, KP_LATERAL = 1.0 / 3 * KP_HEADING, PURSUIT_TAU = 0.5 * kTauDs;
   double s, r;
   lane_local(tl, x, y, s, r);
   double lane_next = s + speed * PURSUIT_TAU;
-  double lfh = lane_heading_at(tl, lane_next);
+  double lfh = lane_heading_at<SINE>(tl, lane_next);
   double lat_cmd = -KP_LATERAL * r;
   double nz = not_zero(speed);
   double heading_command = mmm_asin(clipd(lat_cmd / nz, -1, 1));

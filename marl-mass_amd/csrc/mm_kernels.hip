@@ -317,12 +317,13 @@ MM_DEV double steer_vel_command(double steering_ref, double sang) { return 20 * 
 // st_t: 1/2 tan of the steering command (see steering_control; NaN: not known)
 // STEER = false (general kernels): the steering command is left to ONE steering_control call for CAVs and HDVs together,
 // after the HDVs have decided their target lanes (steer_lanes below); steering does not enter anything in between
+template <bool SINE = false>
 MM_DEV void steer_lane(Veh &v, bool sv, double &st_t) {
-  double steer = steering_control(v.x, v.y, v.h, v.v, v.tlane, st_t);
+  double steer = steering_control<SINE>(v.x, v.y, v.h, v.v, v.tlane, st_t);
   if (sv) { steer = steer_vel_command(steer, v.sang); st_t = __builtin_nan(""); }
   v.act_steer = clipd(steer, -kPi / 3, kPi / 3);
 }
-template <bool STEER = true>
+template <bool STEER = true, bool SINE = false>
 MM_DEV void controlled_act(Veh &v, int action, bool sv, double &st_t) {
   if (lane_after_end(v.tlane, v.x)) v.tlane = next_lane(v.tlane, v.x, v.y);  // follow_road :136-144
   if (action == 2 || action == 0) {
@@ -332,7 +333,7 @@ MM_DEV void controlled_act(Veh &v, int action, bool sv, double &st_t) {
     if (lane_reachable(cand, v.x, v.y)) v.tlane = cand;
   }
   v.act_acc = (1 / kTauA) * (v.tspeed - v.v);  // speed_control :189-197
-  if constexpr (STEER) steer_lane(v, sv, st_t);
+  if constexpr (STEER) steer_lane<SINE>(v, sv, st_t);
 }
 // The high-level act of a policy step: action_type.act -> MDPLCVehicle.act / MDPVehicle.act /
 // ControlledVehicle.act (safe_controller.py:63-66, controller.py:293-311, :90-125).  Road.act()
@@ -395,7 +396,7 @@ struct Cand {
 // sin(beta), cos(psi' + beta), cos(psi') and the three corner angles -- become ONE sincos of the steering angle and ONE of
 // the new heading plus angle sums; beta itself is never formed (include/mm_math.h, "angle-sum forms").
 // GENERAL: the instantiation can meet a steering angle that did not come out of steering_control (kernels with HDVs / steer_vel)
-template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true>
+template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false>
 MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double ch, double dt, bool sv = false) {
   Cand c;
   // "steer_vel" (safe_controller.py:124-150): the slip angle comes from the steering-angle STATE and the
@@ -418,7 +419,7 @@ MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double c
   c.h = v.h + (sv ? d_heading : d_heading * dt);
   mmm_sincos(c.h, &c.spsi, &c.cpsi);
   c.gvx = (KIND == MM_ENV_V1) ? mmm_cos_sum(c.spsi, c.cpsi, sb, cb) : 0.0;
-  c.lane = closest_lane(c.x, c.y, c.h);  // on_state_update kinematics.py:154-159
+  c.lane = closest_lane<SINE>(c.x, c.y, c.h);  // on_state_update kinematics.py:154-159
   c.pk = c.lane;
   if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
   return c;
@@ -1510,6 +1511,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   constexpr bool kSerialOnly = MIXED;
 #endif
 #endif
+  // kSine: the short forms of the sine lane's frame (mm_device.h, SINE), in the fused exact-mode CAV-only kernels of the
+  // power-of-two groups up to 8 lanes.  Elsewhere the shorter code costs registers that are not there -- the 6-lane exact
+  // kernels go from 0 to 2 spilled VGPRs (12 B of scratch) with mmm_atan_small alone -- and those instantiations keep the
+  // general forms: the same bits either way.
+  constexpr bool kSine = SHIELDED && !SPLIT && !MIXED && !IPM && !kSerialOnly && kPow2<G> && G <= 8;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   // power-of-two groups tile the launch seamlessly; 6- / 12-lane groups: 64 / G whole groups per wave, its last 4 lanes idle
@@ -1619,7 +1625,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if (time % c.nsub == 0) hl_act<KIND>(v, action);  // action_type.act abstract.py:516-519
     }
     const int tl_pre = v.tlane;  // what an HDV acting before this vehicle still sees
-    if (live && !hdv && head) controlled_act<!MIXED>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels: steering below)
+    if (live && !hdv && head) controlled_act<!MIXED, kSine>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels: steering below)
     if (head) s_cold[C_TSPEED][tid] = v.tspeed;
     if constexpr (MIXED) { STAMP(1); }  // (general kernels: "act" = the CAVs' part up to here; slots 3 / 4 / 5 split the HDVs' part)
     if constexpr (MIXED) {
@@ -1732,7 +1738,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     Cand cA;
     memset(&cA, 0, sizeof cA);
     const bool shield_on = SHIELDED && live && !hdv && v.hist_len >= 2;  // gate safe_controller.py:232-239
-    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv);
+    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv);
     auto park = [&](auto base_c, const Cand &cc, double steer) {  // a candidate's LDS image (shielded kernels only)
       constexpr int base = decltype(base_c)::value;
       if constexpr (SHIELDED) {
@@ -1754,9 +1760,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if constexpr (SHIELDED) {
         if (needB && !haveB) {
           double tB;
-          double steerB = steering_control(v.x, v.y, v.h, v.v, v.lane, tB);
+          double steerB = steering_control<kSine>(v.x, v.y, v.h, v.v, v.lane, tB);
           if (sv) steerB = steer_vel_command(steerB, v.sang);
-          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
+          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED, kSine>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
           haveB = true;
         }
       }
@@ -2409,7 +2415,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   const unsigned crashed_bits = group_ballot<G>(ctrl && v.crashed, gb);
   const bool done = env_ok && (crashed_bits != 0 || steps >= c.T ||
                                group_ballot<G>(ctrl_x && v.x < 0, gb) != 0);
-  const int nl = v.present ? next_lane(v.lane, v.x, v.y) : 0;
+  // (shielded kernels: the pose code already holds next_lane of this very pose -- pose_code at setup, cc.pk at every commit, and
+  // x, y and the lane have not changed since)
+  int nl = 0;
+  if constexpr (SHIELDED) nl = v.present ? (pk_self >> 3) & 7 : 0;
+  else nl = v.present ? next_lane(v.lane, v.x, v.y) : 0;
   // surrounding_vehicles lane sets (road.py:315-342), as bit sets over lane ids
   const unsigned allow_tbl[6] = {
       (1u << MM_LANE_AB0) | (1u << MM_LANE_BC0), (1u << MM_LANE_AB0) | (1u << MM_LANE_BC0) | (1u << MM_LANE_CD0),
