@@ -290,6 +290,7 @@ def test_six_and_twelve_lane_groups_equal_the_power_of_two_groups(env_id, safety
 
 
 def test_float32_obs_matches_float64():
+    """Exact mode, IDLE actions; the default mode under a lane-change tape: test_default_step_gpu.py."""
     kw = dict(env_id="merge-multi-agent-v1", config={"safety_guarantee": "cbf-cav", "HEADWAY_TIME": 0.5},
               cbf_eta=0.03125, qp_solver="exact", cbf_tau=0.5, seed=7)
     e32, e64 = _gpu_env(256, 8, **kw), _gpu_env(256, 8, obs_f64=True, **kw)
@@ -462,7 +463,7 @@ def test_metrics_accumulator():
 
 
 def test_deferred_metrics_match_per_step_folding():
-    """mm_defer_metrics: the per-wave partials accumulate across steps and reach the caller's 8 doubles only in
+    """mm_defer_metrics (exact mode; the default mode: test_default_step_gpu.py): the per-wave partials accumulate across steps and reach the caller's 8 doubles only in
     mm_flush_metrics / mm_poll_errors -- same totals as the per-step fold (sums up to reassociation, min and counts exactly),
     nothing visible before the flush, nothing counted twice by a second flush, and switching deferral off flushes."""
     kw = dict(env_id="merge-multi-agent-v1", config={"safety_guarantee": "cbf-cav", "HEADWAY_TIME": 0.5}, cbf_eta=0.03125, qp_solver="exact",
@@ -689,8 +690,8 @@ def _compat_replay(compat, z, meta):
 
 
 def test_skipped_outputs_on_gpu():
-    """VecMergeEnv(skip_outputs=...): NULL MMStepOut pointers are not written by the step kernel, everything else is
-    bit-identical to the full call (what bench.py's headline line requests)."""
+    """VecMergeEnv(skip_outputs=...): NULL MMStepOut pointers are not written by the exact-mode step kernel, everything else is
+    bit-identical to the full call (what bench.py's headline line requests).  The default mode: test_default_step_gpu.py."""
     kw = dict(env_id="merge-multi-agent-v1", config={"safety_guarantee": "cbf-cav", "HEADWAY_TIME": 0.5}, cbf_eta=0.03125, qp_solver="exact", cbf_tau=0.5,
               seed=5, auto_reset=True)
     full, lean = _gpu_env(512, 8, **kw), _gpu_env(512, 8, skip_outputs=("agents_info", "action_mask", "crashed"), **kw)

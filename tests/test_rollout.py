@@ -70,7 +70,8 @@ def test_interact_on_gpu():
 
 @pytest.mark.gpu
 def test_graph_captured_rollout_equals_eager():
-    """use_graph: the whole rollout replayed as one hipGraph gives the same tensors as the eager loop
+    """use_graph (exact mode: one step launch per env step; the split default mode: test_default_step_gpu.py): the whole
+    rollout replayed as one hipGraph gives the same tensors as the eager loop
     (a greedy policy makes the comparison independent of the RNG stream), twice in a row."""
     import time
     from marl_mass_amd import VecMergeEnv
@@ -345,7 +346,7 @@ def test_evaluate_refuses_an_env_without_the_outputs_it_reads():
 
 
 def test_step_writes_requested_outputs_into_caller_slots():
-    """step(out={key: tensor}): that step writes those outputs into the caller's tensors (a rollout's rewards[t], dones[t],
+    """step(out={key: tensor}) (oracle backend, exact mode; the HIP default mode: test_default_step_gpu.py): that step writes those outputs into the caller's tensors (a rollout's rewards[t], dones[t],
     ...) and nowhere else; everything else -- state, the other outputs, later steps -- is what a twin without slots gives."""
     kw = dict(env_id="merge-multi-agent-v1", config={"safety_guarantee": "cbf-cav", "HEADWAY_TIME": 0.5}, cbf_eta=0.03125, qp_solver="exact",
               cbf_tau=0.5, seed=4, auto_reset=True)

@@ -98,7 +98,7 @@ import pytest  # noqa: E402
 @pytest.mark.gpu
 def test_two_rank_shards_equal_single_batch_hip(tmp_path):
     """The N > 1 path on the product backend: two rank processes (each with its own library handle, shard and
-    `first_env`), metric all-reduce, against one process holding the whole batch -- every bit of state, and the metrics."""
+    `first_env`), exact mode, metric all-reduce, against one process holding the whole batch -- every bit of state, and the metrics."""
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -131,7 +131,8 @@ def test_shard_range_covers_batch():
 
 
 def test_checkpoint_resume_is_bit_identical():
-    """state_dict / load_state_dict of an env batch (oracle backend): resume reproduces the continuation."""
+    """state_dict / load_state_dict of an env batch (oracle backend, exact mode): resume reproduces the continuation.
+    The default mode, on the oracle and on the HIP backend: test_default_step_host.py / test_default_step_gpu.py."""
     import torch
     import oracle_env
     kw = dict(env_id="merge-multi-agent-v1", config={"safety_guarantee": "cbf-cav", "HEADWAY_TIME": 0.5}, cbf_eta=0.03125, qp_solver="exact",
