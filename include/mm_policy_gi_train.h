@@ -64,7 +64,8 @@ int32_t mm_policy_gi_train_scratch_bytes(int64_t n, uint64_t *bytes);
  * scratch: DEV, scratch_bytes >= mm_policy_gi_train_scratch_bytes(n), 16-byte aligned; contents are undefined afterwards.
  * n == 0 or no valid sample: gradients and losses are written as zeros.  n is limited to 2^31 - 1 (B is a 32-bit count).
  * The scratch is 2 496 bytes per sample plus up to 56 MB of partial blocks and is not chunked: 1.27 GiB at 524 288 samples;
- * a caller with more samples than it can afford scratch for splits the batch itself (one optimiser step per part).
+ * a caller with more samples than it can afford scratch for uses mm_policy_gi_train_chunked below (the same gradient of ONE
+ * loss over all n samples, in passes through the rows of `chunk` samples).
  * MM_ERR_INVALID_ARG: a NULL input, weight or output pointer, n < 0, n_s outside 25..32, obs_stride < n_s, hidden != 128,
  *   n > 2^31 - 1, n_a outside 1..8, critic_loss not one of the two, clip_param < 0, scratch NULL / too small / misaligned.
  */
@@ -73,6 +74,35 @@ int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int64_t n, int3
                            const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a, float clip_param,
                            int32_t critic_loss, const float *adv_sums, const MMGiParams *grads, float *loss, float *logp_taken,
                            float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream);
+
+/*
+ * The same call under a fixed scratch budget (marl-mass_amd/csrc/mm_policy_chunked.hip).  Kernels A and B run over the batch
+ * in passes of `chunk` samples through one set of per-sample rows; each pass's partial blocks are added, in workgroup order and
+ * in fp64, to one accumulator block, and gradients and losses are written once at the end.  They mean what they mean above:
+ * the gradient of ONE loss over all n samples, B the number of valid samples of the whole batch.  Deterministic, no
+ * floating-point atomics, only enqueues on `stream` (1 + 3 launches per pass + 1, and two memsets): graph-capturable.
+ *
+ * chunk: samples per pass, a positive multiple of 64 (every pass but the last is whole 32-sample tiles, and a slice of kernel B
+ * keeps its 2 tiles).  Every other argument is mm_policy_gi_train's.
+ * Scratch (mm_policy_gi_train_chunked_scratch_bytes(n, chunk), 16-byte aligned): the header and the W2^T fragments as above,
+ * the per-sample rows of `chunk` samples (2 496 bytes each), the fp64 loss partials of all ceil(n / 32) tiles (16 bytes each),
+ * the partial blocks of one pass (one per 2 tiles up to 1024 tiles, 512 above: up to 56 MB) and one accumulator block
+ * double[27 952].  At chunk 524 288 that is 1.27 GiB + 0.5 MB per million samples, whatever n.
+ *
+ * A gradient element is float(the fp64 running sum of all partial blocks of all passes, in pass and workgroup order), which is
+ * what the unchunked fold computes over its one pass.  So with chunk >= n the results are bit-identical to mm_policy_gi_train;
+ * for any chunk the losses and the diagnostics are (same tiles, same B, same loss tree), and the gradients differ from it only
+ * through the float32 rounding of a different slicing of the sample sum.
+ * MM_ERR_INVALID_ARG: as mm_policy_gi_train, and chunk <= 0 or not a multiple of 64.  A refused call enqueues nothing.
+ */
+int32_t mm_policy_gi_train_chunked_scratch_bytes(int64_t n, int64_t chunk, uint64_t *bytes);
+
+int32_t mm_policy_gi_train_chunked(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                   int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                   const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a, float clip_param,
+                                   int32_t critic_loss, const float *adv_sums, const MMGiParams *grads, float *loss,
+                                   float *logp_taken, float *value, float *ratio, void *scratch, uint64_t scratch_bytes,
+                                   MMStream stream, int64_t chunk);
 
 #ifdef __cplusplus
 }

@@ -83,8 +83,9 @@ int32_t mm_policy_train_scratch_bytes(int64_t n, uint64_t *bytes);
  * scratch: DEV, scratch_bytes >= mm_policy_train_scratch_bytes(n), 16-byte aligned; contents are undefined afterwards.
  * n == 0 or no valid sample: gradients and losses are written as zeros (n == 0: the per-sample inputs, adv_sums and
  * advantages are not looked at and may be NULL).  n is limited to 2^31 - 1 (B is a 32-bit count).
- * The scratch is not chunked: 1.17 GiB at 524 288 samples; a caller with more samples than it can afford scratch for splits
- * the batch itself (one optimiser step per part).
+ * The scratch is not chunked: 1.17 GiB at 524 288 samples; a caller with more samples than it can afford scratch for uses
+ * mm_policy_train_chunked below (the same gradients of ONE loss per network over all n samples, in passes through the rows of
+ * `chunk` samples).
  * MM_ERR_INVALID_ARG: no network at all, a network without gradients or the reverse, a NULL pointer among a given network's
  *   six, a NULL input the given networks read, loss NULL, n < 0, n > 2^31 - 1, n_s outside 25..32, obs_stride < n_s,
  *   hidden != 128, n_a outside 1..8, critic_loss not one of the two, clip_param < 0, with an actor both or neither of
@@ -96,6 +97,33 @@ int32_t mm_policy_train(const float *obs, int64_t obs_stride, int64_t n, int32_t
                         int32_t critic_loss, const float *adv_sums, const float *advantages, const MMMlpParams *actor_grads,
                         const MMMlpParams *critic_grads, float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
                         uint64_t scratch_bytes, MMStream stream);
+
+/*
+ * The same call under a fixed scratch budget (marl-mass_amd/csrc/mm_policy_chunked.hip), as mm_policy_gi_train_chunked
+ * (include/mm_policy_gi_train.h) is to mm_policy_gi_train.  Kernels A and B run over the batch in passes of `chunk` samples,
+ * the actor's pass and the critic's alternating over the same rows; each pass's partial blocks are added, in workgroup order and
+ * in fp64, to the network's own accumulator block, and gradients and losses are written once at the end: the gradient of ONE
+ * loss per network over all n samples, B the number of valid samples of the whole batch.  Deterministic, no floating-point
+ * atomics, only enqueues on `stream`: graph-capturable.
+ *
+ * chunk: samples per pass, a positive multiple of 64.  Every other argument is mm_policy_train's.
+ * Scratch (mm_policy_train_chunked_scratch_bytes(n, chunk), 16-byte aligned): the header and both networks' fragments as above,
+ * the per-sample rows of `chunk` samples (2 240 bytes each), the fp64 loss partials of all ceil(n / 32) tiles (8 bytes per tile
+ * and network: both networks' are folded at the end), the partial blocks of one pass (one per 2 tiles up to 1024 tiles, 512
+ * above: up to 55 MB) and two accumulator blocks double[26 896].
+ *
+ * With chunk >= n the results are bit-identical to mm_policy_train; for any chunk the losses and the diagnostics are, and the
+ * gradients differ from it only through the float32 rounding of a different slicing of the sample sum.
+ * MM_ERR_INVALID_ARG: as mm_policy_train, and chunk <= 0 or not a multiple of 64.  A refused call enqueues nothing.
+ */
+int32_t mm_policy_train_chunked_scratch_bytes(int64_t n, int64_t chunk, uint64_t *bytes);
+
+int32_t mm_policy_train_chunked(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden, int32_t n_a,
+                                float clip_param, int32_t critic_loss, const float *adv_sums, const float *advantages,
+                                const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, float *logp_taken,
+                                float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk);
 
 #ifdef __cplusplus
 }

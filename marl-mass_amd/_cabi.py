@@ -324,6 +324,20 @@ class CLib(object):
             lib.mm_policy_train.argtypes = [vp, i64, i64, i32, vp, i64, vp, i64, vp, vp, pp, pp, i32, i32, f32, i32, vp, vp, pp, pp,
                                             vp, vp, vp, vp, vp, u64, vp]
             lib.mm_policy_train.restype = i32
+        # both gradient entries in passes of `chunk` samples under a fixed scratch budget (the same two headers): the
+        # unchunked entry's arguments and the chunk
+        self.has_policy_gi_train_chunked = self.has_policy_gi_train and hasattr(lib, "mm_policy_gi_train_chunked")
+        if self.has_policy_gi_train_chunked:
+            lib.mm_policy_gi_train_chunked_scratch_bytes.argtypes = [i64, i64, C.POINTER(u64)]
+            lib.mm_policy_gi_train_chunked_scratch_bytes.restype = i32
+            lib.mm_policy_gi_train_chunked.argtypes = list(lib.mm_policy_gi_train.argtypes) + [i64]
+            lib.mm_policy_gi_train_chunked.restype = i32
+        self.has_policy_train_chunked = self.has_policy_train and hasattr(lib, "mm_policy_train_chunked")
+        if self.has_policy_train_chunked:
+            lib.mm_policy_train_chunked_scratch_bytes.argtypes = [i64, i64, C.POINTER(u64)]
+            lib.mm_policy_train_chunked_scratch_bytes.restype = i32
+            lib.mm_policy_train_chunked.argtypes = list(lib.mm_policy_train.argtypes) + [i64]
+            lib.mm_policy_train_chunked.restype = i32
         # clip_grad_norm_ + RMSprop / Adam + soft target update in one launch (include/mm_opt_step.h), also libmm_hip.so only
         self.has_opt_step = hasattr(lib, "mm_opt_step")
         if self.has_opt_step:
@@ -373,6 +387,18 @@ class CLib(object):
         self.check(self.lib.mm_policy_gi_train_scratch_bytes(n, C.byref(b)))
         return b.value
 
+    def require_policy_gi_train_chunked(self):
+        if not self.has_policy_gi_train_chunked:
+            raise NotImplementedError("%s does not export mm_policy_gi_train_chunked: the shared actor-critic's gradient under a "
+                                      "scratch budget needs the HIP library" % os.path.basename(self.path))
+
+    def policy_gi_train_chunked_scratch_bytes(self, n, chunk):
+        """Bytes of scratch mm_policy_gi_train_chunked needs for n samples in passes of chunk (include/mm_policy_gi_train.h)."""
+        self.require_policy_gi_train_chunked()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_gi_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
+        return b.value
+
     def require_policy_train(self):
         if not self.has_policy_train:
             raise NotImplementedError("%s does not export mm_policy_train: the separate actor's and critic's gradients need the "
@@ -383,6 +409,18 @@ class CLib(object):
         self.require_policy_train()
         b = C.c_uint64()
         self.check(self.lib.mm_policy_train_scratch_bytes(n, C.byref(b)))
+        return b.value
+
+    def require_policy_train_chunked(self):
+        if not self.has_policy_train_chunked:
+            raise NotImplementedError("%s does not export mm_policy_train_chunked: the separate actor's and critic's gradients "
+                                      "under a scratch budget need the HIP library" % os.path.basename(self.path))
+
+    def policy_train_chunked_scratch_bytes(self, n, chunk):
+        """Bytes of scratch mm_policy_train_chunked needs for n samples in passes of chunk (include/mm_policy_train.h)."""
+        self.require_policy_train_chunked()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
         return b.value
 
     def require_opt_step(self):

@@ -21,6 +21,7 @@
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
 #include "mm_policy_mfma.h"
 #include "../../include/mm_policy_gi_train.h"
+#include "mm_policy_chunked.h"
 
 namespace mm {
 namespace gi_train {
@@ -367,3 +368,30 @@ extern "C" int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int6
                      G, (const double *)(sc + L.lossp), L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
+
+// ---- host-side launch helpers of the chunked entry (mm_policy_chunked.hip, declared in mm_policy_chunked.h): the same launches
+// as above on the samples and rows the caller points at
+namespace mm {
+namespace gi_train {
+
+mfma::Layout layout_of(long long n) { return layout(n); }
+
+void launch_prep(hipStream_t s, const float *W2, float4 *frag, const uint8_t *valid, long long n, int *count) {
+  hipLaunchKernelGGL(gi_train_prep_kernel, dim3(5 * 4 * 4 * 64 / 256), dim3(256), 0, s, W2, frag, valid, n, count);
+}
+
+void launch_sample(hipStream_t s, const PassArgs &p) {
+  const unsigned gridA = persistent_grid((p.n + 31) / 32, kThreadsA / 64);
+  hipLaunchKernelGGL(policy_gi_train_sample_kernel, dim3(gridA), dim3(kThreadsA), 0, s, p.obs, p.obs_stride, p.n, p.actions,
+                     p.act_stride, p.returns, p.ret_stride, p.old_logp, p.valid, p.w, p.n_a, p.clip_param, p.huber, p.adv_sums,
+                     p.count, p.frag, p.rows.h1, p.rows.dz1, p.rows.h2, p.rows.dz2, p.rows.dh, p.rows.xs, p.lossp, p.logp_out,
+                     p.value_out, p.ratio_out);
+}
+
+void launch_wgrad(hipStream_t s, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
+  hipLaunchKernelGGL(policy_gi_train_wgrad_kernel, dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs, n_pad,
+                     slice_rows, part);
+}
+
+}  // namespace gi_train
+}  // namespace mm

@@ -30,6 +30,7 @@
 // The actor's three kernels run first, then the critic's over the same scratch (stream order).
 #include "mm_policy_mfma.h"
 #include "../../include/mm_policy_train.h"
+#include "mm_policy_chunked.h"
 
 namespace mm {
 namespace pt {
@@ -449,3 +450,42 @@ extern "C" int32_t mm_policy_train(const float *obs, int64_t obs_stride, int64_t
   }
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
+
+// ---- host-side launch helpers of the chunked entry (mm_policy_chunked.hip, declared in mm_policy_chunked.h): the same launches
+// as above on the samples and rows the caller points at
+namespace mm {
+namespace pt {
+
+mfma::Layout layout_of(long long n) { return layout(n); }
+
+long long critic_frag_offset() { return kFrag; }
+
+void launch_prep(hipStream_t s, const float *W2a, const float *W2c, int k2c, float4 *frag, const uint8_t *valid, long long n,
+                 int *count) {
+  hipLaunchKernelGGL(policy_train_prep_kernel, dim3(2 * 4096 / 256), dim3(256), 0, s, W2a, W2c, k2c, frag, valid, n, count);
+}
+
+void launch_sample(hipStream_t s, bool critic, const PassArgs &p) {
+  SampleArgs a = {};
+  a.obs = p.obs; a.obs_stride = p.obs_stride; a.n = p.n; a.n_s = p.n_s; a.actions = p.actions; a.act_stride = p.act_stride;
+  a.returns = p.returns; a.ret_stride = p.ret_stride; a.old_logp = p.old_logp; a.valid = p.valid; a.w = p.w; a.n_a = p.n_a;
+  a.clip_param = p.clip_param; a.huber = p.huber; a.adv_sums = p.adv_sums; a.advantages = p.advantages; a.count = p.count;
+  a.frag = p.frag;
+  a.s_h1 = p.rows.h1; a.s_dz1 = p.rows.dz1; a.s_h2 = p.rows.h2; a.s_dz2 = p.rows.dz2; a.s_dh = p.rows.dh; a.s_xs = p.rows.xs;
+  a.lossp = p.lossp; a.out0 = p.out0; a.out1 = p.out1;
+  const unsigned grid = grid_a((p.n + 31) / 32);
+  if (critic) hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+  else hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+}
+
+void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
+  if (critic)
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
+                       n_pad, slice_rows, part);
+  else
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
+                       n_pad, slice_rows, part);
+}
+
+}  // namespace pt
+}  // namespace mm

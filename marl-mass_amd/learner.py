@@ -20,6 +20,11 @@ shape [B, 1], so `ratio * advantages` broadcasts to [B, B]: every sample's ratio
 non-negative / negative advantages.  `form="reference"` computes exactly that (it is what the reference's checkpoints were
 trained with, and tests/golden/gi_train_*.npz pin it to the reference's own run); `form="flat"` is textbook per-sample
 PPO-clip on all B * N samples in one optimiser step.
+
+The gradient kernels keep 2 496 B (shared network) / 2 240 B (separate networks) of scratch per sample.  With
+`scratch_budget_bytes` a learner never holds more than that: a call whose unchunked scratch does not fit takes the same
+gradient of ONE loss over all its samples with `mm_policy_gi_train_chunked` / `mm_policy_train_chunked`, in passes through
+the rows of the largest chunk that fits -- still one optimiser step, the same losses bit for bit.
 """
 import copy
 import ctypes as C
@@ -220,10 +225,46 @@ class _DeviceLearner(object):
             target.load_state_dict(sd)
 
     def _ensure_scratch(self, n):
-        need = self._scratch_bytes(n)
+        return self._grow(self._scratch_bytes(n))
+
+    def _grow(self, need):
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
         return self._scratch
+
+    def _init_budget(self, scratch_budget_bytes, require_chunked, chunked_bytes):
+        """scratch_budget_bytes None: the unchunked entry, whatever it needs.  A budget: the scratch never exceeds it -- the
+        unchunked entry where its scratch fits, else the chunked one (`chunked_bytes`: its size query, (n, chunk) -> bytes)
+        with the largest chunk that fits.  ValueError for a budget below the smallest pass, 64 samples."""
+        self.scratch_budget_bytes = None if scratch_budget_bytes is None else int(scratch_budget_bytes)
+        self._chunked_bytes, self._chunks = chunked_bytes, {}
+        if self.scratch_budget_bytes is not None:
+            require_chunked()
+            least = chunked_bytes(64, 64)
+            if self.scratch_budget_bytes < least:
+                raise ValueError("scratch_budget_bytes=%d is below the %d bytes of the smallest pass (64 samples)"
+                                 % (self.scratch_budget_bytes, least))
+
+    def _plan(self, n):
+        """(chunk, scratch) of a gradient call on n samples: chunk None for the unchunked entry."""
+        budget = self.scratch_budget_bytes
+        if budget is None:
+            return None, self._ensure_scratch(n)
+        if n not in self._chunks:
+            need = self._scratch_bytes(n)
+            if need <= budget:
+                self._chunks[n] = (None, need)
+            else:
+                if self._chunked_bytes(n, 64) > budget:
+                    raise ValueError("scratch_budget_bytes=%d is below the %d bytes %d samples need in passes of 64"
+                                     % (budget, self._chunked_bytes(n, 64), n))
+                lo, hi = 1, (n + 63) // 64  # the size grows with the chunk: the largest multiple of 64 that fits
+                while lo < hi:
+                    mid = (lo + hi + 1) // 2
+                    lo, hi = (mid, hi) if self._chunked_bytes(n, 64 * mid) <= budget else (lo, mid - 1)
+                self._chunks[n] = (64 * lo, self._chunked_bytes(n, 64 * lo))
+        chunk, need = self._chunks[n]
+        return chunk, self._grow(need)
 
 
 class SharedPPOLearner(_DeviceLearner):
@@ -232,7 +273,9 @@ class SharedPPOLearner(_DeviceLearner):
     float32, on the device -- typically the module a DeviceRollout acts with, so the next rollout uses the updated weights."""
 
     def __init__(self, policy, clib, lr=1e-4, optimizer_type="rmsprop", clip_param=0.2, critic_loss="mse", max_grad_norm=0.5,
-                 target_tau=1.0, target_update_steps=5, fused_step=False):
+                 target_tau=1.0, target_update_steps=5, fused_step=False, scratch_budget_bytes=None):
+        # (first: a budget no call can meet is refused whatever else is passed)
+        self._init_budget(scratch_budget_bytes, clib.require_policy_gi_train_chunked, clib.policy_gi_train_chunked_scratch_bytes)
         if type(policy) is not ActorCriticNetwork or not policy.state_split or policy.fc2.weight.shape[0] != 128:
             raise ValueError("SharedPPOLearner needs rollout.ActorCriticNetwork(state_split=True) with hidden size 128")
         p0 = policy.fc2.weight
@@ -295,7 +338,9 @@ class SharedPPOLearner(_DeviceLearner):
         the float32 [3] tensor (actor loss, critic loss, their sum); with diagnostics also (logp_taken, value, ratio) [n].
         obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns float32 [n] (any stride),
         old_logp float32 [n], valid uint8 / bool [n] or None.  adv_sums: float32 [2] (S+, S-) for the reference's [B, B]
-        objective, None for per-sample PPO-clip (see the module docstring).  Only enqueues work: no host synchronisation."""
+        objective, None for per-sample PPO-clip (see the module docstring).  Only enqueues work: no host synchronisation.
+        With a scratch budget that the unchunked call's scratch exceeds, the same gradient comes from
+        mm_policy_gi_train_chunked in passes of the largest chunk that fits."""
         n, S = obs.shape
         if obs.dtype != torch.float32 or (n and obs.stride(1) != 1):
             raise ValueError("obs must be float32 [n, S] with contiguous rows")
@@ -315,13 +360,17 @@ class SharedPPOLearner(_DeviceLearner):
             setattr(G, name, p.grad.data_ptr())
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
         diag = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3)] if diagnostics else [None] * 3
-        scratch = self._ensure_scratch(n)
+        chunk, scratch = self._plan(n)
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self.clib.check(self.clib.lib.mm_policy_gi_train(
+        args = (
             obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
             returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), C.byref(W), self.policy.fc2.weight.shape[0], self.n_a,
             self.clip_param, abi.GI_CRITIC_LOSS[self.critic_loss], opt(adv_sums), C.byref(G), loss.data_ptr(), opt(diag[0]),
-            opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream()))
+            opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream())
+        if chunk is None:
+            self.clib.check(self.clib.lib.mm_policy_gi_train(*args))
+        else:
+            self.clib.check(self.clib.lib.mm_policy_gi_train_chunked(*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
 
     # -- MAPPO_GI.train() ----------------------------------------------------------------------
@@ -396,7 +445,8 @@ class PPOLearner(_DeviceLearner):
 
     def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
-                 soft_update_every="train"):
+                 soft_update_every="train", scratch_budget_bytes=None):
+        self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
         if soft_update_every not in ("train", "agent_step"):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
@@ -492,7 +542,8 @@ class PPOLearner(_DeviceLearner):
         float32 [n] (any stride), old_logp float32 [n], valid uint8 / bool [n] or None.  Exactly one of adv_sums -- float32
         [2] (S+, S-): the reference's [B, B] objective -- and advantages -- float32 [n]: per-sample PPO-clip.  networks
         "both" | "actor" | "critic": the other one's gradient and loss are left out (its .grad is not touched, its loss is 0).
-        Only enqueues work: no host synchronisation."""
+        Only enqueues work: no host synchronisation.  With a scratch budget that the unchunked call's scratch exceeds, the
+        same gradients come from mm_policy_train_chunked in passes of the largest chunk that fits."""
         n, S = self._check_batch(obs, actions)
         if networks not in ("both", "actor", "critic"):
             raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
@@ -514,13 +565,17 @@ class PPOLearner(_DeviceLearner):
         loss = torch.empty(2, dtype=torch.float32, device=self.device)
         new = lambda on: torch.empty(n, dtype=torch.float32, device=self.device) if (diagnostics and on) else None  # noqa: E731
         diag = [new(with_a), new(with_c), new(with_a)]
-        scratch = self._ensure_scratch(n)
+        chunk, scratch = self._plan(n)
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self.clib.check(self.clib.lib.mm_policy_train(
+        args = (
             obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
             returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), 128, self.n_a, self.clip_param,
             abi.PT_CRITIC_LOSS[self.critic_loss], opt(adv_sums) if with_a else None, opt(advantages) if with_a else None, ref(G[0]),
-            ref(G[1]), loss.data_ptr(), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream()))
+            ref(G[1]), loss.data_ptr(), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream())
+        if chunk is None:
+            self.clib.check(self.clib.lib.mm_policy_train(*args))
+        else:
+            self.clib.check(self.clib.lib.mm_policy_train_chunked(*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
 
     # -- MAPPO.train() -------------------------------------------------------------------------
