@@ -95,6 +95,20 @@ struct SweepBuf {
 MM_DEV double &sw_f(const SweepBuf &sb, int f, int a, long long e) { return sb.F[((long long)f * sb.N + a) * sb.Ep + e]; }
 MM_DEV int &sw_i(const SweepBuf &sb, int f, int a, long long e) { return sb.I[((long long)f * sb.N + a) * sb.Ep + e]; }
 
+// Derived pose values carried from launch to launch (device memory owned by the handle, never the caller's; kCarry in
+// step_kernel).  A launch ends holding sin / cos of every vehicle's heading and its pose code; the next launch would form
+// the same three again from the same pose.  The planes keep them together with the KEY they were formed for -- the bits of
+// x, y and h, and in the code word the lane, the shield kind and a "written" mark -- and a lane takes them back only if
+// that key equals the state it loaded bit for bit.  The values are a pure function of the key, so whoever wrote the state
+// in between (mm_reset, mm_init_from_kinematics, a resumed batch, the caller itself, another kernel) can only cause a
+// mismatch, which runs the derivation.  Planes are [field][agent] like the state's: 5 doubles + 1 int = 44 B per agent.
+enum { PB_SIN, PB_COS, PB_KX, PB_KY, PB_KH, PB_F_COUNT };
+constexpr int kPoseWritten = 0x200;  // code word: pose code (bits 0..7) | MASS << 8 | this mark (a zeroed plane matches nothing)
+struct PoseBuf {
+  double *F;  // [PB_F_COUNT][A]
+  int *code;  // [A]
+};
+
 // Translation units.  The library is built from this one source compiled six times (Makefile):
 //   MM_TU=1  everything except the "general" step kernels (MIXED = true: HDVs and/or steer_vel),
 //   MM_TU=2  only those (round 1 built them with conservative SGPR spilling, DESIGN.md "toolchain note"; no longer),
@@ -1489,7 +1503,7 @@ template <int G, int KIND, int SHIELD, bool MIXED, bool IPM = false, bool TRACE 
 #define MM_STEP_BLOCK 64  // one wave per workgroup: waves of a 256-thread block drifted ~12 % apart and the block held its LDS until the slowest was done (0.355 -> 0.333 ms)
 #endif
 __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_waves<G, SHIELD, MIXED>(IPM))) void step_kernel(DevCfg c, DevState st, const int32_t *__restrict__ actions,
-                                                   MMStepOut out, double *metrics, SweepBuf sb, int kb) {
+                                                   MMStepOut out, double *metrics, SweepBuf sb, int kb, PoseBuf pb) {
   constexpr bool IDM = kIdm<KIND>;  // hdv-v1: IDMVehicleHist everywhere (log_step histories as in v1 mixed traffic)
   constexpr bool LC = (KIND == MM_ENV_V1) || IDM;
   constexpr bool SHIELDED = LC && (SHIELD != MM_SHIELD_NONE);
@@ -1516,6 +1530,12 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // kernels go from 0 to 2 spilled VGPRs (12 B of scratch) with mmm_atan_small alone -- and those instantiations keep the
   // general forms: the same bits either way.
   constexpr bool kSine = SHIELDED && !SPLIT && !MIXED && !IPM && !kSerialOnly && kPow2<G> && G <= 8;
+  // kCarry: sin / cos of the heading and the pose code come from the previous launch (PoseBuf) where their key matches the
+  // loaded state.  In the kSine kernels only: same register gate (-DMM_CARRY_POSE=0: A-B timing without it).
+#ifndef MM_CARRY_POSE
+#define MM_CARRY_POSE 1
+#endif
+  constexpr bool kCarry = kSine && MM_CARRY_POSE != 0;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   // power-of-two groups tile the launch seamlessly; 6- / 12-lane groups: 64 / G whole groups per wave, its last 4 lanes idle
@@ -1536,8 +1556,18 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #endif
   Veh v;
   const bool sv = MIXED && KIND == MM_ENV_V1 && c.steer_vel != 0;
-  load_veh(st, i, valid, v, sv);
   int steps = 0, time = 0, n_merge = 0, episode = 0;
+  int car_code = 0;
+  long long car_kx = 0, car_ky = 0, car_kh = 0;
+  double car_s = 0.0, car_c = 1.0;
+  if constexpr (kCarry) {
+    if (valid) {
+      car_kx = __double_as_longlong(pb.F[PB_KX * A + i]); car_ky = __double_as_longlong(pb.F[PB_KY * A + i]);
+      car_kh = __double_as_longlong(pb.F[PB_KH * A + i]);
+      car_s = pb.F[PB_SIN * A + i]; car_c = pb.F[PB_COS * A + i]; car_code = pb.code[i];
+    }
+  }
+  load_veh(st, i, valid, v, sv);
   if (e < st.E) {
     steps = st.I[MM_E_STEPS * st.E + e]; time = st.I[MM_E_TIME * st.E + e];
     // n_merge / episode are only needed by the epilogue: loaded there, not held across the sub-steps
@@ -1562,9 +1592,18 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // derived per-vehicle registers the shield keeps current across sub-steps
   double cpsi = 1.0, spsi = 0.0;  // cos / sin of my current heading (every kernel: the bicycle step is built on them)
   double st_t = __builtin_nan("");  // 1/2 tan(v.act_steer) once steering_control has produced it (NaN: not known -- an IDM action persisting from the last launch -- and predict() runs the general sincos)
-  if (v.present) mmm_sincos(v.h, &spsi, &cpsi);
   int pk_self = v.lane;  // pose code of my current (pre-step) pose
-  if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags(v.x, v.y, spsi, cpsi, v.lane) : 0);
+  bool carried = false;  // wave-uniform
+  if constexpr (kCarry) {
+    const bool hit = car_kx == __double_as_longlong(v.x) && car_ky == __double_as_longlong(v.y) && car_kh == __double_as_longlong(v.h) &&
+                     (car_code >> 8) == ((kPoseWritten >> 8) | (MASS ? 1 : 0)) && (car_code & 7) == v.lane;
+    carried = !__any(v.present && !hit);
+    if (carried && v.present) { spsi = car_s; cpsi = car_c; pk_self = car_code & 0xFF; }
+  }
+  if (!carried) {
+    if (v.present) mmm_sincos(v.h, &spsi, &cpsi);
+    if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags(v.x, v.y, spsi, cpsi, v.lane) : 0);
+  }
 
   // Register relief: lane-private values that are written once and read rarely live in LDS ("cold"
   // slots, one column per thread) instead of being spilled to scratch by the compiler (measured: each
@@ -2592,6 +2631,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   }
   STAMP(15);  // metrics
   // ---------------- optional re-spawn (marl/mappo.py:133-135 `if done: env.reset()`) --------------
+  if constexpr (kCarry) { car_s = spsi; car_c = cpsi; }  // what goes to the planes: the pose's own values (re-spawn: below)
   if (c.auto_reset && done) {
     const uint64_t seed = st.seeds[e];
     Veh nv;
@@ -2616,6 +2656,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     if (spawn) {
       v = nv;
       spsi = 0.0; cpsi = 1.0;  // heading 0
+      if constexpr (kCarry) {  // what the next launch would derive for the spawned pose, by the very calls it would make
+        mmm_sincos(v.h, &car_s, &car_c);
+        pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags(v.x, v.y, car_s, car_c, v.lane) : 0);
+      }
       s_cold[C_H1X][tid] = v.h1x; s_cold[C_H1VX][tid] = v.h1vx; s_cold[C_H2X][tid] = v.h2x; s_cold[C_H2VX][tid] = v.h2vx;
       s_cold[C_SSTEER][tid] = v.safe_steer; s_cold[C_SACC][tid] = v.safe_acc; s_cold[C_TSPEED][tid] = v.tspeed;
     }
@@ -2629,6 +2673,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     }
     v.tspeed = s_cold[C_TSPEED][tid];
     store_veh(st, i, v, sv);
+    if constexpr (kCarry) {
+      pb.F[PB_KX * A + i] = v.x; pb.F[PB_KY * A + i] = v.y; pb.F[PB_KH * A + i] = v.h;
+      pb.F[PB_SIN * A + i] = car_s; pb.F[PB_COS * A + i] = car_c;
+      pb.code[i] = (pk_self & 0xFF) | (MASS ? 0x100 : 0) | kPoseWritten;
+    }
   }
   if (e < st.E && a == 0) {
     st.I[MM_E_STEPS * st.E + e] = steps; st.I[MM_E_TIME * st.E + e] = time;
@@ -2909,6 +2958,10 @@ struct MMHandle_ : MMHandleHead {  // cfg, E, N, device, state, lay, first_env: 
   // configuration steps that way (shielded v1, qp_solver = MM_QP_IPM, CAV-only), never inside mm_step
   SweepBuf sweep;
   void *sweep_mem;
+  // derived pose values carried from launch to launch (PoseBuf): allocated by mm_create / mm_set_config for the shielded v1
+  // configurations, whose exact-mode CAV-only step kernels read and write them; never inside mm_step
+  PoseBuf pose;
+  void *pose_mem;
   int n_simd;  // SIMDs of the handle's device (4 per CU), read at mm_create
   char err[256];
 };
@@ -3019,6 +3072,23 @@ static hipError_t ensure_sweep(MMHandle_ *h) {
   return hipSuccess;
 }
 
+// device memory of the carried pose planes (idempotent; the caller holds a DeviceGuard).  Zeroed: no key of a zeroed plane
+// carries the "written" mark, so a fresh handle derives everything in its first step.
+static bool carries_pose(const MMHandle_ *h) { return h->cfg.env_kind == MM_ENV_V1 && h->cfg.shield != MM_SHIELD_NONE; }
+static hipError_t ensure_pose(MMHandle_ *h) {
+  if (h->pose_mem || !carries_pose(h)) return hipSuccess;
+  const uint64_t A = (uint64_t)h->E * (uint64_t)h->N;
+  const uint64_t bF = align256(A * 8u * PB_F_COUNT), bI = align256(A * 4u);
+  unsigned char *m = nullptr;
+  hipError_t rc = hipMalloc((void **)&m, bF + bI);
+  if (rc != hipSuccess) return rc;
+  rc = hipMemset(m, 0, bF + bI);
+  if (rc != hipSuccess) { (void)hipFree(m); return rc; }
+  h->pose_mem = m;
+  h->pose.F = (double *)m; h->pose.code = (int *)(m + bF);
+  return hipSuccess;
+}
+
 static thread_local char g_create_err[256] = "null handle";  // why the last mm_create of this thread refused (there is no handle to ask)
 void mm_set_thread_error(const char *text) { snprintf(g_create_err, sizeof g_create_err, "%s", text); }  // (mm_handle.h)
 // The host-side entries that touch the runtime outside a stream (allocation, latch poll, drain) must address the handle's
@@ -3067,7 +3137,13 @@ extern "C" int32_t mm_create(const MMConfig *cfg, int32_t E, int32_t N, int32_t 
   if (rc == hipSuccess) rc = hipMalloc((void **)&h->dev_err, MM_LW_COUNT * sizeof(int));
   if (rc == hipSuccess) rc = hipMemset(h->dev_err, 0, MM_LW_COUNT * sizeof(int));
   if (rc == hipSuccess) rc = ensure_sweep(h);
-  if (rc != hipSuccess) { if (h->dev_err) (void)hipFree(h->dev_err); free(h); return MM_ERR_DEVICE; }
+  if (rc == hipSuccess) rc = ensure_pose(h);
+  if (rc != hipSuccess) {
+    if (h->dev_err) (void)hipFree(h->dev_err);
+    if (h->sweep_mem) (void)hipFree(h->sweep_mem);
+    free(h);
+    return MM_ERR_DEVICE;
+  }
   *out = h;
   return MM_OK;
 }
@@ -3080,6 +3156,7 @@ extern "C" int32_t mm_destroy(MMHandle h) {
   if (h->dev_err) (void)hipFree(h->dev_err);
   if (h->metrics_partial) (void)hipFree(h->metrics_partial);
   if (h->sweep_mem) (void)hipFree(h->sweep_mem);
+  if (h->pose_mem) (void)hipFree(h->pose_mem);
   free(h);
   return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
@@ -3153,7 +3230,9 @@ extern "C" int32_t mm_set_config(MMHandle h, const MMConfig *cfg) {
   DeviceGuard dg(h->device);  // (the new configuration may step in the split form: its hand-off planes are allocated here)
   hipError_t hrc = dg.rc;
   if (hrc == hipSuccess) hrc = ensure_sweep(h);
-  return hrc == hipSuccess ? MM_OK : hip_fail(h, hrc, "hand-off planes of the split interior-point step");
+  if (hrc != hipSuccess) return hip_fail(h, hrc, "hand-off planes of the split interior-point step");
+  hrc = ensure_pose(h);
+  return hrc == hipSuccess ? MM_OK : hip_fail(h, hrc, "carried pose planes");
 }
 extern "C" int32_t mm_set_metrics_buffer(MMHandle h, double *metrics) {
   if (!h) return MM_ERR_INVALID_ARG;
@@ -3269,10 +3348,10 @@ static void launch_step_t(MMHandle h, const int32_t *actions, const MMStepOut *o
                                  : (unsigned)((h->E + 64 / G - 1) / (64 / G));  // rotation layouts: 64 / G whole groups per wave
   if (out->trace)
     hipLaunchKernelGGL((step_kernel<G, KIND, SHIELD, MIXED, IPM, true>), dim3(grid), dim3(MM_STEP_BLOCK), 0, s, dev_cfg(h), dev_state(h),
-                       actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0);
+                       actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0, h->pose);
   else
     hipLaunchKernelGGL((step_kernel<G, KIND, SHIELD, MIXED, IPM, false>), dim3(grid), dim3(MM_STEP_BLOCK), 0, s, dev_cfg(h), dev_state(h),
-                       actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0);
+                       actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0, h->pose);
 }
 #if MM_TU == 0 || MM_TU == 6 || MM_TU == 7
 // The split interior-point step (SweepBuf, sweep_kernel): nsub + 1 phase launches with a sweep launch after each act half.
@@ -3288,7 +3367,7 @@ static void launch_split_gs(MMHandle h, const int32_t *actions, const MMStepOut 
   constexpr bool MASS = SHIELD == MM_SHIELD_MASS;
   for (int kb = 0; kb <= dc.nsub; kb++) {
     hipLaunchKernelGGL((step_kernel<G, MM_ENV_V1, SHIELD, MIXED, true, true, true>), dim3(grid), dim3(MM_STEP_BLOCK), 0, s, dc, ds, actions,
-                       *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, kb);
+                       *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, kb, h->pose);
     if (kb == dc.nsub) break;
     // One sweep wave per SIMD is the design point (65 536 envs = 1 024 waves = the chip's SIMDs; the kernel is bound by the
     // latency of a lone wave).  Its LDS footprint would let a CU take five single-wave workgroups -- two of them on one SIMD
@@ -3476,6 +3555,9 @@ extern "C" int32_t mm_step(MMHandle h, const int32_t *actions, const MMStepOut *
   } else if (steps_split(h)) {  // interior-point mode, CAV-only: phase kernels + sweep kernels (SweepBuf)
     if (!h->sweep_mem) { snprintf(h->err, sizeof h->err, "mm_step: the hand-off planes of the split interior-point step are missing"); return MM_ERR_DEVICE; }
     mm_launch_step_split(h, step_group(h), actions, out, s);
+  } else if (carries_pose(h) && !h->pose_mem) {
+    snprintf(h->err, sizeof h->err, "mm_step: the carried pose planes are missing");
+    return MM_ERR_DEVICE;
   } else
 #ifdef MM_ONLY_G  // tuning builds: one group size, seconds to compile
   launch_step_g<MM_ONLY_G>(h, actions, out, s);
