@@ -355,6 +355,8 @@ const char *mm_last_error(MMHandle h);
  * softmax / cumsum round trips through HBM (24 B per agent in and out).
  * logp: DEV float[n][n_a] (n_a <= 8); counter: DEV uint64 (read by the launch, then incremented by one
  * on the stream, so hipGraph replays draw fresh numbers); actions: DEV int32[n].  Stateless.
+ * A -inf entry (a masked action) has probability 0 and is never drawn; rows need not be normalised.
+ * n = 0: MM_OK, nothing is enqueued and *counter stays as it is.
  */
 int32_t mm_sample_actions(const float *logp, int64_t n, int32_t n_a, uint64_t seed, uint64_t *counter,
                           int32_t *actions, MMStream stream);
@@ -365,7 +367,11 @@ int32_t mm_sample_actions(const float *logp, int64_t n, int32_t n_a, uint64_t se
  * observation rows mm_step wrote to the next actions.  HIP build: f32-input MFMA, activations kept in
  * registers (marl-mass_amd/csrc/mm_kernels.hip policy_kernel).  hidden must be 128 (the reference's only
  * value), n_s <= 32, n_a <= 8.  obs: DEV float[n][n_s]; logp: optional DEV float[n][n_a] (the log-softmax
- * the sample was drawn from); counter / actions as for mm_sample_actions.
+ * the sample was drawn from); counter / actions as for mm_sample_actions.  logp = (logit - max) - log(sum exp(logit - max)),
+ * torch's order: exp(logp) of a row sums to 1 within 1e-6 whatever the logits' size.
+ * n = 0: MM_OK, nothing is enqueued and *counter stays as it is.
+ * Observations must be finite.  Non-finite observations are outside the contract: fmaxf drops a NaN pre-activation where
+ * torch's relu keeps it.  (A non-finite row still reaches no other row's outputs.)
  */
 int32_t mm_policy_act(const float *obs, int64_t n, int32_t n_s, const float *W1, const float *b1, const float *W2,
                       const float *b2, const float *W3, const float *b3, int32_t hidden, int32_t n_a, uint64_t seed,

@@ -37,6 +37,10 @@ extern "C" {
  *   counter is neither read nor written (it may be NULL).
  * logp: optional DEV float[n][n_a] (the log-softmax the sample is drawn from); value: optional DEV float[n].
  * At least one of actions / logp / value must be given.  Only enqueues work on `stream`: graph-capturable.
+ * n = 0: MM_OK, nothing is enqueued and *counter stays as it is.
+ * Observations must be finite in the columns the split reads (0..24; columns 25..n_s-1 are never read).  Non-finite
+ *   observations are outside the contract: fmaxf drops a NaN pre-activation where torch's relu keeps it.  (A non-finite row
+ *   still reaches no other row's outputs.)
  * MM_ERR_INVALID_ARG: NULL weights, n < 0, n_s outside 25..32, hidden != 128, n_a outside 1..8, no output,
  *   actions without counter.
  */

@@ -3892,12 +3892,14 @@ __global__ __launch_bounds__(kPolThreads) void policy_kernel(const float *__rest
     float se = 0.0f;
 #pragma unroll
     for (int o = 0; o < 8; o++) se += (o < n_a) ? expf(logit[o] - mx) : 0.0f;
-    const float lse = mx + logf(se);
+    // log-softmax as (logit - mx) - log(sum), torch's order: logit - (mx + log(sum)) rounds the normaliser at ulp(mx) and
+    // shifts a whole row by up to ulp(max |logit|) / 2 (4e-6 at |logit| ~ 100: logsumexp(logp) is then no longer 0 to 1e-6)
+    const float lg = logf(se);
     if (live && h == 0) {
       double cdf[8], acc = 0;
 #pragma unroll
       for (int o = 0; o < 8; o++) {
-        const float lp = logit[o] - lse;
+        const float lp = (logit[o] - mx) - lg;
         if (o < n_a) {
           if (logp_out) logp_out[ag * n_a + o] = lp;
           acc = acc + mmm_exp((double)lp);

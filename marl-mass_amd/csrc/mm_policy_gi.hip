@@ -125,13 +125,13 @@ __global__ __launch_bounds__(kThreads) void policy_gi_kernel(
     float se = 0.0f;
 #pragma unroll
     for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
-    const float lse = mx + logf(se);
+    const float lg = logf(se);  // (logit - mx) - log(sum), as policy_kernel: the normaliser is not rounded at ulp(mx)
     if (live && h == 0) {
       if (value_out) value_out[ag] = v + sBh[8];
       double cdf[8], acc = 0;
 #pragma unroll
       for (int o = 0; o < 8; o++) {
-        const float lp = logit[o] - lse;
+        const float lp = (logit[o] - mx) - lg;
         if (o < n_a) {
           if (logp_out) logp_out[ag * n_a + o] = lp;
           acc = acc + mmm_exp((double)lp);

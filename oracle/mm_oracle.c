@@ -1986,8 +1986,8 @@ int32_t mm_policy_act(const float *obs, int64_t n, int32_t n_s, const float *W1,
     }
     float se = 0;
     for (int o = 0; o < n_a; o++) se += expf(lg[o] - mx);
-    const float lse = mx + logf(se);
-    for (int o = 0; o < n_a; o++) lp_all[i * n_a + o] = lg[o] - lse;
+    const float lns = logf(se); /* (logit - mx) - log(sum), the HIP kernel's order: the normaliser is not rounded at ulp(mx) */
+    for (int o = 0; o < n_a; o++) lp_all[i * n_a + o] = (lg[o] - mx) - lns;
   }
   int32_t rc = mm_sample_actions(lp_all, n, n_a, seed, counter, actions, stream);
   if (!logp) free(lp_all);

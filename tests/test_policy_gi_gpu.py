@@ -11,6 +11,7 @@ import torch
 
 from golden_util import GOLDEN
 from marl_mass_amd.rollout import ActorCriticNetwork, DeviceRollout
+from policy_act_util import sampler_u as _philox_u53  # the numpy Philox, pinned to known answers in test_policy_act_host.py
 
 pytestmark = pytest.mark.gpu
 
@@ -58,23 +59,6 @@ def _sample(logp, seed, counter):
     clib.check(clib.lib.mm_sample_actions(logp.contiguous().data_ptr(), n, n_a, seed, counter.data_ptr(), out.data_ptr(),
                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
-
-
-def _philox_u53(idx, ctr, seed):
-    """The sampler's uniform (mm_sample_actions): Philox4x32-10 on (agent, ctr, domain), key = seed; u53 of words 0, 1."""
-    M = np.uint64(0xFFFFFFFF)
-    c0 = (idx & M).astype(np.uint64); c1 = (idx >> np.uint64(32)).astype(np.uint64)
-    c2 = np.full_like(c0, ctr & 0xFFFFFFFF); c3 = np.full_like(c0, ((ctr >> 32) ^ 0x53414D50) & 0xFFFFFFFF)
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        n0 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0)
-        n2 = (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)
-        c0, c1, c2, c3 = n0 & M, p1 & M, n2 & M, p0 & M
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    a, b = c0, c1
-    return ((a >> np.uint64(5)).astype(np.float64) * 67108864.0 + (b >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
 
 
 @pytest.mark.parametrize("n", [31, 1000, 65536 * 8 + 13])
