@@ -303,6 +303,12 @@ class CLib(object):
         if self.has_policy_gi:
             lib.mm_policy_gi_act.argtypes = [vp, i64, i32] + [vp] * 12 + [i32, i32, u64, vp, vp, vp, vp, vp]
             lib.mm_policy_gi_act.restype = i32
+        # the hidden-512 actor + sample in one launch (include/mm_policy_wide.h: mm_policy_act's arguments), also
+        # libmm_hip.so only; mm_policy_act(hidden = 512) forwards to it
+        self.has_policy_wide = hasattr(lib, "mm_policy_wide_act")
+        if self.has_policy_wide:
+            lib.mm_policy_wide_act.argtypes = list(lib.mm_policy_act.argtypes)
+            lib.mm_policy_wide_act.restype = i32
         # the shared actor-critic's loss + parameter gradient (include/mm_policy_gi_train.h), also libmm_hip.so only
         self.has_policy_gi_train = hasattr(lib, "mm_policy_gi_train")
         if self.has_policy_gi_train:
@@ -373,6 +379,11 @@ class CLib(object):
     def require_policy_gi(self):
         if not self.has_policy_gi:
             raise NotImplementedError("%s does not export mm_policy_gi_act: the fused shared actor-critic needs the HIP library"
+                                      % os.path.basename(self.path))
+
+    def require_policy_wide(self):
+        if not self.has_policy_wide:
+            raise NotImplementedError("%s does not export mm_policy_wide_act: the fused hidden-512 actor needs the HIP library"
                                       % os.path.basename(self.path))
 
     def require_policy_gi_train(self):

@@ -31,6 +31,7 @@
 #include "mm_handle.h"
 #define MM_COUNTS_FN __host__ __device__ inline
 #include "../../include/mm_counts.h"
+#include "../../include/mm_policy_wide.h"  // mm_policy_act forwards hidden = 512 to it
 
 using namespace mm;
 
@@ -3922,6 +3923,8 @@ extern "C" int32_t mm_policy_act(const float *obs, int64_t n, int32_t n_s, const
                                  const float *b2, const float *W3, const float *b3, int32_t hidden, int32_t n_a, uint64_t seed,
                                  uint64_t *counter, int32_t *actions, float *logp, MMStream stream) {
   if (!obs || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !counter || !actions) return MM_ERR_INVALID_ARG;
+  if (hidden == 512)  // the reference's other actor size: its own kernel (mm_policy_wide.hip), the same contract
+    return mm_policy_wide_act(obs, n, n_s, W1, b1, W2, b2, W3, b3, hidden, n_a, seed, counter, actions, logp, stream);
   if (n < 0 || n_s < 1 || n_s > 32 || hidden != kPolHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
   if (n == 0) return MM_OK;
   hipStream_t s = (hipStream_t)stream;

@@ -16,7 +16,8 @@ bookkeeping) + bootstrap + discounting -- into one hipGraph on first use and rep
 (static output buffers; the env state, the carried observation and the RNG offset advance inside
 the graph exactly as they do eagerly).
 
-Networks mirror marl/single_agent/Model_common.py:5-41 (state -> 128 -> 128 -> n_a, log-softmax;
+Networks mirror marl/single_agent/Model_common.py:5-41 (state -> hidden -> hidden -> n_a, log-softmax, hidden 128 or, in the
+steer_vel configurations, 512: both have a fused act launch on the device;
 critic takes the one-hot action after the first layer) and, for MAPPO_GI with shared_network = True,
 marl/single_agent/Model_gi.py:137-216 (ActorCriticNetwork: split first layer, shared trunk, actor and
 critic heads; fused on the device as `mm_policy_gi_act`, include/mm_policy_gi.h).
@@ -147,7 +148,7 @@ class DeviceRollout(object):
         self.sample_seed = int(sample_seed) & 0xFFFFFFFFFFFFFFFF
         self.obs, _ = env.reset()
         self.obs = self.obs.clone()
-        # fused actor + sampling launch for the reference's ActorNetwork (hidden 128), and for its state-split
+        # fused actor + sampling launch for the reference's ActorNetwork (hidden 128 or 512), and for its state-split
         # ActorCriticNetwork (hidden 128) on the device; anything else goes through the module's own forward
         f32 = next(actor.parameters()).dtype == torch.float32
         if self.shared:
@@ -157,7 +158,11 @@ class DeviceRollout(object):
             if self.fused_policy:
                 env.clib.require_policy_gi()
         else:
-            self.fused_policy = bool(fused_policy) and type(actor) is ActorNetwork and actor.fc2.weight.shape[0] == 128 and f32
+            # hidden 128: mm_policy_act in both libraries.  hidden 512 (the steer_vel configurations): mm_policy_act forwards
+            # to mm_policy_wide_act, a HIP-library entry; on the CPU oracle such an actor goes through the module
+            hidden = actor.fc2.weight.shape[0] if type(actor) is ActorNetwork else 0
+            wide = hidden == 512 and self.obs.device.type == "cuda" and env.clib.has_policy_wide
+            self.fused_policy = bool(fused_policy) and type(actor) is ActorNetwork and f32 and (hidden == 128 or wide)
         self._sample_counter = torch.zeros(1, dtype=torch.int64, device=self.obs.device)  # advanced by mm_sample_actions
         self.use_graph = bool(use_graph)
         if self.use_graph:
