@@ -93,7 +93,11 @@ enum {
 #define MM_LATERAL_STEER_VEL 1
 #define MM_FLAG_COLLABORATE_ADJ 1u
 #define MM_FLAG_IS_LC_SAFE 2u  /* vehicle.is_lc_safe of the last shield call (decentral_layer.py:504,742).  The HIP step also reads it as the FIRST GUESS of
-                                  this sub-step's veto (a scheduling prior: results do not depend on it, tests/test_hip_parity.py) */
+                                  this sub-step's veto, and in the fused exact-mode CAV-only kernels of the 2- / 4- / 8-lane groups it thereby
+                                  selects the FIRST CANDIDATE the step predicts -- the veto's steering (to the current lane) where the flag is
+                                  clear and a lane change is under way, else the nominal one; the other candidate is evaluated only where it
+                                  is read (a scheduling prior: results do not depend on it, tests/test_hip_parity.py,
+                                  tests/test_candidate_prior_gpu.py) */
 #define MM_FLAG_IS_COLLABORATING 4u
 #define MM_HL_NONE 255u
 

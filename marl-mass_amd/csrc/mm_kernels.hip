@@ -142,10 +142,28 @@ __device__ unsigned long long g_stamps_s[4096 * 8];  // sweep kernel: per wave {
     if ((threadIdx.x & 63) == (k)) _t_acc += _t - _t_last;                               \
     _t_last = __builtin_amdgcn_s_memtime();                                              \
   } while (0)
+// Second-candidate evaluations of step_kernel by cause: lanes 16 .. 31 of a wave keep these in the same register, stored to
+// g_stamps_c and read with mm_debug_read_cand_stamps.  MM_CS_UPFRONT_CYCLES is a cycle stamp like the sixteen above; the
+// others count, by ballot at wave-uniform points, lanes (low word) and waves with at least one such lane (<< 32).
+enum { MM_CS_UPFRONT_CYCLES = 16,  // cycles between "predict A" and the veto passes: candidate B up front, from the prior
+       MM_CS_UPFRONT,              // cause (a): B evaluated up front, from the prior
+       MM_CS_LAZY_B,               // cause (b): B evaluated because a veto fired in a pass
+       MM_CS_FALLBACK,             // cause (c): the literal sweep's evaluation of whatever is missing
+       MM_CS_PRIOR_HELD,           // started the sub-step from the prior "vetoed", and the veto held
+       MM_CS_PRIOR_LIFTED,         // ... and the veto was lifted
+       MM_CS_LAZY_A,               // kPrimary: A evaluated because the veto of a first_B lane was lifted
+       MM_CS_FIRST_B };            // kPrimary: B is the main pass's candidate
+__device__ unsigned long long g_stamps_c[MM_STAMP_WAVES * 16];
+#define CAND_COUNT(k, cond)                                                                                  \
+  do {                                                                                                       \
+    const unsigned long long _m = __ballot(cond);                                                            \
+    if ((threadIdx.x & 63) == (k)) _t_acc += (unsigned long long)__popcll(_m) + (_m ? 1ull << 32 : 0ull);    \
+  } while (0)
 #else
 #define STAMP(k) do {} while (0)
 #define SSTAMP(k) do {} while (0)
 #define SCOUNT(k) do {} while (0)
+#define CAND_COUNT(k, cond) do {} while (0)
 #endif
 
 // merge-multi-agent-hdv-v1 (MergeEnvLCHDV, merge_env_v1.py:552-674): every vehicle an IDMVehicleHist, none controlled, every
@@ -1537,6 +1555,14 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #define MM_CARRY_POSE 1
 #endif
   constexpr bool kCarry = kSine && MM_CARRY_POSE != 0;
+  // kPrimary: the veto prior (kVetoPrior) also chooses which candidate the main pass predicts -- B, toward the current lane,
+  // for a vehicle whose lane change was vetoed a sub-step ago -- and the other one is evaluated where it is first read, if
+  // at all.  The same candidates with the same bits; only when they are computed changes.  In the kSine kernels without the
+  // trace: same register gate (-DMM_PRIMARY_PRIOR=0: A-B timing without it).
+#ifndef MM_PRIMARY_PRIOR
+#define MM_PRIMARY_PRIOR 1
+#endif
+  constexpr bool kPrimary = kSine && !TRACE && kVetoPrior && MM_PRIMARY_PRIOR != 0;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   // power-of-two groups tile the launch seamlessly; 6- / 12-lane groups: 64 / G whole groups per wave, its last 4 lanes idle
@@ -1665,7 +1691,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if (time % c.nsub == 0) hl_act<KIND>(v, action);  // action_type.act abstract.py:516-519
     }
     const int tl_pre = v.tlane;  // what an HDV acting before this vehicle still sees
-    if (live && !hdv && head) controlled_act<!MIXED, kSine>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels: steering below)
+    if (live && !hdv && head) controlled_act<!MIXED && !kPrimary, kSine>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels, kPrimary: steering below)
     if (head) s_cold[C_TSPEED][tid] = v.tspeed;
     if constexpr (MIXED) { STAMP(1); }  // (general kernels: "act" = the CAVs' part up to here; slots 3 / 4 / 5 split the HDVs' part)
     if constexpr (MIXED) {
@@ -1772,9 +1798,27 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if (head && live && (!hdv || !v.crashed)) steer_lane(v, sv && !hdv, st_t);
       if (head && hdv && live) v.gvx += dt;  // IDMVehicle.step: self.timer += dt (behavior.py:102-109)
     }
-    if (live && head) clip_actions(v, LC && !hdv, st_t);
+    // kPrimary: the candidate this lane predicts in the main pass is B where the veto prior says "vetoed" (first_B), else A.
+    // One steering_control + one predict for both kinds of lane: the target lane is a per-lane select, and so is the slot base.
+    // (shield_on and needB as defined below: the gate and "the veto's command can differ from the nominal one")
+    bool first_B = false;
+    if constexpr (kPrimary) {
+      static_assert(!MIXED && !SPLIT, "kPrimary: no HDVs, no steer_vel, every launch a whole step");
+      first_B = (c.debug_flags & 1) == 0 && live && v.hist_len >= 2 && (v.tlane != v.lane || v.crashed) && !(v.flags & MM_FLAG_IS_LC_SAFE);
+      if (live) {
+        // (the select is between a value and zero, not between two members of v: a select of their addresses keeps v in memory)
+        const int tl_1 = v.tlane + (first_B ? v.lane - v.tlane : 0);
+        const double steer = steering_control<kSine>(v.x, v.y, v.h, v.v, tl_1, st_t);
+        v.act_steer = clipd(steer, -kPi / 3, kPi / 3);
+        const double steer_1 = v.act_steer, st_t_1 = st_t;
+        clip_actions(v, LC, st_t);
+        if (first_B) { v.act_steer = steer_1; st_t = st_t_1; }  // (a crashed vehicle's steering is zeroed in candidate A only: B keeps its command)
+      }
+    } else {
+      if (live && head) clip_actions(v, LC && !hdv, st_t);
+    }
     STAMP(1);  // act
-    // predicted post-state for the nominal steering (the only one when nothing vetoes)
+    // predicted post-state for the nominal steering (the only one when nothing vetoes; kPrimary: for this lane's first candidate)
     Cand cA;
     memset(&cA, 0, sizeof cA);
     const bool shield_on = SHIELDED && live && !hdv && v.hist_len >= 2;  // gate safe_controller.py:232-239
@@ -1787,15 +1831,40 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         s_cold[base + 6][tid] = cc.gvx; s_cold[base + 7][tid] = cc.spsi;
       }
     };
-    if (head) park(std::integral_constant<int, C_A>{}, cA, v.act_steer);
+    auto park_at = [&](int base, const Cand &cc, double steer) {  // the same at a per-lane slot base (kPrimary)
+      s_cold[base + 0][tid] = cc.x; s_cold[base + 1][tid] = cc.y; s_cold[base + 2][tid] = cc.h;
+      cold_i(base + 3, tid) = cc.pk; s_cold[base + 4][tid] = cc.cpsi; s_cold[base + 5][tid] = steer;
+      s_cold[base + 6][tid] = cc.gvx; s_cold[base + 7][tid] = cc.spsi;
+    };
+    if constexpr (kPrimary) park_at(first_B ? (int)C_B : (int)C_A, cA, v.act_steer);
+    else if (head) park(std::integral_constant<int, C_A>{}, cA, v.act_steer);
     STAMP(2);  // predict A
     // LC veto re-steers to the CURRENT lane (decentral_layer.py:501-506,739-744); identical to the
     // nominal command unless a lane change / lane hand-over is under way or the car crashed.
-    // Candidate B is only predicted when a veto actually fires (lazily, below).
+    // Candidate B is only predicted when a veto actually fires (lazily, below), or up front where the veto prior says so.
     // ("steer_vel": the veto's velocity command is not clipped to +-pi/3 like the nominal one, so it can
     // differ even without a lane change)
     const bool needB = SHIELDED && shield_on && (v.tlane != v.lane || v.crashed || sv);
-    bool haveB = false;
+    bool haveB = first_B, haveA = !first_B;  // (haveA: kPrimary only -- everywhere else A is the main pass's)
+    (void)haveA;
+    // kPrimary: the candidate a lane does not have yet, evaluated where it is first read -- B after a veto fired, A after the
+    // veto of a first_B lane was lifted, both for the literal sweep -- and parked in its own slots.  One call site for both.
+    auto make_other = [&]() {
+      if constexpr (kPrimary) {
+        const bool mk_A = !haveA;  // (a lane has at least one of the two)
+        if (mk_A || (needB && !haveB)) {
+          double t_o;
+          const int tl_o = v.lane + (mk_A ? v.tlane - v.lane : 0);  // (as in the main pass: no select of addresses)
+          double steer_o = steering_control<kSine>(v.x, v.y, v.h, v.v, tl_o, t_o);
+          if (mk_A) {  // the nominal command as the act phase forms it: steer_lane's clip, clip_actions' crashed-vehicle clip
+            steer_o = clipd(steer_o, -kPi / 3, kPi / 3);
+            if (v.crashed) { steer_o = 0; t_o = 0; }
+          }
+          park_at(mk_A ? (int)C_A : (int)C_B, predict<KIND, true, MASS, MIXED, kSine>(v, steer_o, t_o, spsi, cpsi, dt, false), steer_o);
+          haveA = true; haveB = haveB || !mk_A;
+        }
+      }
+    };
     auto make_B = [&]() {
       if constexpr (SHIELDED) {
         if (needB && !haveB) {
@@ -1844,13 +1913,27 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     double new_acc = v.act_acc;
     bool use_B = false, veto = false;
     int new_flags = v.flags;
-    if constexpr (SHIELDED && !SPLIT && !kSerialOnly && kVetoPrior) {
+#ifdef MM_STAMPS
+    bool st_prior = false;  // (stamps builds: this lane started the sub-step from the prior "vetoed")
+#endif
+    if constexpr (kPrimary) {
+      use_B = first_B;  // (the first guess of the veto passes, as below: the candidate the main pass predicted)
+#ifdef MM_STAMPS
+      st_prior = first_B;
+#endif
+      CAND_COUNT(MM_CS_FIRST_B, first_B);
+    } else if constexpr (SHIELDED && !SPLIT && !kSerialOnly && kVetoPrior) {
       // First guess of the veto passes below: what this vehicle's shield said one sub-step ago (a vetoed lane change usually
       // stays vetoed: starting from "no veto" cost such a wave a second classification + solve pass in every sub-step).  The
       // passes converge to the sequential answer from ANY first guess (rank r is final after pass r); a wrong one costs
       // the pass the right one saves.
+      CAND_COUNT(MM_CS_UPFRONT, (c.debug_flags & 1) == 0 && shield_on && needB && !(v.flags & MM_FLAG_IS_LC_SAFE));
       if ((c.debug_flags & 1) == 0 && shield_on && needB && !(v.flags & MM_FLAG_IS_LC_SAFE)) { make_B(); use_B = true; }
+#ifdef MM_STAMPS
+      st_prior = use_B;
+#endif
     }
+    STAMP(MM_CS_UPFRONT_CYCLES);  // candidate B up front, from the prior (nothing where the prior picks the main pass's candidate)
     if constexpr (SPLIT) {
       if (head) {
         // act half of sub-step k: hand the shield's inputs to the sweep kernel (one lane per env there)
@@ -2161,8 +2244,16 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           if (TRACE && shield_on) trace_status(out.trace + (long long)k * MM_T_COUNT * A + i, A, so);
           STAMP(4);  // selection + fixed-point rounds
           const bool want_B = shield_on && so.veto && needB;
-          if (want_B) make_B();
-          STAMP(5);  // lazy candidate B
+          CAND_COUNT(MM_CS_LAZY_B, want_B && !haveB);
+          if constexpr (kPrimary) {
+            // the candidate this lane commits from here on is the one it does not have: a veto fired on a lane that has A, or
+            // (new) the veto of a first_B lane was lifted
+            CAND_COUNT(MM_CS_LAZY_A, !want_B && !haveA);
+            if (want_B ? !haveB : !haveA) make_other();
+          } else {
+            if (want_B) make_B();
+          }
+          STAMP(5);  // lazy candidate
           const bool flip = want_B != use_B;
           use_B = want_B;
           if (!__any(flip)) break;
@@ -2176,7 +2267,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       }
       if (!SPLIT && serial) {
         // ------------- literal front-to-back sweep (fallback / validation form) -----------------
-        make_B();
+        CAND_COUNT(MM_CS_FALLBACK, !haveA || (needB && !haveB));
+        if constexpr (kPrimary) make_other();  // (the literal sweep reads either candidate of every vehicle)
+        else make_B();
         use_B = false; veto = false; new_acc = v.act_acc; new_flags = v.flags;
         // working copy of what the others see of me; committed stage by stage
         if constexpr (kRoomy) { v.gvx = GVX(); cpsi = CPSI(); }
@@ -2308,6 +2401,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
      }
     }
     STAMP(6);  // serial fallback (if taken) + sweep exit
+    CAND_COUNT(MM_CS_PRIOR_HELD, st_prior && use_B);     // started from "vetoed" and the veto held: candidate A is never read
+    CAND_COUNT(MM_CS_PRIOR_LIFTED, st_prior && !use_B);  // ... and the veto was lifted: A is what the vehicle commits
     if (SPLIT && SHIELDED && out.trace && live && tail && !shield_on) {  // (the sweep kernel wrote the QP planes of the vehicles it ran)
       out.trace[(long long)k * MM_T_COUNT * A + i + MM_T_QP_ROWS * A] = 0;
     }
@@ -2333,6 +2428,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         if (!hdv) {
           // a veto re-steers to the current lane; identical to the nominal command unless B was needed
           // (shielded kernels: the nominal command was parked with candidate A -- its register is free since then)
+          // (kPrimary: a first_B lane that never evaluated A holds a stale image in C_A.  Its veto passes ended with
+          // want_B == use_B == true -- a pass that ends with !want_B evaluates A before it leaves, and so does the literal
+          // sweep -- so veto && haveB holds and the select below takes B's command: the load from C_A + 5 is issued for the
+          // whole wave, but its value is not read for that lane)
           double steer_nom = v.act_steer;
           if constexpr (SHIELDED) steer_nom = s_cold[C_A + 5][tid];
           s_cold[C_SSTEER][tid] = (SHIELDED && shield_on && veto && haveB) ? s_cold[C_B + 5][tid] : steer_nom;
@@ -2694,6 +2793,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   {
     const long long wv = gtid >> 6;
     if ((threadIdx.x & 63) < 16 && wv < MM_STAMP_WAVES) g_stamps_w[wv * 16 + (threadIdx.x & 63)] += _t_acc;
+    else if ((threadIdx.x & 63) < 32 && wv < MM_STAMP_WAVES) g_stamps_c[wv * 16 + (threadIdx.x & 63) - 16] += _t_acc;
   }
 #endif
 }
@@ -3960,6 +4060,25 @@ extern "C" int32_t mm_debug_read_stamps(unsigned long long *out16, int32_t reset
   if (rc == hipSuccess && reset) {
     memset(host, 0, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
     rc = hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_w), host, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
+  }
+  return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+// out32[k], k = slot - 16: the cycle sum (slot MM_CS_UPFRONT_CYCLES) or the lanes counted; out32[16 + k]: the waves counted
+extern "C" int32_t mm_debug_read_cand_stamps(unsigned long long *out32, int32_t reset) {
+  static unsigned long long *host = nullptr;
+  if (!host) host = (unsigned long long *)malloc(sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
+  hipError_t rc = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps_c), sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
+  for (int k = 0; k < 32; k++) out32[k] = 0;
+  for (long long w = 0; w < MM_STAMP_WAVES; w++)
+    for (int k = 0; k < 16; k++) {
+      const unsigned long long x = host[w * 16 + k];
+      if (k == MM_CS_UPFRONT_CYCLES - 16) { out32[k] += x; continue; }
+      out32[k] += x & 0xFFFFFFFFull;
+      out32[16 + k] += x >> 32;
+    }
+  if (rc == hipSuccess && reset) {
+    memset(host, 0, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
+    rc = hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_c), host, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
   }
   return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }

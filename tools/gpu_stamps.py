@@ -1,4 +1,6 @@
-"""Diagnostic: per-phase cycle shares of step_kernel (build with `make tuning EXTRA="-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false"`, copy to libmm_hip_stamps.so)."""
+"""Diagnostic: per-phase cycle shares of step_kernel (build with `make tuning EXTRA="-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false"`, copy to libmm_hip_stamps.so),
+and its second-candidate evaluations by cause (up front from the veto prior, lazily after a veto fired / was lifted, literal fallback).
+MM_HIP_LIB: another stamps library (e.g. one built with -DMM_PRIMARY_PRIOR=0)."""
 import ctypes, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -19,23 +21,35 @@ p = torch.tensor([0.1, 0.6, 0.1, 0.1, 0.1], device="cuda:0")
 ring = [torch.multinomial(p, E * N, True, generator=g).view(E, N).int() for _ in range(8)]
 lib = hip_library().lib
 buf = (ctypes.c_ulonglong * 16)()
+cand = (ctypes.c_ulonglong * 32)()  # second-candidate evaluations by cause (mm_kernels.hip, MM_CS_*): lanes [k], waves [16 + k]
 for t in range(100): env.step(ring[t % 8])
-torch.cuda.synchronize(); lib.mm_debug_read_stamps(buf, 1)
+torch.cuda.synchronize(); lib.mm_debug_read_stamps(buf, 1); lib.mm_debug_read_cand_stamps(cand, 1)
 K = 50
 for t in range(K): env.step(ring[t % 8])
-torch.cuda.synchronize(); lib.mm_debug_read_stamps(buf, 1)
+torch.cuda.synchronize(); lib.mm_debug_read_stamps(buf, 1); lib.mm_debug_read_cand_stamps(cand, 1)
 names = ["load+setup", "act", "predict A", "S1 classify", "select+rounds", "lazy B", "sweep exit/serial", "commit", "collisions", "trace+terminal", "rewards+outputs", "respawn+store", "observation", "(count)", "barrier before obs", "metrics"]
-tot = sum(buf[k] for k in range(16) if k != 13)
+names[5] = "lazy candidate"
+upfront_cycles = cand[0]  # between "predict A" and the veto passes: candidate B up front, from the prior (billed to "S1 classify" before)
+tot = sum(buf[k] for k in range(16) if k != 13) + upfront_cycles
 waves = E * 8 / 64
 for k, nme in enumerate(names):
     if k == 13: continue
     print("%-20s %6.2f %%   %8.0f cycles/wave/step" % (nme, 100.0 * buf[k] / tot, buf[k] / waves / K))
+print("%-20s %6.2f %%   %8.0f cycles/wave/step" % ("B up front (prior)", 100.0 * upfront_cycles / tot, upfront_cycles / waves / K))
 print("total %.0f cycles/wave/step" % (tot / waves / K))
+cand_names = ["", "(a) B up front, from the prior", "(b) B lazily, a veto fired in a pass", "(c) literal fallback", "prior 'vetoed', veto held",
+              "prior 'vetoed', veto lifted", "A lazily, the veto of a first-B lane was lifted", "B is the main pass's candidate"]
+cand_out = {}
+for k in range(1, 8):
+    cand_out[cand_names[k]] = {"lanes_per_wave_step": cand[k] / waves / K, "waves_per_wave_step": cand[16 + k] / waves / K}
+    print("%-50s %8.4f lanes   %8.4f wave evaluations   per wave and step" % (cand_names[k], cand[k] / waves / K, cand[16 + k] / waves / K))
 import json
 out = {"workload": "%d envs x 8 CAVs, %s, stationary batch (staggered phases + 100-step pre-roll), %d steps" % (E, shield, K),
        "build": "-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false (s_memtime stamps cost ~10 %% themselves)",
-       "cycles_per_wave_step": {n: buf[k] / waves / K for k, n in enumerate(names) if k != 13}, "total_cycles_per_wave_step": tot / waves / K,
-       "share": {n: buf[k] / tot for k, n in enumerate(names) if k != 13},
+       "cycles_per_wave_step": dict({n: buf[k] / waves / K for k, n in enumerate(names) if k != 13}, **{"B up front (prior)": upfront_cycles / waves / K}),
+       "total_cycles_per_wave_step": tot / waves / K,
+       "share": dict({n: buf[k] / tot for k, n in enumerate(names) if k != 13}, **{"B up front (prior)": upfront_cycles / tot}),
+       "second_candidate_evaluations": cand_out,
        "shielded_wave_substeps": int(buf[13]) >> 32, "veto_passes": int(buf[13]) & 0xFFFFFFFF,
        "veto_passes_per_wave_substep": (int(buf[13]) & 0xFFFFFFFF) / max(int(buf[13]) >> 32, 1)}
 os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
