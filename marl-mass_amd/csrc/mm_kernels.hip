@@ -152,7 +152,10 @@ enum { MM_CS_UPFRONT_CYCLES = 16,  // cycles between "predict A" and the veto pa
        MM_CS_PRIOR_HELD,           // started the sub-step from the prior "vetoed", and the veto held
        MM_CS_PRIOR_LIFTED,         // ... and the veto was lifted
        MM_CS_LAZY_A,               // kPrimary: A evaluated because the veto of a first_B lane was lifted
-       MM_CS_FIRST_B };            // kPrimary: B is the main pass's candidate
+       MM_CS_FIRST_B,              // kPrimary: B is the main pass's candidate
+       MM_CS_NEAR,                 // collision pre-check, per partner and sub-step: lanes within 5 m of that partner / waves with such a lane
+       MM_CS_NEAR_ANY,             // ... per sub-step: lanes within 5 m of any partner / waves with such a lane
+       MM_CS_PRECHECK };           // ... per sub-step: live lanes / waves with a live lane (what the two above are shares of)
 __device__ unsigned long long g_stamps_c[MM_STAMP_WAVES * 16];
 #define CAND_COUNT(k, cond)                                                                                  \
   do {                                                                                                       \
@@ -193,15 +196,28 @@ MM_DEV int shfl_i(int v, int src) { return __shfl(v, src, 64); }
 // permutations (v_mov_b32_dpp: no LDS round trip, a few cycles) instead of ds_bpermute:
 //   M = 1,2,3 quad_perm; 7 row_half_mirror; 8 row_ror:8; 15 row_mirror; the rest are compositions.
 // Every lane of the wave must be active where these are used (they sit in uniform control flow).
+// bound_ctrl = true: with both masks 0xF every lane is written, and a lane whose source is invalid or switched off reads 0.
+// The `old` operand (what such a lane would keep with bound_ctrl = false) is therefore never observable and the compiler
+// no longer has to materialise it: one v_mov_b32 vdst, 0 less in front of every v_mov_b32_dpp.  For the controls below
+// no source lane is ever invalid (quad_perm, the mirrors and row_ror permute within the row), so with every lane active
+// the two forms return the same bits; `old` was the literal 0 anyway, the value bound_ctrl supplies.  A control that
+// shifts lanes out of the row (row_shl / row_shr, wave_*) or a row / bank mask below 0xF does not belong here: its
+// invalid or masked lanes would depend on `old` and need update_dpp with an explicit one.
+template <int CTRL>
+MM_DEV int dpp_perm(int v) {
+  static_assert((CTRL >= 0x00 && CTRL <= 0xFF) || (CTRL >= 0x121 && CTRL <= 0x12F) || CTRL == 0x140 || CTRL == 0x141,
+                "only controls without invalid source lanes: quad_perm, row_ror, row_mirror, row_half_mirror");
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
 template <int M>
 MM_DEV int dppx_i(int v) {
   static_assert(M >= 1 && M <= 15, "xor mask within a 16-lane DPP row");
-  if constexpr (M == 1) return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);        // quad_perm:[1,0,3,2]
-  else if constexpr (M == 2) return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);   // quad_perm:[2,3,0,1]
-  else if constexpr (M == 3) return __builtin_amdgcn_update_dpp(0, v, 0x1B, 0xF, 0xF, false);   // quad_perm:[3,2,1,0]
-  else if constexpr (M == 7) return __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  else if constexpr (M == 8) return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  else if constexpr (M == 15) return __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false); // row_mirror
+  if constexpr (M == 1) return dpp_perm<0xB1>(v);        // quad_perm:[1,0,3,2]
+  else if constexpr (M == 2) return dpp_perm<0x4E>(v);   // quad_perm:[2,3,0,1]
+  else if constexpr (M == 3) return dpp_perm<0x1B>(v);   // quad_perm:[3,2,1,0]
+  else if constexpr (M == 7) return dpp_perm<0x141>(v);  // row_half_mirror
+  else if constexpr (M == 8) return dpp_perm<0x128>(v);  // row_ror:8
+  else if constexpr (M == 15) return dpp_perm<0x140>(v); // row_mirror
   else if constexpr (M < 7) return dppx_i<7>(dppx_i<7 - M>(v));
   else if constexpr (M < 12) return dppx_i<8>(dppx_i<M - 8>(v));
   else return dppx_i<15>(dppx_i<15 - M>(v));
@@ -2456,14 +2472,23 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     // an exact early-out on top of it (a pair it rejects would test false), so the full test -- ONE copy of the code, in a
     // loop over the flagged partners -- runs only on near-contacts.
     unsigned need = 0;  // bit p: partner with creation index p; bit G: the obstacle
+#ifdef MM_STAMPS
+    bool near_any = false;  // (stamps builds: how often the 5 m pre-check lets a pair through)
+    CAND_COUNT(MM_CS_PRECHECK, live);
+#endif
     for_partners<G>([&](auto mc) {
       constexpr int m = decltype(mc)::value;
       double px = px_d<m, G>(v.x, a), py = px_d<m, G>(v.y, a), ph = px_d<m, G>(v.h, a);
       bool pp = px_i<m, G>((int)live, a) != 0;
       double dx = px - v.x, dy = py - v.y;
       const bool near = live & pp & !((dx * dx + dy * dy) > kU5);  // norm > LENGTH pre-check, sqrt-free
+      CAND_COUNT(MM_CS_NEAR, near);
+#ifdef MM_STAMPS
+      near_any |= near;
+#endif
       need |= (near & boxes_may_touch(dx, dy, v.h, ph, 0.9 * kVehLength / 2, 0.9 * kVehWidth / 2)) ? 1u << pidx<m, G>(a) : 0u;
     });
+    CAND_COUNT(MM_CS_NEAR_ANY, near_any);
     {
       double dx = kObstX - v.x, dy = kObstY - v.y;
       const bool near = live & !((dx * dx + dy * dy) > kU5);

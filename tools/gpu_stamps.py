@@ -1,5 +1,5 @@
 """Diagnostic: per-phase cycle shares of step_kernel (build with `make tuning EXTRA="-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false"`, copy to libmm_hip_stamps.so),
-and its second-candidate evaluations by cause (up front from the veto prior, lazily after a veto fired / was lifted, literal fallback).
+and its second-candidate evaluations by cause (up front from the veto prior, lazily after a veto fired / was lifted, literal fallback), and how often the collision pre-check's 5 m test lets a pair through.
 MM_HIP_LIB: another stamps library (e.g. one built with -DMM_PRIMARY_PRIOR=0)."""
 import ctypes, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +43,15 @@ cand_out = {}
 for k in range(1, 8):
     cand_out[cand_names[k]] = {"lanes_per_wave_step": cand[k] / waves / K, "waves_per_wave_step": cand[16 + k] / waves / K}
     print("%-50s %8.4f lanes   %8.4f wave evaluations   per wave and step" % (cand_names[k], cand[k] / waves / K, cand[16 + k] / waves / K))
+# collision pre-check: how often `near` (within 5 m) is set -- per (partner, sub-step) evaluation of a wave and per sub-step
+pre_checks = int(cand[26])  # wave-sub-steps whose pre-check had a live lane (slot MM_CS_PRECHECK: counted where the pre-check runs, shield or not)
+pair_evals = pre_checks * (N - 1)
+near_out = {"near_lanes_per_wave_step": cand[8] / waves / K, "wave_partner_substeps_with_a_near_lane_per_wave_step": cand[24] / waves / K,
+            "share_of_wave_partner_substeps_with_a_near_lane": cand[24] / max(pair_evals, 1),
+            "wave_substeps_with_a_near_lane_per_wave_step": cand[25] / waves / K,
+            "share_of_wave_substeps_with_a_near_lane": cand[25] / max(pre_checks, 1),
+            "wave_substeps_with_a_live_lane_per_wave_step": pre_checks / waves / K}
+for k_, v_ in near_out.items(): print("%-60s %10.5f" % (k_, v_))
 import json
 out = {"workload": "%d envs x 8 CAVs, %s, stationary batch (staggered phases + 100-step pre-roll), %d steps" % (E, shield, K),
        "build": "-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false (s_memtime stamps cost ~10 %% themselves)",
@@ -50,6 +59,7 @@ out = {"workload": "%d envs x 8 CAVs, %s, stationary batch (staggered phases + 1
        "total_cycles_per_wave_step": tot / waves / K,
        "share": dict({n: buf[k] / tot for k, n in enumerate(names) if k != 13}, **{"B up front (prior)": upfront_cycles / tot}),
        "second_candidate_evaluations": cand_out,
+       "collision_pre_check_near": near_out,
        "shielded_wave_substeps": int(buf[13]) >> 32, "veto_passes": int(buf[13]) & 0xFFFFFFFF,
        "veto_passes_per_wave_substep": (int(buf[13]) & 0xFFFFFFFF) / max(int(buf[13]) >> 32, 1)}
 os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
