@@ -103,6 +103,17 @@ MM_DEV void lane_local(int l, double x, double y, double &s, double &r) {  // la
   r = y - lane_sy(l);
   if (l == MM_LANE_KB0) r = r - kSineAmp * mmm_sin(kSinePuls * s + kSinePhase);
 }
+// The same with the sine of kb0's frame at this x as the caller carried it (`car`; NaN: not known -- closest_lane<true> formed
+// it for the pose the vehicle then committed): one wave-uniform test decides whether any lane still needs a sine of its own.
+// The argument is the one closest_lane forms (x - 220 is x - lane_sx(kb0)), so the carried value has mmm_sin's bits.
+MM_DEV void lane_local_carried(int l, double x, double y, double car, double &s, double &r) {
+  s = x - lane_sx(l);
+  r = y - lane_sy(l);
+  const bool kb = l == MM_LANE_KB0;
+  double sn = car;
+  if (__any(kb && car != car)) sn = (car != car) ? mmm_sin(kSinePuls * s + kSinePhase) : car;
+  if (kb) r = r - kSineAmp * sn;
+}
 // the sine lane's slope is at most kSineAmp * kSinePuls = 0.1021 (mmm_cos may overshoot 1 by an ulp or two): mmm_atan_small's
 // range, where it returns mmm_atan's bits without the division and the breakpoint selects
 static_assert(kSineAmp * kSinePuls * (1.0 + 0x1p-40) < 0.125, "the sine lane's heading needs the general mmm_atan");
@@ -137,8 +148,10 @@ MM_DEV bool lane_after_end(int l, double x) {  // lane.py:92-95 (longitudinal on
 // road.py:51-65 get_closest_lane_index: argmin of distance_with_heading (lane.py:102-108), first
 // minimum in insertion order.  The five straight lanes share heading 0, so |wrap(h - 0)| is
 // computed once; only kb0 needs the sine frame.
+// sine_out (optional): the sine of kb0's frame at x where it was evaluated, else NaN (kb0 could not win: the early-out)
 template <bool SINE = false>
-MM_DEV int closest_lane(double x, double y, double h) {
+MM_DEV int closest_lane(double x, double y, double h, double *sine_out = nullptr) {
+  if (sine_out) *sine_out = __builtin_nan("");
   const double ang0 = fabs(wrap_to_pi(h - 0.0));
   int best = 0;
   double bd = 0;
@@ -165,6 +178,7 @@ MM_DEV int closest_lane(double x, double y, double h) {
         sp = mmm_sin(ph); cp = mmm_cos(ph);
         lh = 0.0 + mmm_atan(kSineAmp * kSinePuls * cp);
       }
+      if (sine_out) *sine_out = sp;
       double r = (y - 7.25) - kSineAmp * sp;
       double d = fabs(r) + tail + head + 1.0 * fabs(wrap_to_pi(h - lh));
       if (d < bd) { bd = d; best = MM_LANE_KB0; }
@@ -190,11 +204,13 @@ MM_DEV double index_to_speed(int i) { return 10 + i * (30.0 - 10) / (5 - 1); }  
 // half_tan: 1/2 tan of the returned (clipped) angle -- what the bicycle step needs of it (beta = atan(1/2 tan delta)).  The
 // command is an arcsine, so sin / cos of it are its argument and the square root asin already formed (or the constants at
 // the +-pi/3 limit): no second range reduction, no polynomials (device arithmetic, oracle math mode 1 alike)
-template <bool SINE = false>
-MM_DEV double steering_control(double x, double y, double heading, double speed, int tl, double &half_tan) {  // :146-187
+// CARRIED: `car` is the sine of kb0's frame at x, or NaN (lane_local_carried)
+template <bool SINE = false, bool CARRIED = false>
+MM_DEV double steering_control(double x, double y, double heading, double speed, int tl, double &half_tan, double car = 0.0) {  // :146-187
   constexpr double KP_HEADING = 1 / kTauDs, KP_LATERAL = 1.0 / 3 * KP_HEADING, PURSUIT_TAU = 0.5 * kTauDs;
   double s, r;
-  lane_local(tl, x, y, s, r);
+  if constexpr (CARRIED) lane_local_carried(tl, x, y, car, s, r);
+  else lane_local(tl, x, y, s, r);
   double lane_next = s + speed * PURSUIT_TAU;
   double lfh = lane_heading_at<SINE>(tl, lane_next);
   double lat_cmd = -KP_LATERAL * r;

@@ -155,7 +155,14 @@ enum { MM_CS_UPFRONT_CYCLES = 16,  // cycles between "predict A" and the veto pa
        MM_CS_FIRST_B,              // kPrimary: B is the main pass's candidate
        MM_CS_NEAR,                 // collision pre-check, per partner and sub-step: lanes within 5 m of that partner / waves with such a lane
        MM_CS_NEAR_ANY,             // ... per sub-step: lanes within 5 m of any partner / waves with such a lane
-       MM_CS_PRECHECK };           // ... per sub-step: live lanes / waves with a live lane (what the two above are shares of)
+       MM_CS_PRECHECK,             // ... per sub-step: live lanes / waves with a live lane (what the two above are shares of)
+       MM_CS_ROUND_CYCLES,         // cycles of the exact-mode MASS round loop alone (+ its shield_post): "select+rounds" without selection / gather / shield_static
+       MM_CS_ROUNDS,               // per round of that loop: shielded lanes / rounds
+       MM_CS_PASSES,               // per veto pass that runs the loop: shielded lanes / passes
+       MM_CS_SEED_ACTIVE,          // ... lanes whose QP is active (d != 0) when evaluated from the MM_ROUNDS_PRIOR seed / passes with such a lane
+       MM_CS_DIAG_CYCLES };        // cycles of the evaluation that counts MM_CS_SEED_ACTIVE (stamps builds only; in no phase's sum)
+static_assert(MM_CS_DIAG_CYCLES == 31, "sixteen slots: lanes 16 .. 31");
+constexpr bool mm_cs_is_cycles(int slot) { return slot == MM_CS_UPFRONT_CYCLES || slot == MM_CS_ROUND_CYCLES || slot == MM_CS_DIAG_CYCLES; }
 __device__ unsigned long long g_stamps_c[MM_STAMP_WAVES * 16];
 #define CAND_COUNT(k, cond)                                                                                  \
   do {                                                                                                       \
@@ -251,6 +258,12 @@ template <int G> constexpr bool kPow2 = (G & (G - 1)) == 0;
 #define MM_ROUNDS_LITE 1
 #endif
 constexpr bool kRoundsLite = MM_ROUNDS_LITE != 0;
+// exact-mode MASS rounds: a shielded lane starts from the acceleration of its INACTIVE QP (d = 0), not from 0.0 (see the rounds;
+// -DMM_ROUNDS_PRIOR=0: A-B timing without it)
+#ifndef MM_ROUNDS_PRIOR
+#define MM_ROUNDS_PRIOR 1
+#endif
+constexpr bool kRoundsPrior = MM_ROUNDS_PRIOR != 0;
 #ifndef MM_VETO_PRIOR
 #define MM_VETO_PRIOR 1
 #endif
@@ -446,7 +459,7 @@ struct Cand {
 // the new heading plus angle sums; beta itself is never formed (include/mm_math.h, "angle-sum forms").
 // GENERAL: the instantiation can meet a steering angle that did not come out of steering_control (kernels with HDVs / steer_vel)
 template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false>
-MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double ch, double dt, bool sv = false) {
+MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double ch, double dt, bool sv = false, double *sine_out = nullptr) {
   Cand c;
   // "steer_vel" (safe_controller.py:124-150): the slip angle comes from the steering-angle STATE and the
   // heading advances by d_heading without the dt factor (sic, :135)
@@ -468,7 +481,7 @@ MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double c
   c.h = v.h + (sv ? d_heading : d_heading * dt);
   mmm_sincos(c.h, &c.spsi, &c.cpsi);
   c.gvx = (KIND == MM_ENV_V1) ? mmm_cos_sum(c.spsi, c.cpsi, sb, cb) : 0.0;
-  c.lane = closest_lane<SINE>(c.x, c.y, c.h);  // on_state_update kinematics.py:154-159
+  c.lane = closest_lane<SINE>(c.x, c.y, c.h, sine_out);  // on_state_update kinematics.py:154-159 (sine_out: see closest_lane)
   c.pk = c.lane;
   if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
   return c;
@@ -916,6 +929,9 @@ MM_DEV ShieldRows shield_rows(const DevCfg &c, const ShieldStatic &s, const Neig
   if (s.cadj) r.h3 = s.base3 + (-g0u0 + r.g4u4);
   return r;
 }
+// The acceleration a shielded lane derives when its QP is inactive (d = 0): shield_post's expression with us0 = u0 (u0 >= +0,
+// so u0 + 0.0 is u0; a slow-LC lane that is not vetoed takes u0 as well).  The seed of the exact-mode MASS rounds.
+MM_DEV double rounds_seed(const DevCfg &c, const ShieldStatic &s) { return div_c(s.u0 - s.evx, c.dt, c.inv_dt); }
 // exact KKT point of min 1/2(d^2 + e^2 + 1e18 s^2) s.t. a d - s <= hc, lo <= d <= hi.  (d is clipped into
 // [v_min - u0, v_max - u0] and v_min <= v_max, so check_bounds cannot fire in this mode.)
 MM_DEV double qp_exact(const ShieldStatic &s, const ShieldRows &r) {
@@ -1579,6 +1595,16 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #define MM_PRIMARY_PRIOR 1
 #endif
   constexpr bool kPrimary = kSine && !TRACE && kVetoPrior && MM_PRIMARY_PRIOR != 0;
+  // The sine of kb0's frame that predict's closest_lane forms for the main pass's candidate serves the next sub-step's
+  // steering_control where the vehicle committed that candidate (same x, same argument): one register pair, NaN where the
+  // value is missing -- first sub-step of a launch, closest_lane's early-out, the other candidate committed, lane not live.
+  // kPrimary kernels only (the others steer inside controlled_act).  -DMM_SINE_CARRY=1 to time it: DESIGN.md 6.2.
+#ifndef MM_SINE_CARRY
+#define MM_SINE_CARRY 0
+#endif
+  constexpr bool kSineCarry = kPrimary && MM_SINE_CARRY != 0;
+  double car_sn = __builtin_nan("");
+  (void)car_sn;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   // power-of-two groups tile the launch seamlessly; 6- / 12-lane groups: 64 / G whole groups per wave, its last 4 lanes idle
@@ -1824,7 +1850,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if (live) {
         // (the select is between a value and zero, not between two members of v: a select of their addresses keeps v in memory)
         const int tl_1 = v.tlane + (first_B ? v.lane - v.tlane : 0);
-        const double steer = steering_control<kSine>(v.x, v.y, v.h, v.v, tl_1, st_t);
+        const double steer = steering_control<kSine, kSineCarry>(v.x, v.y, v.h, v.v, tl_1, st_t, car_sn);
         v.act_steer = clipd(steer, -kPi / 3, kPi / 3);
         const double steer_1 = v.act_steer, st_t_1 = st_t;
         clip_actions(v, LC, st_t);
@@ -1838,7 +1864,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     Cand cA;
     memset(&cA, 0, sizeof cA);
     const bool shield_on = SHIELDED && live && !hdv && v.hist_len >= 2;  // gate safe_controller.py:232-239
-    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv);
+    if constexpr (kSineCarry) car_sn = __builtin_nan("");
+    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv, kSineCarry ? &car_sn : nullptr);
     auto park = [&](auto base_c, const Cand &cc, double steer) {  // a candidate's LDS image (shielded kernels only)
       constexpr int base = decltype(base_c)::value;
       if constexpr (SHIELDED) {
@@ -2218,10 +2245,36 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
             const bool slow_lc = (v.hl == 2 || v.hl == 0) && v.v < kStoppingSpeed;
             ShieldRows rr;
             double d_cur = 0.0;
+            // The seed.  Most QPs are inactive (d = 0), and their answer is known before the first round (rounds_seed).  Seeded
+            // with it, round 0 changes only the lanes whose QP is active or that read such a lane: a wave without an active QP
+            // leaves after one round instead of two, and L active followers in a row behind an inactive vehicle that accelerates
+            // need L + 1 rounds, the confirming one included, instead of L + 2 (the count of tests/test_rounds_prior_host.py).
+            // The answer is the same from ANY seed: ol_dyn / oa_dyn read lanes of strictly lower rank only, so the map has one
+            // fixed point -- the sequential answer --, the rank-r lane is final after round r whatever it started from (the bound
+            // stands), and the loop leaves on `no lane changed` only, i.e. at that fixed point.  Measured: DESIGN.md 2.
+            if constexpr (kRoundsPrior) {
+              if (shield_on) acc_cur = rounds_seed(c, ss);
+            }
+#ifdef MM_STAMPS
+            {  // how often would round 0 reproduce the seed in every lane?  (evaluated from the seed whichever seed the build uses)
+              STAMP(4);
+              const double a_seed = shield_on ? rounds_seed(c, ss) : v.act_acc;
+              const double gu_seed = slot_gu<true>(h1vx_mine, a_seed, mine_gvx, dt);
+              const double da = shfl_d(gu_seed, src_ol), db = shfl_d(gu_seed, src_oa);
+              Neigh ns = nb;
+              if (ol_dyn) ns.ol_gu = da;
+              if (oa_dyn) ns.oa_gu = db;
+              const double d_seed = qp_exact(ss, shield_rows<true>(c, ss, ns));
+              CAND_COUNT(MM_CS_PASSES, shield_on);
+              CAND_COUNT(MM_CS_SEED_ACTIVE, shield_on && d_seed != 0.0);
+              STAMP(MM_CS_DIAG_CYCLES);
+            }
+#endif
             for (int round = 0; round <= st.N; round++) {
 #if defined(MM_STAMPS) && defined(MM_COUNT_ROUNDS)
               if ((threadIdx.x & 63) == 13) _t_acc += 1;
 #endif
+              CAND_COUNT(MM_CS_ROUNDS, shield_on);
               const double gu_cur = slot_gu<true>(h1vx_mine, acc_cur, mine_gvx, dt);  // my post-step record under my current decision
               const double da = shfl_d(gu_cur, src_ol), db = shfl_d(gu_cur, src_oa);
               if (ol_dyn) nb.ol_gu = da;
@@ -2235,12 +2288,13 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               }
               const bool changed = __double_as_longlong(acc_next) != __double_as_longlong(acc_cur);
               acc_cur = acc_next;
-              // (4.3 rounds per pass on the headline batch.  Leaving without the confirming round -- on "no decision some lane
-              // reads changed", by ballot, or on "no lane received anything new" at the next exchange -- saves an evaluation and
-              // measured 2 - 3 % SLOWER both ways: profiles/r04/variants.jsonl)
+              // (Leaving without the confirming round -- on "no decision some lane reads changed", by ballot, or on "no lane
+              // received anything new" at the next exchange -- saves an evaluation and measured 2 - 3 % SLOWER both ways:
+              // profiles/r04/variants.jsonl; rounds per pass: profiles/rounds_prior/)
               if (!__any(changed)) break;
             }
             so = shield_post<true>(c, v, ss, rr, d_cur, true, false);
+            STAMP(MM_CS_ROUND_CYCLES);  // the round loop alone
           } else {
           for (int round = 0; round <= st.N; round++) {
             if (MASS) {
@@ -2430,6 +2484,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     }
     if (tail) {  // (split form: the commit half)
     // ---------------- commit Vehicle.step / MDPLCVehicle.step for every vehicle -------------------
+    if constexpr (kSineCarry) {
+      if (!(live && use_B == first_B)) car_sn = __builtin_nan("");  // (the value belongs to the main pass's candidate)
+    }
     if (live) {
       const Cand cc = chosen(use_B);
       const double acc = (SHIELDED && shield_on) ? new_acc : v.act_acc;
@@ -4088,7 +4145,7 @@ extern "C" int32_t mm_debug_read_stamps(unsigned long long *out16, int32_t reset
   }
   return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
-// out32[k], k = slot - 16: the cycle sum (slot MM_CS_UPFRONT_CYCLES) or the lanes counted; out32[16 + k]: the waves counted
+// out32[k], k = slot - 16: the cycle sum (the slots of mm_cs_is_cycles) or the lanes counted; out32[16 + k]: the waves counted
 extern "C" int32_t mm_debug_read_cand_stamps(unsigned long long *out32, int32_t reset) {
   static unsigned long long *host = nullptr;
   if (!host) host = (unsigned long long *)malloc(sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
@@ -4097,7 +4154,7 @@ extern "C" int32_t mm_debug_read_cand_stamps(unsigned long long *out32, int32_t 
   for (long long w = 0; w < MM_STAMP_WAVES; w++)
     for (int k = 0; k < 16; k++) {
       const unsigned long long x = host[w * 16 + k];
-      if (k == MM_CS_UPFRONT_CYCLES - 16) { out32[k] += x; continue; }
+      if (mm_cs_is_cycles(k + 16)) { out32[k] += x; continue; }
       out32[k] += x & 0xFFFFFFFFull;
       out32[16 + k] += x >> 32;
     }

@@ -1,6 +1,8 @@
 """Diagnostic: per-phase cycle shares of step_kernel (build with `make tuning EXTRA="-DMM_STAMPS -DMM_ONLY_G=8 -DMM_ONLY_MIXED=false"`, copy to libmm_hip_stamps.so),
 and its second-candidate evaluations by cause (up front from the veto prior, lazily after a veto fired / was lifted, literal fallback), and how often the collision pre-check's 5 m test lets a pair through.
-MM_HIP_LIB: another stamps library (e.g. one built with -DMM_PRIMARY_PRIOR=0)."""
+Exact-mode MASS: the round loop alone (its cycles are part of "select+rounds"), rounds per veto pass, and the share of passes in which no
+QP is active when evaluated from the MM_ROUNDS_PRIOR seed (round 0 would reproduce the seed in every lane).
+MM_HIP_LIB: another stamps library (e.g. one built with -DMM_ROUNDS_PRIOR=0)."""
 import ctypes, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -29,6 +31,8 @@ for t in range(K): env.step(ring[t % 8])
 torch.cuda.synchronize(); lib.mm_debug_read_stamps(buf, 1); lib.mm_debug_read_cand_stamps(cand, 1)
 names = ["load+setup", "act", "predict A", "S1 classify", "select+rounds", "lazy B", "sweep exit/serial", "commit", "collisions", "trace+terminal", "rewards+outputs", "respawn+store", "observation", "(count)", "barrier before obs", "metrics"]
 names[5] = "lazy candidate"
+round_cycles = cand[11]  # the exact-mode MASS round loop (slot MM_CS_ROUND_CYCLES): billed to "select+rounds" as before
+buf[4] += round_cycles
 upfront_cycles = cand[0]  # between "predict A" and the veto passes: candidate B up front, from the prior (billed to "S1 classify" before)
 tot = sum(buf[k] for k in range(16) if k != 13) + upfront_cycles
 waves = E * 8 / 64
@@ -37,6 +41,16 @@ for k, nme in enumerate(names):
     print("%-20s %6.2f %%   %8.0f cycles/wave/step" % (nme, 100.0 * buf[k] / tot, buf[k] / waves / K))
 print("%-20s %6.2f %%   %8.0f cycles/wave/step" % ("B up front (prior)", 100.0 * upfront_cycles / tot, upfront_cycles / waves / K))
 print("total %.0f cycles/wave/step" % (tot / waves / K))
+rounds, passes, seed_active_passes = int(cand[16 + 12]), int(cand[16 + 13]), int(cand[16 + 14])
+rounds_out = {"round_loop_cycles_per_wave_step": round_cycles / waves / K, "round_loop_share": round_cycles / tot,
+              "selection_gather_static_cycles_per_wave_step": (buf[4] - round_cycles) / waves / K,
+              "rounds_per_wave_step": rounds / waves / K, "passes_per_wave_step": passes / waves / K,
+              "rounds_per_pass": rounds / max(passes, 1), "cycles_per_round": round_cycles / max(rounds, 1),
+              "shielded_lanes_per_pass": cand[13] / max(passes, 1),
+              "active_qp_lanes_from_the_seed_per_pass": cand[14] / max(passes, 1),
+              "share_of_passes_without_an_active_qp_from_the_seed": 1.0 - seed_active_passes / max(passes, 1),
+              "diagnostic_cycles_per_wave_step_not_in_total": cand[15] / waves / K}
+for k_, v_ in rounds_out.items(): print("%-60s %12.5f" % (k_, v_))
 cand_names = ["", "(a) B up front, from the prior", "(b) B lazily, a veto fired in a pass", "(c) literal fallback", "prior 'vetoed', veto held",
               "prior 'vetoed', veto lifted", "A lazily, the veto of a first-B lane was lifted", "B is the main pass's candidate"]
 cand_out = {}
@@ -60,6 +74,7 @@ out = {"workload": "%d envs x 8 CAVs, %s, stationary batch (staggered phases + 1
        "share": dict({n: buf[k] / tot for k, n in enumerate(names) if k != 13}, **{"B up front (prior)": upfront_cycles / tot}),
        "second_candidate_evaluations": cand_out,
        "collision_pre_check_near": near_out,
+       "mass_rounds": rounds_out,
        "shielded_wave_substeps": int(buf[13]) >> 32, "veto_passes": int(buf[13]) & 0xFFFFFFFF,
        "veto_passes_per_wave_substep": (int(buf[13]) & 0xFFFFFFFF) / max(int(buf[13]) >> 32, 1)}
 os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
