@@ -264,6 +264,13 @@ constexpr bool kRoundsLite = MM_ROUNDS_LITE != 0;
 #define MM_ROUNDS_PRIOR 1
 #endif
 constexpr bool kRoundsPrior = MM_ROUNDS_PRIOR != 0;
+// the sweep rank of step_kernel and observe()'s neighbour order with non-short-circuit logic on comparisons that are evaluated
+// anyway (compares and v_cndmask instead of one exec-mask region per condition and partner; the same predicates, the same bits;
+// -DMM_SCAN_SELECTS=0: the short-circuit chains, for A-B timing)
+#ifndef MM_SCAN_SELECTS
+#define MM_SCAN_SELECTS 1
+#endif
+constexpr bool kScanSelects = MM_SCAN_SELECTS != 0;
 #ifndef MM_VETO_PRIOR
 #define MM_VETO_PRIOR 1
 #endif
@@ -593,7 +600,8 @@ MM_DEV int spawn_vehicle(Veh &v, int a, int n_cav, int n_hdv, uint64_t seed, uin
 // ------------------------------------------------------------------------------------------------
 // observation (envs/common/observation.py:181-273) + action mask (abstract.py:219-240)
 // ------------------------------------------------------------------------------------------------
-template <int G, int KIND, bool LEND = false>
+// SEL: the select forms of the neighbour order and the row masks (kScanSelects)
+template <int G, int KIND, bool LEND = false, bool SEL = kScanSelects>
 MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, bool valid, void *obs,
                     uint8_t *avail, float *stage = nullptr, const double *sincos_h = nullptr) {
   constexpr int F = (KIND != MM_ENV_V0) ? 6 : 5;
@@ -635,8 +643,13 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
       double px = mb[0 * 64 + pl], py = mb[1 * 64 + pl];
       bool pp = px_i<m, G>((int)v.present, a) != 0;
       double dx = px - v.x, dy = py - v.y;
-      bool close = pp && (dx * dx + dy * dy) < kT180;  // norm < PERCEPTION_DISTANCE, sqrt-free
-      key[m] = close ? fabs((px - sx) - (v.x - sx)) : INFINITY;
+      if constexpr (SEL) {
+        const double d2 = dx * dx + dy * dy, dist = fabs((px - sx) - (v.x - sx));
+        key[m] = (pp & (d2 < kT180)) ? dist : INFINITY;
+      } else {
+        bool close = pp && (dx * dx + dy * dy) < kT180;  // norm < PERCEPTION_DISTANCE, sqrt-free
+        key[m] = close ? fabs((px - sx) - (v.x - sx)) : INFINITY;
+      }
     });
     // pass 2: the 4 nearest in stable order become rows 1..4: sel[q] = the partner offset m of row q (0: none)
     int sel[4] = {0, 0, 0, 0};
@@ -647,7 +660,9 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
     for (int m = 1; m < G; m++)
 #pragma unroll
       for (int m2 = m + 1; m2 < G; m2++) {
-        const bool m2_first = key[m2] < key[m] || (key[m2] == key[m] && pidx_rt<G>(a, m2) < pidx_rt<G>(a, m));
+        bool m2_first;
+        if constexpr (SEL) m2_first = (key[m2] < key[m]) | ((key[m2] == key[m]) & (pidx_rt<G>(a, m2) < pidx_rt<G>(a, m)));
+        else m2_first = key[m2] < key[m] || (key[m2] == key[m] && pidx_rt<G>(a, m2) < pidx_rt<G>(a, m));
         rank[m] += m2_first ? 1 : 0;
         rank[m2] += m2_first ? 0 : 1;
       }
@@ -655,7 +670,10 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
       constexpr int m = decltype(mc)::value;
       const bool use = key[m] < INFINITY;
 #pragma unroll
-      for (int q = 0; q < 4; q++) sel[q] = (use && rank[m] == q) ? m : sel[q];
+      for (int q = 0; q < 4; q++) {
+        if constexpr (SEL) sel[q] = (use & (rank[m] == q)) ? m : sel[q];
+        else sel[q] = (use && rank[m] == q) ? m : sel[q];
+      }
     });
     double row[4][F - 1];
     bool have[4];
@@ -687,14 +705,21 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
     auto emit = [&](auto put) {
       put(0, ctrl ? 1.0 : 0.0);
 #pragma unroll
-      for (int f = 0; f < F - 1; f++) put(1 + f, ctrl ? lmap(ego[f], f) : 0.0);
+      for (int f = 0; f < F - 1; f++) {
+        if constexpr (SEL) { const double w = lmap(ego[f], f); put(1 + f, ctrl ? w : 0.0); }  // (lmap of every lane, then the mask)
+        else put(1 + f, ctrl ? lmap(ego[f], f) : 0.0);
+      }
 #pragma unroll
       for (int q = 0; q < 4; q++) {
-        const bool hq = ctrl && have[q];
+        bool hq;
+        if constexpr (SEL) hq = ctrl & have[q];
+        else hq = ctrl && have[q];
         put((q + 1) * F, hq ? 1.0 : 0.0);
 #pragma unroll
-        for (int f = 0; f < F - 1; f++)
-          put((q + 1) * F + 1 + f, hq ? lmap(row[q][f], f) : 0.0);
+        for (int f = 0; f < F - 1; f++) {
+          if constexpr (SEL) { const double w = lmap(row[q][f], f); put((q + 1) * F + 1 + f, hq ? w : 0.0); }
+          else put((q + 1) * F + 1 + f, hq ? lmap(row[q][f], f) : 0.0);
+        }
       }
     };
     if (c.obs_f64) {
@@ -1581,6 +1606,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // kernels go from 0 to 2 spilled VGPRs (12 B of scratch) with mmm_atan_small alone -- and those instantiations keep the
   // general forms: the same bits either way.
   constexpr bool kSine = SHIELDED && !SPLIT && !MIXED && !IPM && !kSerialOnly && kPow2<G> && G <= 8;
+  // kScan: the select forms of the sweep rank and of observe() (kScanSelects) in the CAV-only kernels without the trace, every
+  // group size, QP mode and the split phase form.  The general and the trace-carrying kernels already spill, and there the
+  // other code shape moves the allocation either way: nine of them gain 4 .. 72 B of scratch with the selects (the 16-lane
+  // general kernels most), so all of them keep the short-circuit chains: the same bits either way.
+  constexpr bool kScan = kScanSelects && !MIXED && !TRACE;
   // kCarry: sin / cos of the heading and the pose code come from the previous launch (PoseBuf) where their key matches the
   // loaded state.  In the kSine kernels only: same register gate (-DMM_CARRY_POSE=0: A-B timing without it).
 #ifndef MM_CARRY_POSE
@@ -1725,7 +1755,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         constexpr int m = decltype(mc)::value;
         double px = px_d<m, G>(v.x, a);
         bool pp = px_i<m, G>((int)live, a) != 0;
-        rank += (pp && (px > v.x || (px == v.x && pidx<m, G>(a) < a))) ? 1 : 0;
+        if constexpr (kScan) rank += (pp & ((px > v.x) | ((px == v.x) & (pidx<m, G>(a) < a)))) ? 1 : 0;
+        else rank += (pp && (px > v.x || (px == v.x && pidx<m, G>(a) < a))) ? 1 : 0;
       });
     }
     if (head) v.tspeed = s_cold[C_TSPEED][tid];
@@ -2869,7 +2900,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   __syncthreads();  // every wave is done with its cold slots: the obs staging below reuses that LDS
   STAMP(14);  // barrier (+ drain of the stores issued before it)
   const double sc_h[2] = {spsi, cpsi};
-  observe<G, KIND, true>(c, v, a, gb, i, valid, out.obs, out.action_mask, (float *)&s_cold[0][0], sc_h);
+  observe<G, KIND, true, kScan>(c, v, a, gb, i, valid, out.obs, out.action_mask, (float *)&s_cold[0][0], sc_h);
   STAMP(12);  // observation
 #ifdef MM_STAMPS
   {

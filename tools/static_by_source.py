@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Static instructions of the headline step kernel by source line (build-container tool: no GPU needed).
 
-    python tools/static_by_source.py [--root CHECKOUT] [--label NAME] [--json OUT] [--top 40]
+    python tools/static_by_source.py [--root CHECKOUT] [--label NAME] [--json OUT] [--top 40] [--exec-regions]
 
 Compiles the single-instantiation form of marl-mass_amd/csrc/mm_kernels.hip for gfx950 to assembly with line tables
 (-gline-tables-only: code generation is the release build's), walks the body of step_kernel<8, MM_ENV_V1, MM_SHIELD_MASS, false,
 false, false, false> and books every instruction on the `.loc` in force, i.e. on the innermost inlined source line.  Output:
 totals per file, per function of include/mm_math.h and marl-mass_amd/csrc/mm_device.h (by the line ranges of their
 definitions), literal s_mov_b32, fp64 divisions (v_div_fmas_f64) per function, and the heaviest lines.
+
+--exec-regions books the exec-mask instructions instead (s_*_saveexec_b64 and s_cbranch_*: what a short-circuit chain or a
+divergent `if` compiles to) on their source lines: totals, per file, per function of the two headers and EVERY line that holds
+one, heaviest first -- the candidate list for the next select-form rewrite, read from a file instead of derived again.
 """
 import argparse
 import collections
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--label", default="tree")
     ap.add_argument("--json", default=None)
     ap.add_argument("--top", type=int, default=40)
+    ap.add_argument("--exec-regions", action="store_true")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     args = ap.parse_args()
     csrc = os.path.join(args.root, "marl-mass_amd", "csrc")
@@ -60,6 +65,7 @@ def main():
     files, cur, inside = {}, None, False
     by_line, by_file = collections.Counter(), collections.Counter()
     lit, div = collections.Counter(), collections.Counter()
+    saveexec, cbranch = collections.Counter(), collections.Counter()
     total = 0
     for ln in text:
         m = re.match(r"\s*\.file\s+(\d+)\s+\"([^\"]*)\"(?:\s+\"([^\"]*)\")?", ln)
@@ -87,8 +93,28 @@ def main():
             lit[cur] += 1
         if m.group(1) == "v_div_fmas_f64":
             div[cur] += 1
+        if re.match(r"s_\w+_saveexec_b64$", m.group(1)):
+            saveexec[cur] += 1
+        if m.group(1).startswith("s_cbranch_"):
+            cbranch[cur] += 1
     fn = {"mm_math.h": functions(os.path.join(args.root, "include", "mm_math.h")),
           "mm_device.h": functions(os.path.join(csrc, "mm_device.h"))}
+    if args.exec_regions:
+        lines = sorted(set(saveexec) | set(cbranch), key=lambda k: (-(saveexec[k] + cbranch[k]), k))
+        per_file, per_fn = collections.Counter(), collections.Counter()
+        for f, l in lines:
+            per_file[f] += saveexec[(f, l)] + cbranch[(f, l)]
+            if f in fn:
+                per_fn["%s:%s" % (f, owner(fn[f], l) or "(line 0: compiler-generated)")] += saveexec[(f, l)] + cbranch[(f, l)]
+        res = {"label": args.label, "kernel": KERNEL, "flags": " ".join(FLAGS), "total": total, "saveexec": sum(saveexec.values()),
+               "cbranch": sum(cbranch.values()), "by_file": dict(per_file.most_common()), "by_function": dict(per_fn.most_common()),
+               "lines": [{"file": f, "line": l, "saveexec": saveexec[(f, l)], "cbranch": cbranch[(f, l)]} for f, l in lines]}
+        print(json.dumps({k: v for k, v in res.items() if k != "lines"}, indent=1))
+        for r in res["lines"][:args.top]:
+            print("%-16s %5d  saveexec %3d  cbranch %3d" % (r["file"], r["line"], r["saveexec"], r["cbranch"]))
+        if args.json:
+            json.dump(res, open(args.json, "w"), indent=1)
+        return
     by_fn, lit_fn, div_fn = collections.Counter(), collections.Counter(), collections.Counter()
     for (f, l), n in by_line.items():
         if f in fn:
