@@ -1,0 +1,104 @@
+/*
+ * mm_policy_wide_train.h -- loss and full parameter gradient of MAPPO's separate actor and critic at hidden size 512 (the
+ * lateral_control = steer_vel configurations), and the forward-only mm_policy_wide_eval.
+ *
+ * It is include/mm_policy_train.h's contract at the other hidden size the reference trains with: the same networks
+ * (Model_common.py:5-41), the same objective (one agent step of MAPPO.train(), marl/mappo.py:170-201, in its reference
+ * [B, B] form through adv_sums or per sample through advantages), the same arguments, MMMlpParams and MM_PT_CRITIC_*:
+ *   actor:  W1 [512][n_s], b1 [512]; W2 [512][512],       b2 [512]; W3 [n_a][512], b3 [n_a]
+ *   critic: W1 [512][n_s], b1 [512]; W2 [512][512 + n_a], b2 [512]; W3 [1][512],   b3 [1]
+ * mm_policy_train / mm_policy_eval keep refusing hidden != 128; these entries refuse hidden != 512.
+ *
+ * One preparation launch, then per network three kernels over ONE scratch that the second network reuses:
+ *   A  per sample (one wave per MM_POLICY_WIDE_TRAIN_TILE samples, MM_POLICY_WIDE_TRAIN_WAVES waves per workgroup, at most
+ *      MM_POLICY_WIDE_TRAIN_MAX_GRID persistent workgroups): fc1, fc2 (f32 MFMA, fc2's weight read from global memory), the
+ *      head, the loss terms, dz2, and dz1 = (W2[:, :512]^T dz2) . [h1 > 0] (f32 MFMA against the transposed copy that the
+ *      preparation launch wrote);
+ *   B  dW2 = dz2^T [h1 | one_hot], dW3, dW1 (f32 MFMA, the sample index as the reduction) and the bias sums, split over
+ *      slices of samples that each write one partial block;
+ *   C  the fold of the partial blocks in slice order with an fp64 running sum.
+ * No floating-point atomics anywhere: two calls on the same inputs give bit-identical outputs.  Only enqueues work on
+ * `stream` (no allocation, no synchronisation): graph-capturable.
+ *
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip): no oracle twin, not part of
+ * include/mm_abi.h's symbol list or version.  torch.autograd on the two rollout modules is the CPU form.
+ */
+#ifndef MM_POLICY_WIDE_TRAIN_H
+#define MM_POLICY_WIDE_TRAIN_H
+
+#include <stdint.h>
+
+#include "mm_abi.h"
+#include "mm_policy_train.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The decomposition of the launches, for callers that test their boundaries.  A row's diagnostics and mm_policy_wide_eval's
+ * outputs depend on none of them. */
+#define MM_POLICY_WIDE_TRAIN_TILE 32       /* samples per tile: one wave of kernel A owns one tile at a time */
+#define MM_POLICY_WIDE_TRAIN_WAVES 8       /* waves per workgroup of kernel A */
+#define MM_POLICY_WIDE_TRAIN_MAX_GRID 256  /* kernel A launches at most this many persistent workgroups */
+/* Kernel B's slices are whole tiles: tiles_per_slice = max(MM_POLICY_WIDE_TRAIN_MIN_SLICE_TILES, ceil(ntiles /
+ * MM_POLICY_WIDE_TRAIN_MAX_SLICES)), ntiles = ceil(n / 32), slices = ceil(ntiles / tiles_per_slice); the last slice is the
+ * shorter one. */
+#define MM_POLICY_WIDE_TRAIN_MAX_SLICES 48
+#define MM_POLICY_WIDE_TRAIN_MIN_SLICE_TILES 2
+
+/* The scratch, in bytes (what mm_policy_wide_train_scratch_bytes adds up):
+ *   MM_POLICY_WIDE_TRAIN_FIXED_BYTES   a 256-byte header (the count of valid samples) and four [512][512] float blocks:
+ *                                      W2[:, :512]^T of the actor and of the critic for dz1, and a copy of each network's
+ *                                      W2[:, :512] at row pitch 512 (used in place of W2 where its rows are not 16-byte
+ *                                      aligned, as the critic's are for n_a = 5)
+ *   MM_POLICY_WIDE_TRAIN_ROW_BYTES     per sample of the n rounded up to whole tiles: x (32 floats), h1, h2, dz2, dz1 (512
+ *                                      each) and the head's gradient (16); one network at a time
+ *   8 bytes per tile                   the fp64 loss partial
+ *   MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES per slice: dW2 [512][544], the head rows [16][512], dW1 [512][32], the bias sums
+ *                                      [512 + 16 + 512]; at most MM_POLICY_WIDE_TRAIN_MAX_SLICES of them, which is the
+ *                                      upper bound MM_POLICY_WIDE_TRAIN_PARTIAL_MAX_BYTES (58.4 MB) */
+#define MM_POLICY_WIDE_TRAIN_FIXED_BYTES (256 + 4 * 512 * 512 * 4)
+#define MM_POLICY_WIDE_TRAIN_ROW_BYTES ((32 + 4 * 512 + 16) * 4)
+#define MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES ((512 * 544 + 16 * 512 + 512 * 32 + 512 + 16 + 512) * 4)
+#define MM_POLICY_WIDE_TRAIN_PARTIAL_MAX_BYTES (MM_POLICY_WIDE_TRAIN_MAX_SLICES * MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES)
+
+/* Alignment: none beyond mm_policy_train's.  The scratch is MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN-byte aligned (an argument
+ * error otherwise); every other pointer needs its element's alignment only.  fc2's weight is read with 16-byte loads where
+ * its rows allow (pointer and row length multiples of 16 bytes) and with 4-byte loads otherwise -- the same values in the
+ * same order, so the outputs do not depend on which. */
+#define MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN 16
+
+/*
+ * mm_policy_eval's contract (include/mm_policy_train.h) at hidden == 512: logp_taken[j] = actor(obs_j)[action_j] and / or
+ * value[j] = critic(obs_j, one_hot(action_j)); masked slots are not read and get 0; n == 0 does nothing.  A row's outputs
+ * are a function of that row and the weights alone: not of n, nor of where the row falls in the launch, and they equal the
+ * diagnostics mm_policy_wide_train writes for the same row bit for bit.  Needs no scratch.
+ * MM_ERR_INVALID_ARG: as mm_policy_eval, with hidden != 512 in place of hidden != 128.
+ */
+int32_t mm_policy_wide_eval(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                            int64_t act_stride, const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic,
+                            int32_t hidden, int32_t n_a, float *logp_taken, float *value, MMStream stream);
+
+/* Bytes of scratch mm_policy_wide_train needs for n samples (n >= 0), monotone in n: the sum stated above.  Host arithmetic. */
+int32_t mm_policy_wide_train_scratch_bytes(int64_t n, uint64_t *bytes);
+
+/*
+ * mm_policy_train's arguments and contract (include/mm_policy_train.h) with hidden == 512: both actor forms, the optional
+ * valid mask, strides and diagnostics, gradients WRITTEN (not accumulated), loss float[2], either network omitted together
+ * with its gradients, n == 0 or no valid sample writes zeros.  Gradient rows of masked or out-of-range samples are exact
+ * zeros and a masked sample's inputs are not read.
+ * MM_ERR_INVALID_ARG: every case of mm_policy_train, with hidden != 512 in place of hidden != 128, scratch NULL, smaller
+ * than mm_policy_wide_train_scratch_bytes(n) or off MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN.  A refused call enqueues nothing and
+ * writes nothing.
+ */
+int32_t mm_policy_wide_train(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                             int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                             const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
+                             int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums, const float *advantages,
+                             const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, float *logp_taken,
+                             float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MM_POLICY_WIDE_TRAIN_H */

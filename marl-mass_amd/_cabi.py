@@ -344,6 +344,17 @@ class CLib(object):
             lib.mm_policy_train_chunked_scratch_bytes.restype = i32
             lib.mm_policy_train_chunked.argtypes = list(lib.mm_policy_train.argtypes) + [i64]
             lib.mm_policy_train_chunked.restype = i32
+        # the same two entries and the scratch query at hidden 512 (include/mm_policy_wide_train.h: mm_policy_eval's and
+        # mm_policy_train's arguments), also libmm_hip.so only
+        self.has_policy_wide_train = self.has_policy_train and all(
+            hasattr(lib, s) for s in ("mm_policy_wide_train", "mm_policy_wide_eval", "mm_policy_wide_train_scratch_bytes"))
+        if self.has_policy_wide_train:
+            lib.mm_policy_wide_eval.argtypes = list(lib.mm_policy_eval.argtypes)
+            lib.mm_policy_wide_eval.restype = i32
+            lib.mm_policy_wide_train_scratch_bytes.argtypes = [i64, C.POINTER(u64)]
+            lib.mm_policy_wide_train_scratch_bytes.restype = i32
+            lib.mm_policy_wide_train.argtypes = list(lib.mm_policy_train.argtypes)
+            lib.mm_policy_wide_train.restype = i32
         # clip_grad_norm_ + RMSprop / Adam + soft target update in one launch (include/mm_opt_step.h), also libmm_hip.so only
         self.has_opt_step = hasattr(lib, "mm_opt_step")
         if self.has_opt_step:
@@ -432,6 +443,20 @@ class CLib(object):
         self.require_policy_train_chunked()
         b = C.c_uint64()
         self.check(self.lib.mm_policy_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
+        return b.value
+
+    def require_policy_wide_train(self):
+        if not self.has_policy_wide_train:
+            raise NotImplementedError("%s does not export mm_policy_wide_train: the hidden-512 actor's and critic's gradients "
+                                      "need the HIP library" % os.path.basename(self.path))
+
+    def policy_wide_train_scratch_bytes(self, n):
+        """Bytes of scratch mm_policy_wide_train needs for n samples (include/mm_policy_wide_train.h)."""
+        self.require_policy_wide_train()
+        if n < 0:
+            raise ValueError("n must be >= 0, got %d" % n)
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_wide_train_scratch_bytes(n, C.byref(b)))
         return b.value
 
     def require_opt_step(self):

@@ -1,6 +1,7 @@
 """The learners on the device.  `PPOLearner` (below `SharedPPOLearner`) is plain MAPPO's (marl/mappo.py:161-206): separate actor
 and critic, their targets and two optimisers, with both losses and both parameter gradients taken by one library call
-(`mm_policy_train`, include/mm_policy_train.h) and the targets evaluated by `mm_policy_eval`.
+(`mm_policy_train`, include/mm_policy_train.h) and the targets evaluated by `mm_policy_eval`; with hidden-512 networks (the
+steer_vel configurations) the same two calls are `mm_policy_wide_train` / `mm_policy_wide_eval` (include/mm_policy_wide_train.h).
 
 `SharedPPOLearner` is the learner of MAPPO_GI with shared_network = True on the device: `MAPPO_GI.train()` (marl/mappo_gi.py:232-352, the shared
 branch :305-352) with the loss and the full parameter gradient taken by one library call (`mm_policy_gi_train`,
@@ -435,7 +436,8 @@ def _mlp_struct(net, grads=False):
 
 class PPOLearner(_DeviceLearner):
     """`MAPPO`'s actor / critic / actor_target / critic_target / two optimisers and its train() (marl/mappo.py:70-95, :161-206);
-    defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, hidden 128, float32,
+    defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, both of hidden size 128
+    or both 512 (the steer_vel configurations; `mm_policy_wide_train` / `mm_policy_wide_eval`, include/mm_policy_wide_train.h), float32,
     on the device -- typically the modules a DeviceRollout acts with, so the next rollout uses the updated weights.
 
     Per agent step the reference takes the actor's loss with advantages from the CRITIC TARGET and old log-probabilities from
@@ -451,11 +453,14 @@ class PPOLearner(_DeviceLearner):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
             raise ValueError("PPOLearner needs a rollout.ActorNetwork and a rollout.CriticNetwork")
-        n_s, n_a = actor.fc1.weight.shape[1], actor.fc3.weight.shape[0]
-        if (tuple(actor.fc1.weight.shape) != (128, n_s) or tuple(actor.fc2.weight.shape) != (128, 128)
-                or tuple(actor.fc3.weight.shape) != (n_a, 128) or tuple(critic.fc1.weight.shape) != (128, n_s)
-                or tuple(critic.fc2.weight.shape) != (128, 128 + n_a) or tuple(critic.fc3.weight.shape) != (1, 128)):
-            raise ValueError("PPOLearner needs hidden size 128 in both networks, the same state and action sizes, one critic output")
+        n_s, n_a, hid = actor.fc1.weight.shape[1], actor.fc3.weight.shape[0], actor.fc2.weight.shape[0]
+        if (hid not in (128, 512) or tuple(actor.fc1.weight.shape) != (hid, n_s) or tuple(actor.fc2.weight.shape) != (hid, hid)
+                or tuple(actor.fc3.weight.shape) != (n_a, hid) or tuple(critic.fc1.weight.shape) != (hid, n_s)
+                or tuple(critic.fc2.weight.shape) != (hid, hid + n_a) or tuple(critic.fc3.weight.shape) != (1, hid)):
+            raise ValueError("PPOLearner needs hidden size 128 or 512, the same in both networks, the same state and action sizes, "
+                             "one critic output")
+        if hid == 512 and scratch_budget_bytes is not None:
+            raise ValueError("scratch_budget_bytes needs hidden size 128: the chunked gradient entries have no hidden-512 form")
         if not 1 <= n_a <= 8 or not 25 <= n_s <= 32:
             raise ValueError("PPOLearner supports 25..32 state columns and 1..8 actions, got %d and %d" % (n_s, n_a))
         for p in list(actor.parameters()) + list(critic.parameters()):
@@ -464,15 +469,21 @@ class PPOLearner(_DeviceLearner):
         if critic_loss not in abi.PT_CRITIC_LOSS:
             raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
         opt = _optimizer_class(optimizer_type)
-        clib.require_policy_train()
-        _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, clib.policy_train_scratch_bytes)
+        # the library's entries for this hidden size: (gradient, evaluation, scratch query)
+        if hid == 512:
+            clib.require_policy_wide_train()
+            self._entries = (clib.lib.mm_policy_wide_train, clib.lib.mm_policy_wide_eval, clib.policy_wide_train_scratch_bytes)
+        else:
+            clib.require_policy_train()
+            self._entries = (clib.lib.mm_policy_train, clib.lib.mm_policy_eval, clib.policy_train_scratch_bytes)
+        _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, self._entries[2])
         self.actor, self.critic = actor, critic
         self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)
         self.actor_optimizer = opt(actor.parameters(), lr=actor_lr)
         self.critic_optimizer = opt(critic.parameters(), lr=critic_lr)
         self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
         self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
-        self.n_s, self.n_a = n_s, n_a
+        self.n_s, self.n_a, self.hidden = n_s, n_a, hid
         for p in list(actor.parameters()) + list(critic.parameters()):
             _ensure_grad(p)
         # soft_update_every "train": MAPPO's, once per train(); "agent_step": MAPPO_GI's non-shared branch (marl/mappo_gi.py:
@@ -501,7 +512,7 @@ class PPOLearner(_DeviceLearner):
         return n, S
 
     def evaluate(self, obs, actions, actor=None, critic=None, valid=None):
-        """The bare mm_policy_eval: (logp_taken, value), float32 [n] each (None for a network that is not given), zeros in
+        """The bare mm_policy_eval (hidden 512: mm_policy_wide_eval): (logp_taken, value), float32 [n] each (None for a network that is not given), zeros in
         masked slots.  obs [n, S] with any row stride, actions int32 [n] with any stride."""
         n, S = self._check_batch(obs, actions)
         if valid is not None:
@@ -510,9 +521,9 @@ class PPOLearner(_DeviceLearner):
         value = torch.empty(n, dtype=torch.float32, device=self.device) if critic is not None else None
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         ref = lambda net: None if net is None else C.byref(_mlp_struct(net))  # noqa: E731
-        self.clib.check(self.clib.lib.mm_policy_eval(
+        self.clib.check(self._entries[1](
             obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, opt(valid), ref(actor),
-            ref(critic), 128, self.n_a, opt(logp), opt(value), self._stream()))
+            ref(critic), self.hidden, self.n_a, opt(logp), opt(value), self._stream()))
         return logp, value
 
     def old_log_probs(self, obs, actions, valid=None):
@@ -569,11 +580,11 @@ class PPOLearner(_DeviceLearner):
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         args = (
             obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
-            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), 128, self.n_a, self.clip_param,
+            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), self.hidden, self.n_a, self.clip_param,
             abi.PT_CRITIC_LOSS[self.critic_loss], opt(adv_sums) if with_a else None, opt(advantages) if with_a else None, ref(G[0]),
             ref(G[1]), loss.data_ptr(), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream())
         if chunk is None:
-            self.clib.check(self.clib.lib.mm_policy_train(*args))
+            self.clib.check(self._entries[0](*args))
         else:
             self.clib.check(self.clib.lib.mm_policy_train_chunked(*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
