@@ -20,7 +20,9 @@
  * No floating-point atomics anywhere: two calls on the same inputs give bit-identical outputs.  Only enqueues work on
  * `stream` (no allocation, no synchronisation): graph-capturable.
  *
- * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip): no oracle twin, not part of
+ * mm_policy_wide_train_chunked (at the end) is the same gradient in passes under a fixed scratch budget.
+ *
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip, mm_policy_wide_chunked.hip): no oracle twin, not part of
  * include/mm_abi.h's symbol list or version.  torch.autograd on the two rollout modules is the CPU form.
  */
 #ifndef MM_POLICY_WIDE_TRAIN_H
@@ -87,6 +89,9 @@ int32_t mm_policy_wide_train_scratch_bytes(int64_t n, uint64_t *bytes);
  * valid mask, strides and diagnostics, gradients WRITTEN (not accumulated), loss float[2], either network omitted together
  * with its gradients, n == 0 or no valid sample writes zeros.  Gradient rows of masked or out-of-range samples are exact
  * zeros and a masked sample's inputs are not read.
+ * The scratch is not chunked: 4.15 GiB at 524 288 samples; a caller with more samples than it can afford scratch for uses
+ * mm_policy_wide_train_chunked below (the same gradients of ONE loss per network over all n samples, in passes through the
+ * rows of `chunk` samples).
  * MM_ERR_INVALID_ARG: every case of mm_policy_train, with hidden != 512 in place of hidden != 128, scratch NULL, smaller
  * than mm_policy_wide_train_scratch_bytes(n) or off MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN.  A refused call enqueues nothing and
  * writes nothing.
@@ -97,6 +102,55 @@ int32_t mm_policy_wide_train(const float *obs, int64_t obs_stride, int64_t n, in
                              int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums, const float *advantages,
                              const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, float *logp_taken,
                              float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream);
+
+/*
+ * The same call under a fixed scratch budget (marl-mass_amd/csrc/mm_policy_wide_chunked.hip): mm_policy_train_chunked's
+ * contract (include/mm_policy_train.h) at hidden == 512.  Kernels A and B run over the batch in passes of `chunk` samples, the
+ * actor's pass and the critic's alternating over the same rows; each pass's partial blocks are added, in slice order and in
+ * fp64, to the network's own accumulator block, and gradients and losses are written once at the end: the gradient of ONE
+ * loss per network over all n samples, B the number of valid samples of the whole batch, formed by the one preparation
+ * launch.  Deterministic, no floating-point atomics, only enqueues on `stream`: graph-capturable.
+ *
+ * chunk: samples per pass, a positive multiple of 64.  Every other argument is mm_policy_wide_train's.
+ * Scratch (mm_policy_wide_train_chunked_scratch_bytes(n, chunk), MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN-byte aligned), the sum
+ * MM_POLICY_WIDE_TRAIN_CHUNKED_BYTES(n, chunk) of
+ *   MM_POLICY_WIDE_TRAIN_FIXED_BYTES                      as above
+ *   chunk * MM_POLICY_WIDE_TRAIN_ROW_BYTES                the rows of one pass
+ *   MM_POLICY_WIDE_TRAIN_CHUNKED_LOSS_BYTES per tile      the fp64 loss partials of all ceil(n / 32) tiles of BOTH networks
+ *                                                         (both are folded at the end): all that grows with n
+ *   MM_POLICY_WIDE_TRAIN_CHUNKED_BLOCKS(chunk) blocks     of MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES: the partial blocks of one pass.
+ *                                                         The most slices ANY pass of at most `chunk` samples cuts, not the
+ *                                                         slices of a full pass: under the slicing rule above a shorter last
+ *                                                         pass can cut more (chunk 3136 = 98 tiles: 33 slices of 3 tiles; a
+ *                                                         last pass of 3072 samples = 96 tiles: 48 slices of 2)
+ *   2 * MM_POLICY_WIDE_TRAIN_ACC_BYTES                    one accumulator block double[MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES / 4]
+ *                                                         per network
+ * 10.8 MB for the smallest call (64 samples in one pass): the fixed part and the two accumulators.
+ *
+ * With chunk >= n the results are bit-identical to mm_policy_wide_train; for any chunk the losses and the diagnostics are,
+ * and the gradients differ from it only through the float32 rounding of a different slicing of the sample sum.  n == 0 or no
+ * valid sample: as mm_policy_wide_train.
+ * MM_ERR_INVALID_ARG: as mm_policy_wide_train (the scratch against the chunked size), and chunk <= 0 or not a multiple of 64.
+ * A refused call enqueues nothing and writes nothing.
+ */
+#define MM_POLICY_WIDE_TRAIN_CHUNKED_LOSS_BYTES 16
+#define MM_POLICY_WIDE_TRAIN_ACC_BYTES (2 * MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES)
+#define MM_POLICY_WIDE_TRAIN_CHUNKED_BLOCKS(chunk) \
+  ((chunk) / 64 < MM_POLICY_WIDE_TRAIN_MAX_SLICES ? (chunk) / 64 : MM_POLICY_WIDE_TRAIN_MAX_SLICES)
+#define MM_POLICY_WIDE_TRAIN_CHUNKED_BYTES(n, chunk)                                                                          \
+  ((uint64_t)MM_POLICY_WIDE_TRAIN_FIXED_BYTES + (uint64_t)(chunk) * MM_POLICY_WIDE_TRAIN_ROW_BYTES +                            \
+   (((uint64_t)(n) + 31) / 32) * MM_POLICY_WIDE_TRAIN_CHUNKED_LOSS_BYTES +                                                      \
+   (uint64_t)MM_POLICY_WIDE_TRAIN_CHUNKED_BLOCKS(chunk) * MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES + 2 * (uint64_t)MM_POLICY_WIDE_TRAIN_ACC_BYTES)
+
+int32_t mm_policy_wide_train_chunked_scratch_bytes(int64_t n, int64_t chunk, uint64_t *bytes);
+
+int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                     int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                     const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
+                                     int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums,
+                                     const float *advantages, const MMMlpParams *actor_grads, const MMMlpParams *critic_grads,
+                                     float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
+                                     uint64_t scratch_bytes, MMStream stream, int64_t chunk);
 
 #ifdef __cplusplus
 }

@@ -355,6 +355,14 @@ class CLib(object):
             lib.mm_policy_wide_train_scratch_bytes.restype = i32
             lib.mm_policy_wide_train.argtypes = list(lib.mm_policy_train.argtypes)
             lib.mm_policy_wide_train.restype = i32
+        # and its form in passes of `chunk` samples under a fixed scratch budget: the unchunked entry's arguments and the chunk
+        self.has_policy_wide_train_chunked = self.has_policy_wide_train and all(
+            hasattr(lib, s) for s in ("mm_policy_wide_train_chunked", "mm_policy_wide_train_chunked_scratch_bytes"))
+        if self.has_policy_wide_train_chunked:
+            lib.mm_policy_wide_train_chunked_scratch_bytes.argtypes = [i64, i64, C.POINTER(u64)]
+            lib.mm_policy_wide_train_chunked_scratch_bytes.restype = i32
+            lib.mm_policy_wide_train_chunked.argtypes = list(lib.mm_policy_wide_train.argtypes) + [i64]
+            lib.mm_policy_wide_train_chunked.restype = i32
         # clip_grad_norm_ + RMSprop / Adam + soft target update in one launch (include/mm_opt_step.h), also libmm_hip.so only
         self.has_opt_step = hasattr(lib, "mm_opt_step")
         if self.has_opt_step:
@@ -457,6 +465,18 @@ class CLib(object):
             raise ValueError("n must be >= 0, got %d" % n)
         b = C.c_uint64()
         self.check(self.lib.mm_policy_wide_train_scratch_bytes(n, C.byref(b)))
+        return b.value
+
+    def require_policy_wide_train_chunked(self):
+        if not self.has_policy_wide_train_chunked:
+            raise NotImplementedError("%s does not export mm_policy_wide_train_chunked: the hidden-512 actor's and critic's "
+                                      "gradients under a scratch budget need the HIP library" % os.path.basename(self.path))
+
+    def policy_wide_train_chunked_scratch_bytes(self, n, chunk):
+        """Bytes of scratch mm_policy_wide_train_chunked needs for n samples in passes of chunk (include/mm_policy_wide_train.h)."""
+        self.require_policy_wide_train_chunked()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_wide_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
         return b.value
 
     def require_opt_step(self):

@@ -33,50 +33,29 @@
 //   kernel C  every parameter's gradient = the partial blocks summed in slice order (fp64 running sum), written in torch
 //             layout; the loss partials folded by one workgroup in a fixed tree.
 // The actor's three kernels run first, then the critic's over the same scratch (stream order).
-#include "mm_policy_mfma.h"
-#include "../../include/mm_policy_wide_train.h"
+#include "mm_policy_wide_chunked.h"  // kWide, kCat, kSquare, Part, WideLayout; mm_policy_mfma.h and the public header
 
 namespace mm {
 namespace wt {
 
 using namespace mfma;  // frag_row, mfma4, store_tile, relu, the objective's terms, count_valid, fold, loss_tree, persistent_grid
 
-constexpr int kWide = 512;                                // hidden size
 constexpr int kChunks = kWide / 32;                       // 32-feature chunks of a reduction
 constexpr int kWavesA = MM_POLICY_WIDE_TRAIN_WAVES;       // 2 per SIMD
 constexpr int kThreadsA = 64 * kWavesA;
 constexpr int kThreadsB = 256;                            // 4 waves
 constexpr int kOhPitch = kWide + 8;                       // row pitch of the one-hot column table in LDS
-constexpr int kCat = kWide + 32;                          // row pitch of the dW2 partial: 512 + the one-hot tile
 constexpr int kOutBlocks = 10;                            // kernel B: 2 row halves x (4 column groups + the extra group)
-constexpr long long kSquare = (long long)kWide * kWide;   // floats of one [512][512] block
 static_assert(MM_POLICY_WIDE_TRAIN_TILE == 32, "one MFMA tile of samples per wave");
 static_assert(MM_POLICY_WIDE_TRAIN_MAX_GRID == 256, "persistent_grid launches at most one workgroup per CU");
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// the partial block of one slice, in floats
-struct Part {
-  static constexpr int kW2 = 0;                      // [512][544]
-  static constexpr int kHd = kW2 + kWide * kCat;     // [16][512]: head rows
-  static constexpr int kW1 = kHd + 16 * kWide;       // [512][32]: dz1^T x, all columns
-  static constexpr int kb2 = kW1 + kWide * 32;       // [512]
-  static constexpr int kbh = kb2 + kWide;            // [16]
-  static constexpr int kb1 = kbh + 16;               // [512]
-  static constexpr int kSize = kb1 + kWide;
-};
 static_assert(Part::kSize * 4 == MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES, "the header states the partial block");
 static_assert((32 + 4 * kWide + kDh) * 4 == MM_POLICY_WIDE_TRAIN_ROW_BYTES && kXs == 32, "the header states the rows");
 static_assert(kHdr * 4 + 4 * kSquare * 4 == MM_POLICY_WIDE_TRAIN_FIXED_BYTES, "the header states the fixed part");
 
-// The scratch of a call on n samples, offsets in floats
-struct WideLayout {
-  long long n_pad, ntiles;
-  long long w2t, w2p, xs, h1, h2, dz2, dz1, dh, lossp, part, total;  // w2t / w2p: the actor's block, then the critic's
-  int slices;
-  long long slice_rows;
-};
-
+// The scratch of a call on n samples (WideLayout, mm_policy_wide_chunked.h)
 static WideLayout layout(long long n) {
   WideLayout L;
   L.ntiles = (n + 31) / 32;
@@ -552,6 +531,42 @@ static void launch_sample(hipStream_t s, unsigned grid, const SampleArgs &a) {
     hipLaunchKernelGGL((policy_wide_sample_kernel<kCritic, kTrain, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
   else
     hipLaunchKernelGGL((policy_wide_sample_kernel<kCritic, kTrain, false>), dim3(grid), dim3(kThreadsA), 0, s, a);
+}
+
+// ---- host-side launch helpers of the chunked entry (mm_policy_wide_chunked.hip, declared in mm_policy_wide_chunked.h): the same
+// launches as mm_policy_wide_train's below on the samples and rows the caller points at
+WideLayout layout_of(long long n) { return layout(n); }
+
+void launch_prep(hipStream_t s, const float *W2a, const float *W2c, int k2c, float *w2t, float *w2p, const uint8_t *valid, long long n,
+                 int *count) {
+  hipLaunchKernelGGL(policy_wide_prep_kernel, dim3(kPrepGrid), dim3(256), 0, s, W2a, W2c, k2c, w2t, w2p, valid, n, count);
+}
+
+void launch_sample(hipStream_t s, bool critic, const PassArgs &p) {
+  SampleArgs a = {};
+  a.obs = p.obs; a.obs_stride = p.obs_stride; a.n = p.n; a.n_s = p.n_s; a.actions = p.actions; a.act_stride = p.act_stride;
+  a.returns = p.returns; a.ret_stride = p.ret_stride; a.old_logp = p.old_logp; a.valid = p.valid; a.w = p.w; a.n_a = p.n_a;
+  a.clip_param = p.clip_param; a.huber = p.huber; a.adv_sums = p.adv_sums; a.advantages = p.advantages; a.count = p.count;
+  a.w2t = p.w2t;
+  const int k2 = critic ? kWide + p.n_a : kWide;
+  const bool in_place = vec_rows(p.w.W2, k2);
+  a.W2f = in_place ? p.w.W2 : p.w2p;
+  a.pitch2 = in_place ? k2 : kWide;
+  a.s_xs = p.rows.xs; a.s_h1 = p.rows.h1; a.s_h2 = p.rows.h2; a.s_dz2 = p.rows.dz2; a.s_dz1 = p.rows.dz1; a.s_dh = p.rows.dh;
+  a.lossp = p.lossp; a.out0 = p.out0; a.out1 = p.out1;
+  const unsigned grid = grid_a((p.n + 31) / 32);
+  if (critic) launch_sample<true, true>(s, grid, a);
+  else launch_sample<false, true>(s, grid, a);
+}
+
+void launch_wgrad(hipStream_t s, bool critic, const WideRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
+  const dim3 grid_b(slices, kOutBlocks);
+  if (critic)
+    hipLaunchKernelGGL((policy_wide_wgrad_kernel<true>), grid_b, dim3(kThreadsB), 0, s, r.xs, r.h1, r.h2, r.dz2, r.dz1, r.dh, n_pad,
+                       slice_rows, part);
+  else
+    hipLaunchKernelGGL((policy_wide_wgrad_kernel<false>), grid_b, dim3(kThreadsB), 0, s, r.xs, r.h1, r.h2, r.dz2, r.dz1, r.dh, n_pad,
+                       slice_rows, part);
 }
 
 }  // namespace wt

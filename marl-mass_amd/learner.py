@@ -22,10 +22,11 @@ non-negative / negative advantages.  `form="reference"` computes exactly that (i
 trained with, and tests/golden/gi_train_*.npz pin it to the reference's own run); `form="flat"` is textbook per-sample
 PPO-clip on all B * N samples in one optimiser step.
 
-The gradient kernels keep 2 496 B (shared network) / 2 240 B (separate networks) of scratch per sample.  With
-`scratch_budget_bytes` a learner never holds more than that: a call whose unchunked scratch does not fit takes the same
-gradient of ONE loss over all its samples with `mm_policy_gi_train_chunked` / `mm_policy_train_chunked`, in passes through
-the rows of the largest chunk that fits -- still one optimiser step, the same losses bit for bit.
+The gradient kernels keep 2 496 B (shared network) / 2 240 B (separate networks; 8 384 B at hidden 512) of scratch per sample.
+With `scratch_budget_bytes` a learner never holds more than that: a call whose unchunked scratch does not fit takes the same
+gradient of ONE loss over all its samples with `mm_policy_gi_train_chunked` / `mm_policy_train_chunked` /
+`mm_policy_wide_train_chunked` (hidden 512), in passes through the rows of the largest chunk that fits -- still one optimiser
+step, the same losses bit for bit.
 """
 import copy
 import ctypes as C
@@ -425,6 +426,12 @@ def _mlp_params(net):
     return [net.fc1.weight, net.fc1.bias, net.fc2.weight, net.fc2.bias, net.fc3.weight, net.fc3.bias]
 
 
+def _hidden_of(net):
+    """The hidden size of an fc1 / fc2 / fc3 network, None for anything else (the constructor's checks refuse that later)."""
+    w = getattr(getattr(net, "fc2", None), "weight", None)
+    return w.shape[0] if isinstance(w, torch.Tensor) and w.dim() == 2 else None
+
+
 def _mlp_struct(net, grads=False):
     st = abi.MMMlpParams()
     for name, p in zip(abi.MLP_PARAMS, _mlp_params(net)):
@@ -438,7 +445,10 @@ class PPOLearner(_DeviceLearner):
     """`MAPPO`'s actor / critic / actor_target / critic_target / two optimisers and its train() (marl/mappo.py:70-95, :161-206);
     defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, both of hidden size 128
     or both 512 (the steer_vel configurations; `mm_policy_wide_train` / `mm_policy_wide_eval`, include/mm_policy_wide_train.h), float32,
-    on the device -- typically the modules a DeviceRollout acts with, so the next rollout uses the updated weights.
+    on the device -- typically the modules a DeviceRollout acts with, so the next rollout uses the updated weights.  With
+    `scratch_budget_bytes` the scratch never exceeds the budget at either size: a call whose unchunked scratch does not fit runs
+    `mm_policy_train_chunked` (hidden 512: `mm_policy_wide_train_chunked`) in passes of the largest multiple of 64 samples that
+    fits; a budget below that entry's smallest call (64 samples in one pass: 10.8 MB at hidden 512) is a ValueError.
 
     Per agent step the reference takes the actor's loss with advantages from the CRITIC TARGET and old log-probabilities from
     the ACTOR TARGET, then the critic's loss; the two read disjoint parameters, so one `mm_policy_train` call returns both
@@ -448,7 +458,11 @@ class PPOLearner(_DeviceLearner):
     def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
                  soft_update_every="train", scratch_budget_bytes=None):
-        self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
+        # (first: a budget no call can meet is refused whatever else is passed; the smallest pass is that of the hidden size)
+        if _hidden_of(actor) == 512:
+            self._init_budget(scratch_budget_bytes, clib.require_policy_wide_train_chunked, clib.policy_wide_train_chunked_scratch_bytes)
+        else:
+            self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
         if soft_update_every not in ("train", "agent_step"):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
@@ -459,23 +473,25 @@ class PPOLearner(_DeviceLearner):
                 or tuple(critic.fc2.weight.shape) != (hid, hid + n_a) or tuple(critic.fc3.weight.shape) != (1, hid)):
             raise ValueError("PPOLearner needs hidden size 128 or 512, the same in both networks, the same state and action sizes, "
                              "one critic output")
-        if hid == 512 and scratch_budget_bytes is not None:
-            raise ValueError("scratch_budget_bytes needs hidden size 128: the chunked gradient entries have no hidden-512 form")
         if not 1 <= n_a <= 8 or not 25 <= n_s <= 32:
             raise ValueError("PPOLearner supports 25..32 state columns and 1..8 actions, got %d and %d" % (n_s, n_a))
         for p in list(actor.parameters()) + list(critic.parameters()):
             if p.dtype != torch.float32 or p.device.type != "cuda":
-                raise ValueError("PPOLearner needs float32 networks on the device")
+                raise ValueError(("scratch_budget_bytes is a budget of device memory: " if scratch_budget_bytes is not None else "")
+                                 + "PPOLearner needs float32 networks on the device")
         if critic_loss not in abi.PT_CRITIC_LOSS:
             raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
         opt = _optimizer_class(optimizer_type)
-        # the library's entries for this hidden size: (gradient, evaluation, scratch query)
+        # the library's entries for this hidden size: (gradient, evaluation, scratch query, the gradient in passes)
+        chunked = scratch_budget_bytes is not None  # (_init_budget required the entry)
         if hid == 512:
             clib.require_policy_wide_train()
-            self._entries = (clib.lib.mm_policy_wide_train, clib.lib.mm_policy_wide_eval, clib.policy_wide_train_scratch_bytes)
+            self._entries = (clib.lib.mm_policy_wide_train, clib.lib.mm_policy_wide_eval, clib.policy_wide_train_scratch_bytes,
+                             clib.lib.mm_policy_wide_train_chunked if chunked else None)
         else:
             clib.require_policy_train()
-            self._entries = (clib.lib.mm_policy_train, clib.lib.mm_policy_eval, clib.policy_train_scratch_bytes)
+            self._entries = (clib.lib.mm_policy_train, clib.lib.mm_policy_eval, clib.policy_train_scratch_bytes,
+                             clib.lib.mm_policy_train_chunked if chunked else None)
         _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, self._entries[2])
         self.actor, self.critic = actor, critic
         self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)
@@ -554,7 +570,8 @@ class PPOLearner(_DeviceLearner):
         [2] (S+, S-): the reference's [B, B] objective -- and advantages -- float32 [n]: per-sample PPO-clip.  networks
         "both" | "actor" | "critic": the other one's gradient and loss are left out (its .grad is not touched, its loss is 0).
         Only enqueues work: no host synchronisation.  With a scratch budget that the unchunked call's scratch exceeds, the
-        same gradients come from mm_policy_train_chunked in passes of the largest chunk that fits."""
+        same gradients come from mm_policy_train_chunked (hidden 512: mm_policy_wide_train_chunked) in passes of the largest chunk
+        that fits."""
         n, S = self._check_batch(obs, actions)
         if networks not in ("both", "actor", "critic"):
             raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
@@ -586,7 +603,7 @@ class PPOLearner(_DeviceLearner):
         if chunk is None:
             self.clib.check(self._entries[0](*args))
         else:
-            self.clib.check(self.clib.lib.mm_policy_train_chunked(*args, chunk))
+            self.clib.check(self._entries[3](*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
 
     # -- MAPPO.train() -------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Timing of the chunked gradient entries (mm_policy_gi_train_chunked / mm_policy_train_chunked) on the device, n_s 30:
+"""Timing of the chunked gradient entries (mm_policy_gi_train_chunked / mm_policy_train_chunked, and with --entry wide
+mm_policy_wide_train_chunked: the separate networks at hidden 512) on the device, n_s 30:
 
   * the chunked call on n = passes x chunk samples (default 4 x 524 288) against the unchunked entry called on the same
     `passes` parts one after the other, in the same run and in alternating windows: the A and B work is the same, the chunked
@@ -7,8 +8,10 @@
   * one agent step of train(form="reference") at n = --step-n samples (default 6 553 600: 65 536 envs x 100 steps) with a
     learner under --budget-gib of scratch (default 2), which the unchunked entry cannot run at all within that budget.
 
-    python tools/train_chunked_bench.py [--entry gi|pt|both] [--chunk 524288] [--passes 4] [--step-n 6553600] [--json out.json]
+    python tools/train_chunked_bench.py [--entry gi|pt|wide|both] [--chunk 524288] [--passes 4] [--step-n 6553600] [--json out.json]
 
+"both" is gi and pt, the two hidden-128 entries.  A hidden-512 call takes about nine times as long: --entry wide --reps 10
+--step-reps 4 is what profiles/wide_chunked/bench.json was taken with.
 --step-n 0 leaves the agent step out: under `rocprofv3 --kernel-trace --stats` that run gives the accumulate and the fold
 kernels' own times side by side.
 
@@ -54,7 +57,8 @@ def make_learner(entry, clib, **kw):
         net = ActorCriticNetwork(S, N_A, 128, 1, state_split=True).cuda()
         learner, nets = SharedPPOLearner(net, clib, **kw), [net]
     else:
-        actor, critic = ActorNetwork(S, 128, N_A).cuda(), CriticNetwork(S, N_A, 128, 1).cuda()
+        hidden = 512 if entry == "wide" else 128
+        actor, critic = ActorNetwork(S, hidden, N_A).cuda(), CriticNetwork(S, N_A, hidden, 1).cuda()
         learner, nets = PPOLearner(actor, critic, clib, **kw), [actor, critic]
     with torch.no_grad():  # networks that have moved away from their targets: ratios off 1
         for net in nets:
@@ -71,6 +75,13 @@ def batch(n):
     return obs, act, ret
 
 
+def queries(entry, clib):
+    """(chunked, unchunked) size queries of the entry."""
+    return {"gi": (clib.policy_gi_train_chunked_scratch_bytes, clib.policy_gi_train_scratch_bytes),
+            "pt": (clib.policy_train_chunked_scratch_bytes, clib.policy_train_scratch_bytes),
+            "wide": (clib.policy_wide_train_chunked_scratch_bytes, clib.policy_wide_train_scratch_bytes)}[entry]
+
+
 def inputs(entry, learner, obs, act, ret):
     """(old_logp, keyword arguments of loss_and_grad) for the reference form."""
     if entry == "gi":
@@ -84,7 +95,7 @@ def compare(entry, clib, chunk, passes, reps):
     n = chunk * passes
     obs, act, ret = batch(n)
     whole = make_learner(entry, clib)  # no budget: the unchunked entry, called on the parts
-    query = clib.policy_gi_train_chunked_scratch_bytes if entry == "gi" else clib.policy_train_chunked_scratch_bytes
+    query, unchunked = queries(entry, clib)
     budget = query(n, chunk)
     chunked = make_learner(entry, clib, scratch_budget_bytes=budget)  # exactly `passes` passes of `chunk`
     old, kw = inputs(entry, whole, obs, act, ret)
@@ -99,7 +110,6 @@ def compare(entry, clib, chunk, passes, reps):
 
     (sep, sep_lo, sep_hi), (chk, chk_lo, chk_hi) = alternating_ms([separate_calls, chunked_call], reps)
     assert chunked._plan(n)[0] == chunk and chunked._scratch.numel() <= budget
-    unchunked = clib.policy_gi_train_scratch_bytes if entry == "gi" else clib.policy_train_scratch_bytes
     return {"n": n, "chunk": chunk, "passes": passes, "reps_per_window": reps,
             "separate_calls_ms": sep, "separate_calls_ms_min": sep_lo, "separate_calls_ms_max": sep_hi,
             "chunked_ms": chk, "chunked_ms_min": chk_lo, "chunked_ms_max": chk_hi, "chunked_over_separate": chk / sep,
@@ -115,7 +125,7 @@ def agent_step(entry, clib, n, budget, reps):
 
     (ms, lo, hi), = alternating_ms([step], reps)
     chunk = learner._plan(n)[0]
-    unchunked = clib.policy_gi_train_scratch_bytes if entry == "gi" else clib.policy_train_scratch_bytes
+    unchunked = queries(entry, clib)[1]
     return {"n": n, "budget_MB": budget / 2 ** 20, "chunk": chunk, "passes": None if chunk is None else -(-n // chunk),
             "scratch_MB": learner._scratch.numel() / 2 ** 20, "unchunked_scratch_of_n_MB": unchunked(n) / 2 ** 20,
             "reps_per_window": reps, "train_reference_agent_step_ms": ms, "train_reference_agent_step_ms_min": lo,
@@ -124,7 +134,7 @@ def agent_step(entry, clib, n, budget, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--entry", default="both", choices=["gi", "pt", "both"])
+    ap.add_argument("--entry", default="both", choices=["gi", "pt", "wide", "both"])
     ap.add_argument("--chunk", type=int, default=524288)
     ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--step-n", type=int, default=6553600)
