@@ -5,7 +5,9 @@
  * default) rewrites the joint action before the env steps: controlled vehicles are taken in priority order, each one
  * rolled (simulation_frequency // policy_frequency) * n_step sub-steps ahead together with its four lane neighbours on a
  * copy of the env, and an action whose lookahead crashes is replaced by the available action with the largest safety
- * room (abstract.py:219-280).  Exported by libmm_hip.so only; the CPU oracle has no twin of it.
+ * room (abstract.py:219-280).  Exported by libmm_hip.so (marl-mass_amd/csrc/mm_supervisor.hip, DEV = device pointers) and, as
+ * test infrastructure, by the CPU oracle (oracle/mm_oracle.c: a twin written from the reference on a plain per-env copy,
+ * DEV = host pointers, same error codes and contracts; in the oracle's math mode 1 it matches the kernel bit for bit).
  *
  * Scope: merge-multi-agent-v0, CAV-only and mixed traffic.  HDVs (MM_B_KIND 2, IDMVehicle) in the lookahead follow
  * idm_controller.py (generate_actions once at its first sub-step, two draws; a crashed HDV's points alias its live
@@ -36,7 +38,10 @@ int32_t mm_supervise_scratch_bytes(int32_t E, int32_t N, int32_t n_step, int32_t
  *           its order -- one priority tie-breaker per controlled vehicle, in controlled order, then two per HDV
  *           whose actions a lookahead generates, as they happen (at most N_cav + 8 N_cav <= 9 N).  NULL: the device draws
  *           them (Philox4x32-10 keyed on the env's seed plane, MM_E_EPISODE, MM_E_STEPS and the draw index), so a
- *           checkpoint, a sharded batch (first_env) or a graph replay draws what an unbroken run would.
+ *           checkpoint, a sharded batch (first_env) or a graph replay draws what an unbroken run would.  Draw d of env e is
+ *           u53(w[0], w[1]) = ((w[0] >> 5) * 2^26 + (w[1] >> 6)) / 2^53 of the four output words w of Philox4x32-10 with the
+ *           counter (d, MM_E_EPISODE[e], MM_E_STEPS[e], 0x53555056 -- the supervisor's domain word) and the key (low, high
+ *           half of seed[e]).
  * n_draws:  DEV int32[E] or NULL -- uniforms each env consumed.
  * scratch:  DEV, >= mm_supervise_scratch_bytes(E, N, n_step, sub_steps), 8-byte aligned, contents irrelevant.
  * Only enqueues work on `stream` (no allocation, no synchronisation): graph-capturable.

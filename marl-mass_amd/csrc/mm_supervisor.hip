@@ -113,6 +113,12 @@ MM_DEV bool colliding(double ex, double ey, double eh, double ox, double oy, dou
   return rects_intersect(ex, ey, eh, ox, oy, ol, ow, oh);
 }
 
+// PHILOX: the device draws (uniforms == NULL) -- a compile-time choice, not a branch inside draw().  As a run-time test of the
+// (wave-uniform) pointer the compiler kept the answer as a lane mask formed inside the priority-key loop, i.e. under the exec
+// mask of that loop's LAST trip: only the lanes whose env has the most controlled vehicles of the wave.  A later draw by lanes
+// outside that mask (an HDV's generate_actions in a ragged wave) then took the recorded-uniforms path and got its 0.5 filler
+// instead of the Philox value (found by tests/test_supervisor_twin_gpu.py; DESIGN.md "Supervisor parity").
+template <bool PHILOX>
 __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.E) return;
@@ -145,10 +151,13 @@ __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
   const uint32_t episode = (uint32_t)a.ep[MM_E_EPISODE * a.E + e], steps = (uint32_t)a.ep[MM_E_STEPS * a.E + e];
   auto draw = [&]() {
     const int d = nd++;
-    if (a.uniforms) return d < a.stride ? a.uniforms[(long long)e * a.stride + d] : 0.5;  // (at most 9 N draws: see header)
-    uint32_t w[4];
-    philox4x32((uint32_t)d, episode, steps, kDomain, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    return u53(w[0], w[1]);
+    if constexpr (!PHILOX) {
+      return d < a.stride ? a.uniforms[(long long)e * a.stride + d] : 0.5;  // (at most 9 N draws: see header)
+    } else {
+      uint32_t w[4];
+      philox4x32((uint32_t)d, episode, steps, kDomain, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+      return u53(w[0], w[1]);
+    }
   };
   for (int i = 0; i < n; i++) {
     const int l = B(MM_B_LANE, i);
@@ -426,6 +435,8 @@ extern "C" int32_t mm_supervise(MMHandle hd, int32_t kind, int32_t n_step, const
   a.E = h->E; a.N = h->N; a.n_points = np;
   a.dt = 1.0 / c.simulation_frequency;
   a.headway_time = c.headway_time;
-  hipLaunchKernelGGL(mm::sup::supervise_kernel, dim3((unsigned)((h->E + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)((h->E + 63) / 64));
+  if (uniforms) hipLaunchKernelGGL(mm::sup::supervise_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(mm::sup::supervise_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }

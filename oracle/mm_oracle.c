@@ -1680,6 +1680,458 @@ int32_t mm_poll_errors(MMHandle h, MMStream stream) {
   return rc;
 }
 
+/* ------------------------------------------------------------------ safety/central_layer.py: the "priority" supervisor
+ *
+ * Twin of mm_supervise (include/mm_supervisor.h), restated from the reference -- central_layer.py:16-178 safety_supervisor,
+ * abstract.py:219-280 (_get_available_actions, check_safety_room), :614-635 (distance_to_merging_end,
+ * _compute_headway_distance), :721-755 (check_collision, _is_colliding), mdp_controller.py and idm_controller.py -- on a plain
+ * per-env deep copy: env_copy is an Env, every vehicle owns a list of trajectory points as the reference's
+ * vehicle.trajectories does.  It shares no code and no memory layout with the device kernel; the caller's scratch buffer is
+ * only validated.  The lane, steering, rectangle and IDM helpers above are the golden-pinned ones of the step path.
+ * Math mode 0 evaluates libm in the reference's operation order; mode 1 the device arithmetic (include/mm_math.h, angle-sum
+ * bicycle step, powers by multiplication), which makes the device kernel comparable bit for bit.
+ */
+#include "../include/mm_supervisor.h"
+
+#define SUP_DOMAIN 0x53555056u /* Philox domain word of the supervisor's draws (include/mm_supervisor.h) */
+
+/* branches a call went through (orc_supervise_census); names in sup_census_names, same order */
+enum {
+  SC_STATES, SC_LOOKAHEADS, SC_REPLACED,
+  SC_KEY_RAMP, SC_KEY_SPEED_LE0, SC_KEY_NO_FRONT, SC_KEY_NEXT_LANE, SC_ORDER_DIFFERS,
+  SC_EGO_RESET, SC_NB_SKIPPED,
+  SC_Q_BC0_BC1, SC_Q_AB0_KB0, SC_Q_KB0_AB0, SC_Q_BC1_BC0, SC_Q_NONE,
+  SC_FOLLOW_ROAD_CAV, SC_FOLLOW_ROAD_HDV, SC_LC_ACCEPTED, SC_LC_REFUSED,
+  SC_HDV_FRONT_VEHICLE, SC_HDV_FRONT_NONE, SC_HDV_FRONT_OBSTACLE, SC_HDV_CRASHED_START,
+  SC_CLIP_CAV, SC_CLIP_HDV,
+  SC_COLL_FL, SC_COLL_RL, SC_COLL_FR, SC_COLL_RR, SC_COLL_OBSTACLE, SC_COLL_MIN_EGO, SC_COLL_MIN_OTHER,
+  SC_REPL_0, SC_REPL_1, SC_REPL_2, SC_REPL_3, SC_REPL_4,
+  SC_SECOND_REPLACEMENT, SC_ROOM_TIE, SC_NB_CRASH_CLEARED, SC_EGO_CRASHED_START,
+  SC_COUNT
+};
+static const char *const sup_census_names[SC_COUNT] = {
+  "states", "lookaheads", "replaced_actions",
+  "key_ramp", "key_speed_le0", "key_no_front", "key_next_lane_headway", "order_differs",
+  "ego_reset", "neighbour_skipped",
+  "query_bc0_bc1", "query_ab0_kb0", "query_kb0_ab0", "query_bc1_bc0", "query_none",
+  "follow_road_cav", "follow_road_hdv", "lane_change_accepted", "lane_change_refused",
+  "hdv_front_vehicle", "hdv_front_none", "hdv_front_obstacle", "hdv_crashed_start",
+  "speed_clip_cav", "speed_clip_hdv",
+  "collision_fl", "collision_rl", "collision_fr", "collision_rr", "collision_obstacle", "collision_min_ego", "collision_min_other",
+  "replaced_by_0", "replaced_by_1", "replaced_by_2", "replaced_by_3", "replaced_by_4",
+  "second_replacement", "room_tie", "neighbour_crash_cleared", "ego_crashed_start",
+};
+static int64_t g_sup_census[SC_COUNT];
+static double *g_sup_trace;      /* orc_supervise_trace: where the next mm_supervise calls report, or NULL */
+static uint64_t g_sup_trace_len; /* doubles */
+
+/* one entry of vehicle.trajectories: [position, heading, speed].  aliased: idm_controller.py:42-44 appends a crashed
+ * vehicle's position WITHOUT a copy, so the entry keeps reading the vehicle's live position */
+typedef struct { double x, y, heading, speed; int aliased; } SupPoint;
+typedef struct {
+  Env env;                       /* env_copy (central_layer.py:22) */
+  int len[MM_MAX_AGENTS];        /* len(v.trajectories) */
+  SupPoint *traj[MM_MAX_AGENTS]; /* v.trajectories */
+  int n_points;
+  double dt;
+  const double *uniforms; /* this env's row, or NULL: Philox */
+  int stride, n_draws;
+  uint64_t seed;
+  uint32_t episode, steps;
+  int64_t *cen;
+} SupCtx;
+
+/* np.random.rand(): the next recorded uniform, or draw d of the env's Philox stream */
+static double sup_rand(SupCtx *c) {
+  const int d = c->n_draws++;
+  if (c->uniforms) return d < c->stride ? c->uniforms[d] : 0.5; /* (the reference draws at most 9 N values) */
+  uint32_t w[4];
+  philox4x32((uint32_t)d, c->episode, c->steps, SUP_DOMAIN, (uint32_t)c->seed, (uint32_t)(c->seed >> 32), w);
+  return ((w[0] >> 5) * 67108864.0 + (w[1] >> 6)) / 9007199254740992.0;
+}
+static double sup_point_x(const SupCtx *c, int v, int t) { return c->traj[v][t].aliased ? c->env.v[v].x : c->traj[v][t].x; }
+static double sup_point_y(const SupCtx *c, int v, int t) { return c->traj[v][t].aliased ? c->env.v[v].y : c->traj[v][t].y; }
+
+/* clip_actions (mdp_controller.py:118-127, idm_controller.py:230-239); min / max keep their first argument on ties */
+static void sup_clip_actions(double *steer, double *acc, double speed, int crashed) {
+  if (crashed) { *steer = 0; *acc = -1.0 * speed; }
+  if (speed > MAX_SPEED) { const double c = 1.0 * (MAX_SPEED - speed); *acc = c < *acc ? c : *acc; }
+  else if (speed < -MAX_SPEED) { const double c = 1.0 * (MAX_SPEED - speed); *acc = c > *acc ? c : *acc; }
+}
+/* the bicycle step both controllers share (mdp_controller.py:57-63, idm_controller.py:49-55): no speed floor, no lane
+ * update.  from_sc: `steer` is the last steering_control result, whose sin / cos math mode 1 carries */
+static void sup_move(Veh *v, double steer, double acc, double dt, int from_sc) {
+  if (g_math_mode) {
+    double ss, cs, sb, cb, sh, ch;
+    if (from_sc && v->sc_valid && steer == v->sc_steer) { ss = v->sc_sin; cs = v->sc_cos; }
+    else mmm_sincos(steer, &ss, &cs);
+    mmm_slip_sincos(1.0 / 2 * (ss / cs), &sb, &cb);
+    mmm_sincos(v->heading, &sh, &ch);
+    const double vx = v->speed * mmm_cos_sum(sh, ch, sb, cb), vy = v->speed * mmm_sin_sum(sh, ch, sb, cb);
+    v->x += vx * dt;
+    v->y += vy * dt;
+    v->heading += v->speed * sb / (VEH_LENGTH / 2) * dt;
+  } else {
+    const double beta = m_atan(1.0 / 2 * m_tan(steer));
+    const double vx = v->speed * m_cos(v->heading + beta), vy = v->speed * m_sin(v->heading + beta);
+    v->x += vx * dt;
+    v->y += vy * dt;
+    v->heading += v->speed * m_sin(beta) / (VEH_LENGTH / 2) * dt;
+  }
+  v->speed += acc * dt;
+}
+static void sup_append(SupPoint *traj, int *len, int cap, const Veh *v, int aliased) {
+  if (*len >= cap) return; /* (every vehicle holds 0 or n_points points when a lookahead starts) */
+  SupPoint *p = &traj[(*len)++];
+  p->x = v->x; p->y = v->y; p->heading = v->heading; p->speed = v->speed; p->aliased = aliased;
+}
+
+/* mdp_controller.py:19-64 */
+static void sup_mdp_controller(SupCtx *c, Veh *v, SupPoint *traj, int *len, int action) {
+  const int tl0 = v->target_lane;
+  follow_road(v); /* :67-73 */
+  if (v->target_lane != tl0) c->cen[SC_FOLLOW_ROAD_CAV]++;
+  if (action == 3) v->target_speed += 5;
+  else if (action == 4) v->target_speed -= 5;
+  else if (action == 2 || action == 0) { /* np.clip(_id -/+ 1, 0, lanes - 1): only road (b, c) has two lanes */
+    int id = lane_id_in_road(v->target_lane) + (action == 2 ? 1 : -1);
+    const int lanes = lane_road(v->target_lane) == 1 ? 2 : 1;
+    if (id < 0) id = 0;
+    if (id > lanes - 1) id = lanes - 1;
+    const int cand = lane_road(v->target_lane) == 1 ? (id == 1 ? MM_LANE_BC1 : MM_LANE_BC0) : v->target_lane;
+    if (lane_is_reachable_from(cand, v->x, v->y)) {
+      if (cand != v->target_lane) c->cen[SC_LC_ACCEPTED]++;
+      v->target_lane = cand;
+    } else if (cand != v->target_lane) c->cen[SC_LC_REFUSED]++;
+  }
+  double steer = clipd(steering_control(v, v->target_lane), -PI / 3, PI / 3);
+  double acc = speed_control(v, v->target_speed);
+  const int from_sc = !v->crashed;
+  if (v->speed > MAX_SPEED) c->cen[SC_CLIP_CAV]++;
+  sup_clip_actions(&steer, &acc, v->speed, v->crashed);
+  sup_move(v, steer, acc, c->dt, from_sc);
+  sup_append(traj, len, c->n_points, v, 0);
+}
+
+/* idm_controller.py:41-56; the action dict is vehicle.action, so what clip_actions writes into it persists */
+static void sup_idm_controller(SupCtx *c, int i) {
+  Veh *v = &c->env.v[i];
+  if (v->crashed) { sup_append(c->traj[i], &c->len[i], c->n_points, v, 1); return; }
+  if (v->speed > MAX_SPEED) c->cen[SC_CLIP_HDV]++;
+  sup_clip_actions(&v->act_steer, &v->act_acc, v->speed, v->crashed);
+  sup_move(v, v->act_steer, v->act_acc, c->dt, 0);
+  sup_append(c->traj[i], &c->len[i], c->n_points, v, 0);
+}
+/* idm_controller.py:125-166 mobil.  Its "new" and "old" neighbours come from the same own-lane query (:137, :144) */
+static int sup_mobil(const Env *e, int i) {
+  Body self = body_of(&e->v[i]), new_prec, new_foll, old_prec, old_foll;
+  neighbour_vehicles(e, i, e->v[i].lane, &new_prec, &new_foll);
+  const double new_following_a = idm_acceleration(&new_foll, &new_prec);
+  const double new_following_pred_a = idm_acceleration(&new_foll, &self);
+  if (new_following_pred_a < -MOBIL_MAX_BRAKING) return 0;
+  neighbour_vehicles(e, i, e->v[i].lane, &old_prec, &old_foll);
+  const double self_pred_a = idm_acceleration(&self, &new_prec);
+  /* an HDV of this env has no route (merge_env_v1.py:256-258): the acceleration-gain branch */
+  const double self_a = idm_acceleration(&self, &old_prec);
+  const double old_following_a = idm_acceleration(&old_foll, &self);
+  const double old_following_pred_a = idm_acceleration(&old_foll, &old_prec);
+  const double jerk = self_pred_a - self_a + 0. * (new_following_pred_a - new_following_a + old_following_pred_a - old_following_a);
+  if (jerk < MOBIL_MIN_ACC_GAIN) return 0;
+  return 1;
+}
+/* idm_controller.py:87-122 change_lane_policy: returns a lane, changes nothing.  With a lane change ongoing (:99-111) the
+ * abort loop only rebinds a local and the function returns the vehicle's lane */
+static int sup_change_lane_policy(const Env *e, int i) {
+  const Veh *v = &e->v[i];
+  int target = v->target_lane;
+  if (v->lane != target) return v->lane;
+  const int side = v->lane == MM_LANE_BC0 ? MM_LANE_BC1 : (v->lane == MM_LANE_BC1 ? MM_LANE_BC0 : -1); /* side_lanes */
+  if (side >= 0 && lane_is_reachable_from(side, v->x, v->y) && sup_mobil(e, i)) target = side;
+  return target;
+}
+/* idm_controller.py:59-76 generate_actions */
+static void sup_generate_actions(SupCtx *c, int i) {
+  Veh *v = &c->env.v[i];
+  Body front, rear, self;
+  neighbour_vehicles(&c->env, i, v->lane, &front, &rear); /* :242-271: vehicles then objects on its own lane, margin 1 */
+  c->cen[!front.present ? SC_HDV_FRONT_NONE : front.is_object ? SC_HDV_FRONT_OBSTACLE : SC_HDV_FRONT_VEHICLE]++;
+  const int tl0 = v->target_lane;
+  follow_road(v);
+  if (v->target_lane != tl0) c->cen[SC_FOLLOW_ROAD_HDV]++;
+  const int target = sup_change_lane_policy(&c->env, i);
+  double steer = steering_control(v, target);
+  steer = clipd(steer * (sup_rand(c) * 0.1 + 0.95), -PI / 3, PI / 3);
+  self = body_of(v);
+  double acc = idm_acceleration(&self, &front);
+  acc = clipd(acc * (sup_rand(c) * 0.1 + 0.95), -IDM_ACC_MAX, IDM_ACC_MAX);
+  v->act_steer = steer;
+  v->act_acc = acc;
+  v->sc_valid = 0;
+}
+
+/* abstract.py:620-635 _compute_headway_distance; *src: 0 nothing ahead, 1 own lane, 2 the next lane */
+static double sup_headway_distance(const Env *e, int i, int *src) {
+  const Veh *veh = &e->v[i];
+  double hd = 60;
+  *src = 0;
+  const int nl = next_lane(veh->lane, veh->x, veh->y);
+  for (int j = 0; j < e->n; j++) {
+    const Veh *v = &e->v[j];
+    if (v->lane == veh->lane && v->x > veh->x) {
+      const double d = v->x - veh->x;
+      if (d < hd) { hd = d; *src = 1; }
+    }
+    if (veh->lane != MM_LANE_BC1 && v->lane == nl && v->x > veh->x) {
+      const double d = v->x - veh->x;
+      if (d < hd) { hd = d; *src = 2; }
+    }
+  }
+  return hd;
+}
+
+/* abstract.py:242-280 check_safety_room of `copy` (a fresh copy of the original ego) under action a; sv = [fl, rl, fr, rr] */
+static double sup_check_safety_room(SupCtx *c, Veh *copy, SupPoint *traj, int *len, int a, const int *sv, int time_steps) {
+  double min_room = 0;
+  const int lane = copy->lane; /* (mdp_controller never updates lane_index) */
+  for (int t = 0; t <= time_steps; t++) {
+    sup_mdp_controller(c, copy, traj, len, a);
+    double room = lane == MM_LANE_BC1 ? (220.0 + 100.0 + 100.0) - copy->x : 100.0; /* distance_to_merging_end :614-618 */
+    const double x = traj[t].x;
+    if (a == 0 || a == 2) {
+      for (int k = 0; k < 4; k++)
+        if (sv[k] >= 0 && fabs(sup_point_x(c, sv[k], t) - x) <= room) room = fabs(sup_point_x(c, sv[k], t) - x);
+    } else {
+      const int o = (lane == MM_LANE_AB0 || lane == MM_LANE_BC0 || lane == MM_LANE_CD0) ? sv[0] : sv[2];
+      if (o >= 0 && (sup_point_x(c, o, t) - x) <= room) room = sup_point_x(c, o, t) - x;
+    }
+    if (t == 0 || room < min_room) min_room = room;
+  }
+  return min_room;
+}
+
+/* per env: [order N][key N] then per slot [len, x, y, heading, speed, target speed, target lane, crashed, HDV steering,
+ * HDV acceleration] and n_points points of [x, y, heading, speed] (x = y = NaN: aliased) */
+static uint64_t sup_trace_doubles(int N, int n_points) { return (uint64_t)N * (2 + 10 + 4 * (uint64_t)n_points); }
+
+static void sup_one_env(const struct MMHandle_ *h, int64_t e_idx, int n_points, const int32_t *actions, const double *uniforms,
+                        int stride, int32_t *new_actions, int32_t *n_draws, double *trace, int64_t *cen) {
+  const int N = h->N;
+  int act[MM_MAX_AGENTS];
+  for (int v = 0; v < N; v++) act[v] = actions[v]; /* actions = list(actions) :21 */
+  Env env;
+  load_env(h, e_idx, &env);
+  if (trace) for (uint64_t k = 0; k < sup_trace_doubles(N, n_points); k++) trace[k] = 0;
+  if (env.n_ctrl == 0) { /* no controlled vehicle: nothing to supervise */
+    for (int v = 0; v < N; v++) new_actions[v] = act[v];
+    if (n_draws) *n_draws = 0;
+    return;
+  }
+  const int n = env.n_ctrl;
+  cen[SC_STATES]++;
+  SupCtx *c = (SupCtx *)malloc(sizeof *c);
+  /* trajectories of the road's vehicles, then two for the candidates of a replacement (the running one, the best so far) */
+  SupPoint *store = (SupPoint *)malloc(sizeof(SupPoint) * (size_t)(MM_MAX_AGENTS + 2) * (size_t)n_points);
+  c->env = env; /* env_copy = copy.deepcopy(env) :22 */
+  for (int v = 0; v < MM_MAX_AGENTS; v++) { c->len[v] = 0; c->traj[v] = store + (size_t)v * n_points; } /* :28-29 */
+  SupPoint *cand_traj = store + (size_t)MM_MAX_AGENTS * n_points, *best_traj = cand_traj + n_points;
+  c->n_points = n_points;
+  c->dt = 1.0 / h->cfg.simulation_frequency;
+  c->uniforms = uniforms; c->stride = stride; c->n_draws = 0;
+  c->seed = ((const uint64_t *)(h->state + h->lay.seed_offset))[e_idx];
+  c->episode = (uint32_t)env.episode; c->steps = (uint32_t)env.steps;
+  c->cen = cen;
+
+  /* ---- priority numbers :32-65; PriorityQueue.get() yields the smallest first */
+  int order[MM_MAX_AGENTS];
+  double key[MM_MAX_AGENTS];
+  for (int i = 0; i < n; i++) {
+    const Veh *v = &env.v[i];
+    double p = 0;
+    int src;
+    if (v->lane == MM_LANE_BC1) {
+      p = -0.5;
+      const double dme = (220.0 + 100.0 + 100.0) - v->x;
+      p -= (100.0 - dme) / 100.0;
+      cen[SC_KEY_RAMP]++;
+    }
+    const double hd = sup_headway_distance(&env, i, &src);
+    if (src == 0) cen[SC_KEY_NO_FRONT]++;
+    if (src == 2) cen[SC_KEY_NEXT_LANE]++;
+    if (v->speed > 0) p += 0.5 * m_log(hd / (h->cfg.headway_time * v->speed));
+    else { p += 0; cen[SC_KEY_SPEED_LE0]++; }
+    p += sup_rand(c) * 0.001;
+    key[i] = p;
+    order[i] = i;
+  }
+  for (int a = 1; a < n; a++) { /* stable insertion sort: the queue's order for distinct numbers */
+    const int o = order[a];
+    int b = a - 1;
+    while (b >= 0 && key[order[b]] > key[o]) { order[b + 1] = order[b]; b--; }
+    order[b + 1] = o;
+  }
+  for (int i = 0; i < n; i++) if (order[i] != i) { cen[SC_ORDER_DIFFERS]++; break; }
+
+  for (int i = 0; i < n; i++) {
+    const int idx = order[i];
+    int first_change = 1;
+    Veh *ego = &c->env.v[idx];
+    cen[SC_LOOKAHEADS]++;
+    if (c->len[idx] == n_points) { /* stepped before as a neighbour: a fresh copy of the original :72-78 */
+      *ego = env.v[idx];
+      c->len[idx] = 0;
+      cen[SC_EGO_RESET]++;
+    }
+    if (env.v[idx].crashed) cen[SC_EGO_CRASHED_START]++;
+    /* _get_available_actions abstract.py:219-240 */
+    int avail[5], na = 0;
+    avail[na++] = 1;
+    if (ego->lane == MM_LANE_BC1 && lane_is_reachable_from(MM_LANE_BC0, ego->x, ego->y)) avail[na++] = 0;
+    if (ego->lane == MM_LANE_BC0 && lane_is_reachable_from(MM_LANE_BC1, ego->x, ego->y)) avail[na++] = 2;
+    if (ego->speed_index < 5 - 1) avail[na++] = 3;
+    if (ego->speed_index > 0) avail[na++] = 4;
+    /* :85-110 neighbours: sv = [v_fl, v_rl, v_fr, v_rr] */
+    int sv[4] = {-1, -1, -1, -1};
+    const int lane = ego->lane;
+    if (lane == MM_LANE_AB0 || lane == MM_LANE_BC0 || lane == MM_LANE_CD0) {
+      surrounding_vehicles(&c->env, idx, lane, &sv[0], &sv[1]);
+      if (lane == MM_LANE_BC0) { surrounding_vehicles(&c->env, idx, MM_LANE_BC1, &sv[2], &sv[3]); cen[SC_Q_BC0_BC1]++; }
+      else if (lane == MM_LANE_AB0 && ego->x > 220.0) { surrounding_vehicles(&c->env, idx, MM_LANE_KB0, &sv[2], &sv[3]); cen[SC_Q_AB0_KB0]++; }
+      else cen[SC_Q_NONE]++;
+    } else {
+      surrounding_vehicles(&c->env, idx, lane, &sv[2], &sv[3]);
+      if (lane == MM_LANE_BC1) { surrounding_vehicles(&c->env, idx, MM_LANE_BC0, &sv[0], &sv[1]); cen[SC_Q_BC1_BC0]++; }
+      else if (lane == MM_LANE_KB0) { surrounding_vehicles(&c->env, idx, MM_LANE_AB0, &sv[0], &sv[1]); cen[SC_Q_KB0_AB0]++; }
+      else cen[SC_Q_NONE]++;
+    }
+    const int upd[5] = {sv[0], sv[2], idx, sv[1], sv[3]}; /* [v_fl, v_fr, vehicle, v_rl, v_rr] :115 */
+    for (int t = 0; t < n_points; t++) {
+      for (int k = 0; k < 5; k++) {
+        const int v = upd[k];
+        if (v < 0) continue;
+        if (c->len[v] == n_points && i != 0 && v != idx) { if (t == 0) cen[SC_NB_SKIPPED]++; continue; } /* :120 */
+        if (c->env.v[v].kind == 2) { /* type(v) is IDMVehicle: its action is decided at t == 0 */
+          if (t == 0) {
+            if (c->env.v[v].crashed) cen[SC_HDV_CRASHED_START]++;
+            sup_generate_actions(c, v);
+          }
+          sup_idm_controller(c, v);
+        } else if (v != idx) {
+          sup_mdp_controller(c, &c->env.v[v], c->traj[v], &c->len[v], act[0]); /* actions[v.id], id = 0 (controller.py:49) */
+        } else {
+          sup_mdp_controller(c, ego, c->traj[idx], &c->len[idx], act[idx]); /* :137-141: actions[index] either way */
+        }
+      }
+      /* check_collision abstract.py:721-742 against the neighbours' points of this sub-step, then the obstacle */
+      for (int k = 0; k < 4; k++) {
+        const int o = sv[k];
+        if (o < 0 || ego->crashed) continue;
+        SupPoint *p = &c->traj[o][t];
+        if (is_colliding(ego, sup_point_x(c, o, t), sup_point_y(c, o, t), VEH_LENGTH, VEH_WIDTH, p->heading)) {
+          const int other = fabs(p->speed) < fabs(ego->speed); /* min([speed, other], key=abs): the first on ties */
+          const double m = other ? p->speed : ego->speed;
+          ego->speed = m;
+          p->speed = m;
+          ego->crashed = 1;
+          c->env.v[o].crashed = 1;
+          cen[SC_COLL_FL + k]++;
+          cen[other ? SC_COLL_MIN_OTHER : SC_COLL_MIN_EGO]++;
+        }
+      }
+      if (!ego->crashed && is_colliding(ego, OBST_X, OBST_Y, OBST_LENGTH, OBST_WIDTH, 0.0)) {
+        ego->speed = fabs(0.0) < fabs(ego->speed) ? 0.0 : ego->speed;
+        ego->crashed = 1;
+        cen[SC_COLL_OBSTACLE]++;
+      }
+      if (!ego->crashed) continue;
+      /* :151-176 every available action replayed from the original vehicle; the first largest room wins */
+      int best = -1, best_len = 0, ties = 0;
+      double best_room = 0;
+      Veh best_v = env.v[idx];
+      for (int k = 0; k < na; k++) {
+        Veh copy = env.v[idx];
+        int len = 0;
+        const double room = sup_check_safety_room(c, &copy, cand_traj, &len, avail[k], sv, t);
+        if (best >= 0 && room == best_room) ties++;
+        if (best < 0 || room > best_room) {
+          best = k; best_room = room; best_v = copy; best_len = len; ties = 0;
+          memcpy(best_traj, cand_traj, sizeof(SupPoint) * (size_t)len);
+        }
+      }
+      if (ties) cen[SC_ROOM_TIE]++;
+      *ego = best_v;
+      memcpy(c->traj[idx], best_traj, sizeof(SupPoint) * (size_t)best_len);
+      c->len[idx] = best_len;
+      if (first_change) {
+        first_change = 0;
+        act[idx] = avail[best];
+        cen[SC_REPLACED]++;
+        if (avail[best] >= 0 && avail[best] <= 4) cen[SC_REPL_0 + avail[best]]++;
+      } else cen[SC_SECOND_REPLACEMENT]++;
+      for (int k = 0; k < 4; k++)
+        if (sv[k] >= 0 && c->env.v[sv[k]].crashed) { c->env.v[sv[k]].crashed = 0; cen[SC_NB_CRASH_CLEARED]++; }
+    }
+  }
+  for (int v = 0; v < N; v++) new_actions[v] = act[v];
+  if (n_draws) *n_draws = c->n_draws;
+  if (trace) {
+    for (int i = 0; i < n; i++) { trace[i] = order[i]; trace[N + i] = key[i]; }
+    double *tv = trace + 2 * N;
+    for (int v = 0; v < c->env.n; v++, tv += 10 + 4 * n_points) {
+      const Veh *q = &c->env.v[v];
+      tv[0] = c->len[v]; tv[1] = q->x; tv[2] = q->y; tv[3] = q->heading; tv[4] = q->speed; tv[5] = q->target_speed;
+      tv[6] = q->target_lane; tv[7] = q->crashed;
+      tv[8] = q->kind == 2 && c->len[v] ? q->act_steer : 0; tv[9] = q->kind == 2 && c->len[v] ? q->act_acc : 0;
+      for (int t = 0; t < c->len[v]; t++) {
+        const SupPoint *p = &c->traj[v][t];
+        tv[10 + 4 * t + 0] = p->aliased ? NAN : p->x; tv[10 + 4 * t + 1] = p->aliased ? NAN : p->y;
+        tv[10 + 4 * t + 2] = p->heading; tv[10 + 4 * t + 3] = p->speed;
+      }
+    }
+  }
+  free(store);
+  free(c);
+}
+
+int32_t mm_supervise_scratch_bytes(int32_t E, int32_t N, int32_t n_step, int32_t sub_steps, uint64_t *bytes) {
+  if (!bytes || E <= 0 || N <= 0 || N > MM_MAX_AGENTS || n_step < 1 || sub_steps < 1) return MM_ERR_INVALID_ARG;
+  *bytes = 8ull * (uint64_t)E * (uint64_t)N * (uint64_t)(10 + 4 * sub_steps * n_step);
+  return MM_OK;
+}
+
+int32_t mm_supervise(MMHandle h, int32_t kind, int32_t n_step, const int32_t *actions, const double *uniforms,
+                     int32_t uniform_stride, void *scratch, uint64_t scratch_bytes, int32_t *new_actions, int32_t *n_draws,
+                     MMStream stream) {
+  (void)stream;
+  if (!h) return MM_ERR_INVALID_ARG;
+  const MMConfig *cfg = &h->cfg;
+  const int32_t sub = cfg->policy_frequency > 0 ? cfg->simulation_frequency / cfg->policy_frequency : 0;
+  const int64_t np = (int64_t)sub * n_step;
+  if (cfg->env_kind != MM_ENV_V0 || kind != MM_SUP_PRIORITY || n_step < 1 || np < 1 || !actions || !new_actions || !scratch ||
+      ((uintptr_t)scratch & 7u) || (uniforms && uniform_stride < 9 * h->N) ||
+      scratch_bytes < 8ull * (uint64_t)h->E * (uint64_t)h->N * (uint64_t)(10 + 4 * np))
+    return MM_ERR_INVALID_ARG;
+  const uint64_t per_env = sup_trace_doubles(h->N, (int)np);
+  double *trace = g_sup_trace;
+  if (trace && g_sup_trace_len < per_env * (uint64_t)h->E) return MM_ERR_INVALID_ARG;
+  int64_t cen[SC_COUNT] = {0};
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : cen[:SC_COUNT])
+  for (int64_t e = 0; e < h->E; e++)
+    sup_one_env(h, e, (int)np, actions + e * h->N, uniforms ? uniforms + e * (int64_t)uniform_stride : NULL, uniform_stride,
+                new_actions + e * h->N, n_draws ? n_draws + e : NULL, trace ? trace + per_env * (uint64_t)e : NULL, cen);
+  memcpy(g_sup_census, cen, sizeof cen);
+  return MM_OK;
+}
+
+/* Oracle-only: from now on every mm_supervise call also reports, per env, the priority order and numbers and every
+ * vehicle's final lookahead copy (layout: sup_trace_doubles) into `trace` (n_doubles long; NULL: stop reporting). */
+void orc_supervise_trace(double *trace, uint64_t n_doubles) { g_sup_trace = trace; g_sup_trace_len = trace ? n_doubles : 0; }
+/* Oracle-only: the branch counters of the last mm_supervise call, summed over its envs; returns how many there are. */
+int32_t orc_supervise_census(int64_t *out, int32_t n) {
+  for (int k = 0; k < n && k < SC_COUNT; k++) out[k] = g_sup_census[k];
+  return SC_COUNT;
+}
+const char *orc_supervise_census_name(int32_t k) { return k >= 0 && k < SC_COUNT ? sup_census_names[k] : NULL; }
+
 int32_t mm_shield_actions(MMHandle h, const double *act_steer, const double *act_acc, double *safe_steer,
                           double *safe_acc, uint8_t *status, double *margin, double *headway, MMStream stream) {
   (void)stream;

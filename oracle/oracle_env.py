@@ -61,6 +61,12 @@ def library():
         lib.orc_batch_rect.argtypes = [i32] + [vp] * 3
         for n in ("orc_batch_pose", "orc_batch_steering", "orc_batch_rect"):
             getattr(lib, n).restype = None
+        # the supervisor twin's oracle-only exports (mm_oracle.c, "priority" supervisor)
+        lib.orc_supervise_trace.argtypes = [vp, C.c_uint64]
+        lib.orc_supervise_trace.restype = None
+        lib.orc_supervise_census.argtypes = [vp, i32]
+        lib.orc_supervise_census_name.argtypes = [i32]
+        lib.orc_supervise_census_name.restype = C.c_char_p
     return _LIB
 
 

@@ -19,7 +19,7 @@ Cases (marl/configs):
   v0prio  marl_cav-heading-t_headway-priority-mixed-shared.ini       v0, "priority" supervisor, mixed traffic, density 3
 For the v1 cases the SAME MAPPO_GI object code is first run on marl_mass_amd.compat.make(env_id) with the CPU oracle as
 backend and must draw the identical action sequence and match states / returns / ext_info to 1e-9 before anything is
-written.  The oracle has no supervisor, so v0prio is recorded from the reference alone (meta says so); the HIP backend
+written.  The oracle had no supervisor when v0prio was recorded, so it comes from the reference alone (meta says so); the HIP backend
 replays it in tests/test_mappo_gi_dropin.py.
 """
 import json
