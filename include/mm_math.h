@@ -219,6 +219,56 @@ MMM_FN double mmm_asin_w(double x, double *w_out) {
   return x < 0 ? -r : r;
 }
 MMM_FN double mmm_asin(double x) { double w; return mmm_asin_w(x, &w); }
+
+/* ---- select forms (the fused step kernels of marl-mass_amd/csrc choose them per instantiation; nothing else calls them) ----
+ * The same operations on the same operands as the functions above, so the same bits for every input (tests/
+ * test_combined_forms_host.py compares them on the corners); what differs is the shape of the code the GPU compiler makes of
+ * them.  mmm_sin / mmm_cos above are an if / else over the two polynomials -- an exec-mask region each, and a wave whose
+ * lanes sit in both quadrant parities runs both anyway -- and the nested conditionals on j in mmm_atan_ratio become a
+ * branch tree or a table in memory.  Here both polynomials run and one select per result picks, as in mmm_sincos, and hi / lo
+ * are a chain of selects on j with the constants as literals. */
+MMM_FN double mmm_sin_sel(double x) {
+  int q;
+  double r = mmm_reduce(x, &q);
+  double ks = mmm_ksin(r), kc = mmm_kcos(r);
+  double s = (q & 1) ? kc : ks;
+  return (q & 2) ? -s : s;
+}
+MMM_FN double mmm_cos_sel(double x) {
+  int q;
+  double r = mmm_reduce(x, &q);
+  double ks = mmm_ksin(r), kc = mmm_kcos(r);
+  double c = (q & 1) ? ks : kc;
+  return ((q + 1) & 2) ? -c : c;
+}
+MMM_FN double mmm_atan_ratio_sel(double num, double den, double *lo_out) {
+  const int j = (num >= 0.125 * den) + (num >= 0.375 * den) + (num >= 0.625 * den) + (num >= 0.875 * den);
+  double c = 0.25 * (double)j;
+  double t = (num - c * den) / (den + c * num); /* j == 0: num / den */
+  double z = t * t;
+  double p = MMM_K(mmm_t_atan, 0, MMM_A10);
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 1, MMM_A9)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 2, MMM_A8)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 3, MMM_A7)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 4, MMM_A6));
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 5, MMM_A5)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 6, MMM_A4)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 7, MMM_A3)); p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 8, MMM_A2));
+  p = mmm_fma_c(p, z, MMM_K(mmm_t_atan, 9, MMM_A1));
+  double pt = fma(t * z, p, t);
+  double hi = 0.0, lo = 0.0; /* j is 0 .. 4: the last select that holds is the entry of j */
+  hi = j >= 1 ? MMM_ATAN_HI_1 : hi; lo = j >= 1 ? MMM_ATAN_LO_1 : lo;
+  hi = j >= 2 ? MMM_ATAN_HI_2 : hi; lo = j >= 2 ? MMM_ATAN_LO_2 : lo;
+  hi = j >= 3 ? MMM_ATAN_HI_3 : hi; lo = j >= 3 ? MMM_ATAN_LO_3 : lo;
+  hi = j >= 4 ? MMM_ATAN_HI_4 : hi; lo = j >= 4 ? MMM_ATAN_LO_4 : lo;
+  *lo_out = lo;
+  return hi + (pt + lo);
+}
+MMM_FN double mmm_asin_w_sel(double x, double *w_out) {
+  double y = fabs(x), lo;
+  double w = sqrt((1.0 - y) * (1.0 + y));
+  *w_out = w;
+  const int direct = y <= w;
+  double r = mmm_atan_ratio_sel(direct ? y : w, direct ? w : y, &lo);
+  if (!direct) r = MMM_PIO2_HI - (r - MMM_PIO2_LO);
+  return x < 0 ? -r : r;
+}
+MMM_FN double mmm_asin_sel(double x) { double w; return mmm_asin_w_sel(x, &w); }
 /* sin / cos of the steering limit pi/3 (the double 0x1.0c152382d7365p+0), correctly rounded */
 #define MMM_SIN_PI3 0x1.bb67ae8584caap-1
 #define MMM_COS_PI3 0x1.0000000000001p-1

@@ -22,6 +22,28 @@
 
 namespace mm {
 
+// Select forms of the wave's short conditional regions ("the combined forms"), one switch each so that every
+// one can be timed alone (-DMM_..._SELECTS=0: the form it replaces).  They apply in the instantiations that pass SINE / kSine,
+// the same register gate; the same bits either way.
+#ifndef MM_TRIG_SELECTS
+#define MM_TRIG_SELECTS 1  // mmm_sin / mmm_cos: both polynomials and one select (include/mm_math.h: mmm_sin_sel, mmm_cos_sel)
+#endif
+#ifndef MM_ATAN_SELECTS
+#define MM_ATAN_SELECTS 1  // mmm_atan_ratio's hi / lo as a chain of selects on j (mmm_atan_ratio_sel)
+#endif
+#ifndef MM_CORNER_SELECTS
+#define MM_CORNER_SELECTS 1  // corner_flags (mm_kernels.hip)
+#endif
+#ifndef MM_CLIP_SELECTS
+#define MM_CLIP_SELECTS 1  // clip_actions (mm_kernels.hip)
+#endif
+constexpr bool kTrigSelects = MM_TRIG_SELECTS != 0, kAtanSelects = MM_ATAN_SELECTS != 0;
+constexpr bool kCornerSelects = MM_CORNER_SELECTS != 0, kClipSelects = MM_CLIP_SELECTS != 0;
+template <bool SEL> MM_DEV double sin_f(double x) { if constexpr (SEL && kTrigSelects) return mmm_sin_sel(x); else return mmm_sin(x); }
+template <bool SEL> MM_DEV double cos_f(double x) { if constexpr (SEL && kTrigSelects) return mmm_cos_sel(x); else return mmm_cos(x); }
+template <bool SEL> MM_DEV double asin_f(double x) { if constexpr (SEL && kAtanSelects) return mmm_asin_sel(x); else return mmm_asin(x); }
+template <bool SEL> MM_DEV double asin_w_f(double x, double *w) { if constexpr (SEL && kAtanSelects) return mmm_asin_w_sel(x, w); else return mmm_asin_w(x, w); }
+
 constexpr double kPi = 3.141592653589793;  // np.pi
 constexpr double kVehLength = 5.0, kVehWidth = 2.0, kMaxSpeed = 40.0;    // kinematics.py:27-33
 constexpr double kTauA = 0.6, kTauDs = 0.2;                               // controller.py:23-24
@@ -98,20 +120,22 @@ MM_DEV double div_c(double x, double d, double y) {
 #define MM_DIVC(x, d) ::mm::div_c((x), (d), 1.0 / (d))  // d must be a compile-time constant
 
 // ---- road/lane.py -----------------------------------------------------------------------------
+template <bool SEL = false>  // SEL: the select forms of the elementary functions (sin_f ... above), where the kernel passes SINE
 MM_DEV void lane_local(int l, double x, double y, double &s, double &r) {  // lane.py:164-168,208-210
   s = x - lane_sx(l);
   r = y - lane_sy(l);
-  if (l == MM_LANE_KB0) r = r - kSineAmp * mmm_sin(kSinePuls * s + kSinePhase);
+  if (l == MM_LANE_KB0) r = r - kSineAmp * sin_f<SEL>(kSinePuls * s + kSinePhase);
 }
 // The same with the sine of kb0's frame at this x as the caller carried it (`car`; NaN: not known -- closest_lane<true> formed
 // it for the pose the vehicle then committed): one wave-uniform test decides whether any lane still needs a sine of its own.
 // The argument is the one closest_lane forms (x - 220 is x - lane_sx(kb0)), so the carried value has mmm_sin's bits.
+template <bool SEL = false>
 MM_DEV void lane_local_carried(int l, double x, double y, double car, double &s, double &r) {
   s = x - lane_sx(l);
   r = y - lane_sy(l);
   const bool kb = l == MM_LANE_KB0;
   double sn = car;
-  if (__any(kb && car != car)) sn = (car != car) ? mmm_sin(kSinePuls * s + kSinePhase) : car;
+  if (__any(kb && car != car)) sn = (car != car) ? sin_f<SEL>(kSinePuls * s + kSinePhase) : car;
   if (kb) r = r - kSineAmp * sn;
 }
 // the sine lane's slope is at most kSineAmp * kSinePuls = 0.1021 (mmm_cos may overshoot 1 by an ulp or two): mmm_atan_small's
@@ -122,7 +146,7 @@ static_assert(kSineAmp * kSinePuls * (1.0 + 0x1p-40) < 0.125, "the sine lane's h
 // forms change its register allocation: see kSine in step_kernel
 template <bool SINE = false>
 MM_DEV double lane_heading_at(int l, double s) {  // lane.py:158-159, :204-206
-  if constexpr (SINE) return l == MM_LANE_KB0 ? 0.0 + mmm_atan_small(kSineAmp * kSinePuls * mmm_cos(kSinePuls * s + kSinePhase)) : 0.0;
+  if constexpr (SINE) return l == MM_LANE_KB0 ? 0.0 + mmm_atan_small(kSineAmp * kSinePuls * cos_f<true>(kSinePuls * s + kSinePhase)) : 0.0;
   else return l == MM_LANE_KB0 ? 0.0 + mmm_atan(kSineAmp * kSinePuls * mmm_cos(kSinePuls * s + kSinePhase)) : 0.0;
 }
 MM_DEV double lane_distance(int l, double x, double y) {  // lane.py:97-100
@@ -209,18 +233,18 @@ template <bool SINE = false, bool CARRIED = false>
 MM_DEV double steering_control(double x, double y, double heading, double speed, int tl, double &half_tan, double car = 0.0) {  // :146-187
   constexpr double KP_HEADING = 1 / kTauDs, KP_LATERAL = 1.0 / 3 * KP_HEADING, PURSUIT_TAU = 0.5 * kTauDs;
   double s, r;
-  if constexpr (CARRIED) lane_local_carried(tl, x, y, car, s, r);
-  else lane_local(tl, x, y, s, r);
+  if constexpr (CARRIED) lane_local_carried<SINE>(tl, x, y, car, s, r);
+  else lane_local<SINE>(tl, x, y, s, r);
   double lane_next = s + speed * PURSUIT_TAU;
   double lfh = lane_heading_at<SINE>(tl, lane_next);
   double lat_cmd = -KP_LATERAL * r;
   double nz = not_zero(speed);
-  double heading_command = mmm_asin(clipd(lat_cmd / nz, -1, 1));
+  double heading_command = asin_f<SINE>(clipd(lat_cmd / nz, -1, 1));
   double heading_ref = lfh + clipd(heading_command, -kPi / 4, kPi / 4);
   double rate = KP_HEADING * wrap_to_pi(heading_ref - heading);
   const double arg = clipd(kVehLength / 2 / nz * rate, -1, 1);
   double w;
-  const double steer = mmm_asin_w(arg, &w);
+  const double steer = asin_w_f<SINE>(arg, &w);
   const bool sat = fabs(steer) > kPi / 3;
   const double ss = sat ? (arg < 0 ? -MMM_SIN_PI3 : MMM_SIN_PI3) : arg;
   const double cs = sat ? MMM_COS_PI3 : w;

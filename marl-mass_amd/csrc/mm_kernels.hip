@@ -164,6 +164,14 @@ enum { MM_CS_UPFRONT_CYCLES = 16,  // cycles between "predict A" and the veto pa
 static_assert(MM_CS_DIAG_CYCLES == 31, "sixteen slots: lanes 16 .. 31");
 constexpr bool mm_cs_is_cycles(int slot) { return slot == MM_CS_UPFRONT_CYCLES || slot == MM_CS_ROUND_CYCLES || slot == MM_CS_DIAG_CYCLES; }
 __device__ unsigned long long g_stamps_c[MM_STAMP_WAVES * 16];
+// Wave-slot timeline (tools/wave_slots.py): ONE record per wave of the LAST step_kernel launch, overwritten by every launch, not
+// summed -- when the wave began and ended (s_memtime, the shader clock, whose origin differs from place to place on the chip: good
+// for differences inside one wave slot only; s_memrealtime, the 100 MHz clock the whole chip shares),
+// where it ran (HW_ID: wave slot, SIMD, CU, SH, SE; XCC_ID) and this launch's own value of each of the 32 stamp / count slots
+// above (veto passes, rounds, lazy candidates, literal fallback ...) plus the number of its envs that re-spawned.
+#define MM_REC_WAVES (1 << 14)
+enum { MM_REC_BEGIN, MM_REC_END, MM_REC_RT_BEGIN, MM_REC_RT_END, MM_REC_HW, MM_REC_RESPAWN, MM_REC_SLOTS = 8, MM_REC_WORDS = 40 };
+__device__ unsigned long long g_wave_rec[MM_REC_WAVES * MM_REC_WORDS];
 #define CAND_COUNT(k, cond)                                                                                  \
   do {                                                                                                       \
     const unsigned long long _m = __ballot(cond);                                                            \
@@ -271,6 +279,11 @@ constexpr bool kRoundsPrior = MM_ROUNDS_PRIOR != 0;
 #define MM_SCAN_SELECTS 1
 #endif
 constexpr bool kScanSelects = MM_SCAN_SELECTS != 0;
+// step_kernel's prologue issues the action load and the env's n_merge / episode loads together with the state loads instead of
+// behind them (kEarly below; -DMM_EARLY_LOADS=0: A-B timing without it)
+#ifndef MM_EARLY_LOADS
+#define MM_EARLY_LOADS 1
+#endif
 #ifndef MM_VETO_PRIOR
 #define MM_VETO_PRIOR 1
 #endif
@@ -426,22 +439,50 @@ MM_DEV void hl_act(Veh &v, int action) {
 }
 
 // kinematics.py:143-152 clip_actions (+ safe_controller.py:100-104)
+// SEL (kClipSelects, in the kSine kernels): the three ifs as selects -- every right-hand side is a few instructions on values
+// the lane holds anyway, so each is evaluated and a v_cndmask keeps or drops it; the same bits
+template <bool SEL = false>
 MM_DEV void clip_actions(Veh &v, bool lc_vehicle, double &st_t) {
+  if constexpr (SEL && kClipSelects) {
+    const bool cr = v.crashed != 0;
+    v.act_steer = cr ? 0.0 : v.act_steer; st_t = cr ? 0.0 : st_t;
+    double acc = cr ? -1.0 * v.v : v.act_acc;
+    const double room = 1.0 * (kMaxSpeed - v.v);
+    const bool over = v.v > kMaxSpeed, under = !over & (v.v < -kMaxSpeed);
+    const double a_lo = fmin(acc, room), a_hi = fmax(acc, room);
+    acc = over ? a_lo : (under ? a_hi : acc);
+    const double a_lc = clipd(acc, kLcMinAcc, kLcMaxAcc);
+    v.act_acc = lc_vehicle ? a_lc : acc;
+  } else {
   if (v.crashed) { v.act_steer = 0; st_t = 0; v.act_acc = -1.0 * v.v; }
   if (v.v > kMaxSpeed) v.act_acc = fmin(v.act_acc, 1.0 * (kMaxSpeed - v.v));
   else if (v.v < -kMaxSpeed) v.act_acc = fmax(v.act_acc, 1.0 * (kMaxSpeed - v.v));
   if (lc_vehicle) v.act_acc = clipd(v.act_acc, kLcMinAcc, kLcMaxAcc);  // MDPLCVehicle only
+  }
 }
 
 // controller.py:257-267 get_corner("L"/"R") + lane.on_lane of those corners on `lane`
 // -> bit0: the front-left corner is off `lane`, bit1: the front-right one
 // (the three corner angles alpha + h, -alpha + h as angle sums from sin h, cos h: include/mm_math.h "angle-sum forms")
+// SEL (kCornerSelects, in the kSine kernels): the sine stays behind its lane == kb0 test, `off` is selected after it, and the
+// `lon &&` tests and the two kb0 offsets are & / selects: one conditional region (the sine) instead of five; the same bits
+template <bool SEL = false>
 MM_DEV int corner_flags(double x, double y, double sh, double ch, int lane) {
   double cx = x + (kCornerLen * mmm_cos_sum(MMM_CORNER_SIN, MMM_CORNER_COS, sh, ch));
   double cyL = y - (kCornerLen * mmm_sin_sum(MMM_CORNER_SIN, MMM_CORNER_COS, sh, ch)) + 0.01;
   double cyR = y - (kCornerLen * mmm_sin_sum(-MMM_CORNER_SIN, MMM_CORNER_COS, sh, ch)) + 0.01;
   double s = cx - lane_sx(lane);
-  double off = (lane == MM_LANE_KB0) ? kSineAmp * mmm_sin(kSinePuls * s + kSinePhase) : 0.0;
+  if constexpr (SEL && kCornerSelects) {
+    const bool kb = lane == MM_LANE_KB0;
+    double sn = 0.0;
+    if (kb) sn = sin_f<true>(kSinePuls * s + kSinePhase);
+    const double off = kb ? kSineAmp * sn : 0.0;
+    const bool lon = (-kVehLength <= s) & (s < lane_len(lane) + kVehLength);
+    const double rL0 = cyL - lane_sy(lane), rR0 = cyR - lane_sy(lane);
+    const double rL = kb ? rL0 - off : rL0, rR = kb ? rR0 - off : rR0;
+    return (!((fabs(rL) <= kLaneWidth / 2 + 0) & lon) ? 1 : 0) | (!((fabs(rR) <= kLaneWidth / 2 + 0) & lon) ? 2 : 0);
+  }
+  double off = (lane == MM_LANE_KB0) ? kSineAmp * sin_f<SEL>(kSinePuls * s + kSinePhase) : 0.0;
   bool lon = (-kVehLength <= s && s < lane_len(lane) + kVehLength);
   double rL = cyL - lane_sy(lane), rR = cyR - lane_sy(lane);
   if (lane == MM_LANE_KB0) { rL = rL - off; rR = rR - off; }
@@ -490,7 +531,7 @@ MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double c
   c.gvx = (KIND == MM_ENV_V1) ? mmm_cos_sum(c.spsi, c.cpsi, sb, cb) : 0.0;
   c.lane = closest_lane<SINE>(c.x, c.y, c.h, sine_out);  // on_state_update kinematics.py:154-159 (sine_out: see closest_lane)
   c.pk = c.lane;
-  if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
+  if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags<SINE>(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
   return c;
 }
 
@@ -1633,6 +1674,12 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #define MM_SINE_CARRY 0
 #endif
   constexpr bool kSineCarry = kPrimary && MM_SINE_CARRY != 0;
+  // kEarly: the action and the env's n_merge / episode are loaded in front of the state loads, whose address they do not
+  // depend on, instead of behind the `kind` load (the action) and in front of the outputs (the two counters): three
+  // round trips to memory that now overlap the state's.  The CAV-only kernels need no `kind` to address actions[i]; the value
+  // is masked afterwards.  The counters wait in the free high words of two cold slots of the lane's own column (the pose-code
+  // and rank-word slots hold an int in their low word: !kPackMsg), not in registers.  In the kSine kernels: same register gate.
+  constexpr bool kEarly = kSine && MM_EARLY_LOADS != 0;
   double car_sn = __builtin_nan("");
   (void)car_sn;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
@@ -1651,6 +1698,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   const double dt = c.dt;
 
 #ifdef MM_STAMPS
+  const unsigned long long _rec_t0 = __builtin_amdgcn_s_memtime(), _rec_rt0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long _t_last = __builtin_amdgcn_s_memtime(), _t_acc = 0;
 #endif
   Veh v;
@@ -1659,6 +1707,12 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   int car_code = 0;
   long long car_kx = 0, car_ky = 0, car_kh = 0;
   double car_s = 0.0, car_c = 1.0;
+  int act_raw = 1;
+  (void)act_raw;
+  if constexpr (kEarly) {
+    if (valid) act_raw = actions[i];
+    if (e < st.E) { n_merge = st.I[MM_E_N_MERGE * st.E + e]; episode = st.I[MM_E_EPISODE * st.E + e]; }
+  }
   if constexpr (kCarry) {
     if (valid) {
       car_kx = __double_as_longlong(pb.F[PB_KX * A + i]); car_ky = __double_as_longlong(pb.F[PB_KY * A + i]);
@@ -1669,7 +1723,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   load_veh(st, i, valid, v, sv);
   if (e < st.E) {
     steps = st.I[MM_E_STEPS * st.E + e]; time = st.I[MM_E_TIME * st.E + e];
-    // n_merge / episode are only needed by the epilogue: loaded there, not held across the sub-steps
+    // n_merge / episode are only needed by the epilogue: loaded there (kEarly: above, and parked), not held across the sub-steps
   }
   if (!MIXED && v.kind == 2) v.kind = 1;  // CAV-only kernels: the host guarantees there are no HDVs
   if (IDM && v.present) v.kind = 2;        // hdv-v1: whatever the planes say, every vehicle is an HDV
@@ -1678,7 +1732,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // and the headway below run over road.vehicles (MergeEnvLCHDV.step, merge_env_v1.py:604-666) -- it reads no action
   const bool ctrl = IDM ? v.present : (v.present && !hdv);
   const bool ctrl_x = IDM ? false : ctrl;  // vehicles whose x < 0 ends the episode (hdv-v1: none, :671-674)
-  int action = (!IDM && valid && ctrl) ? actions[i] : 1;  // (hdv-v1: step(None), actions may be NULL)
+  int action;
+  if constexpr (kEarly) action = ctrl ? act_raw : 1;  // (ctrl implies valid)
+  else action = (!IDM && valid && ctrl) ? actions[i] : 1;  // (hdv-v1: step(None), actions may be NULL)
   if ((unsigned)action > 4u) {  // self.actions[action]: KeyError in the reference (action.py:194-196) -> latched, acts as IDLE
     if (!SPLIT || kb == 0) atomicOr(c.err, MM_LATCH_BAD_ACTION);
     action = 1;
@@ -1701,7 +1757,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   }
   if (!carried) {
     if (v.present) mmm_sincos(v.h, &spsi, &cpsi);
-    if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags(v.x, v.y, spsi, cpsi, v.lane) : 0);
+    if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, spsi, cpsi, v.lane) : 0);
   }
 
   // Register relief: lane-private values that are written once and read rarely live in LDS ("cold"
@@ -1732,6 +1788,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     s_cold[C_SSTEER][tid] = v.safe_steer; s_cold[C_SACC][tid] = v.safe_acc;
   }
   s_cold[C_TSPEED][tid] = v.tspeed;
+  if constexpr (kEarly) {
+    static_assert(kMailbox && !kPackMsg, "the high words of the pose-code and rank-word slots must be free");
+    ((int *)&s_cold[C_PRE + 3][tid])[1] = n_merge; ((int *)&s_cold[C_MSGW][tid])[1] = episode;
+  }
   // (form / slot selection is `if constexpr` throughout: an instantiation contains no code for slots it does not own)
   if constexpr (kRoomy) { s_cold[C_CPSI][tid] = cpsi; s_cold[C_GVX][tid] = v.gvx; }
   auto CPSI = [&]() -> double { if constexpr (kRoomy) return s_cold[C_CPSI][tid]; else return cpsi; };
@@ -1884,11 +1944,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         const double steer = steering_control<kSine, kSineCarry>(v.x, v.y, v.h, v.v, tl_1, st_t, car_sn);
         v.act_steer = clipd(steer, -kPi / 3, kPi / 3);
         const double steer_1 = v.act_steer, st_t_1 = st_t;
-        clip_actions(v, LC, st_t);
+        clip_actions<kSine>(v, LC, st_t);
         if (first_B) { v.act_steer = steer_1; st_t = st_t_1; }  // (a crashed vehicle's steering is zeroed in candidate A only: B keeps its command)
       }
     } else {
-      if (live && head) clip_actions(v, LC && !hdv, st_t);
+      if (live && head) clip_actions<kSine>(v, LC && !hdv, st_t);
     }
     STAMP(1);  // act
     // predicted post-state for the nominal steering (the only one when nothing vetoes; kPrimary: for this lane's first candidate)
@@ -2777,7 +2837,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     th = h2d / (vx > 1 ? vx : 1);
   }
   const double min_headway = group_min_d<G>(th, a);
-  if (e < st.E) { n_merge = st.I[MM_E_N_MERGE * st.E + e]; episode = st.I[MM_E_EPISODE * st.E + e]; }
+  if constexpr (kEarly) { n_merge = ((const int *)&s_cold[C_PRE + 3][tid])[1]; episode = ((const int *)&s_cold[C_MSGW][tid])[1]; }
+  else if (e < st.E) { n_merge = st.I[MM_E_N_MERGE * st.E + e]; episode = st.I[MM_E_EPISODE * st.E + e]; }
   double merge_pct = __builtin_nan("");
   if (done) {
     const int n_rem = __popc(group_ballot<G>(
@@ -2871,7 +2932,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       spsi = 0.0; cpsi = 1.0;  // heading 0
       if constexpr (kCarry) {  // what the next launch would derive for the spawned pose, by the very calls it would make
         mmm_sincos(v.h, &car_s, &car_c);
-        pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags(v.x, v.y, car_s, car_c, v.lane) : 0);
+        pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, car_s, car_c, v.lane) : 0);
       }
       s_cold[C_H1X][tid] = v.h1x; s_cold[C_H1VX][tid] = v.h1vx; s_cold[C_H2X][tid] = v.h2x; s_cold[C_H2VX][tid] = v.h2vx;
       s_cold[C_SSTEER][tid] = v.safe_steer; s_cold[C_SACC][tid] = v.safe_acc; s_cold[C_TSPEED][tid] = v.tspeed;
@@ -2907,6 +2968,20 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     const long long wv = gtid >> 6;
     if ((threadIdx.x & 63) < 16 && wv < MM_STAMP_WAVES) g_stamps_w[wv * 16 + (threadIdx.x & 63)] += _t_acc;
     else if ((threadIdx.x & 63) < 32 && wv < MM_STAMP_WAVES) g_stamps_c[wv * 16 + (threadIdx.x & 63) - 16] += _t_acc;
+    if (wv < MM_REC_WAVES) {
+      unsigned long long *rec = g_wave_rec + wv * MM_REC_WORDS;
+      const int respawned = __popcll(__ballot(c.auto_reset && done && a == 0 && e < st.E));
+      if ((threadIdx.x & 63) < 32) rec[MM_REC_SLOTS + (threadIdx.x & 63)] = _t_acc;
+      if ((threadIdx.x & 63) == 0) {
+        // s_getreg_b32 of the whole HW_REG_HW_ID (id 4) and HW_REG_XCC_ID (id 20): simm16 = id | offset << 6 | (size - 1) << 11
+        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+        rec[MM_REC_BEGIN] = _rec_t0; rec[MM_REC_RT_BEGIN] = _rec_rt0;
+        rec[MM_REC_HW] = (unsigned long long)hw | (unsigned long long)xcc << 32;
+        rec[MM_REC_RESPAWN] = (unsigned long long)respawned;
+        rec[MM_REC_RT_END] = __builtin_amdgcn_s_memrealtime();
+        rec[MM_REC_END] = __builtin_amdgcn_s_memtime();
+      }
+    }
   }
 #endif
 }
@@ -4174,6 +4249,12 @@ extern "C" int32_t mm_debug_read_stamps(unsigned long long *out16, int32_t reset
     memset(host, 0, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
     rc = hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_w), host, sizeof(unsigned long long) * MM_STAMP_WAVES * 16);
   }
+  return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+// the wave records of the last step_kernel launch, raw: out[n_waves][MM_REC_WORDS] (n_waves <= MM_REC_WAVES)
+extern "C" int32_t mm_debug_read_wave_records(unsigned long long *out, int32_t n_waves) {
+  if (!out || n_waves <= 0 || n_waves > MM_REC_WAVES) return MM_ERR_INVALID_ARG;
+  hipError_t rc = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_rec), sizeof(unsigned long long) * MM_REC_WORDS * (size_t)n_waves);
   return rc == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
 // out32[k], k = slot - 16: the cycle sum (the slots of mm_cs_is_cycles) or the lanes counted; out32[16 + k]: the waves counted
