@@ -117,18 +117,24 @@ def check_supervisor(value):
             "this path: set env.config['safety_guarantee'] to 'none' or 'cbf-*' before stepping" % (value,))
 
 
-SUP_NONE, SUP_PRIORITY = 0, 1  # include/mm_supervisor.h
+SUP_NONE, SUP_PRIORITY, SUP_DMC = 0, 1, 2  # include/mm_supervisor.h
+DMC_LITERAL = 1  # MM_DMC_LITERAL
+DMC_TRACE_DOUBLES = 20  # MM_DMC_TRACE_DOUBLES
 
 
-def supervisor_id(value, env_kind):
+def supervisor_id(value, env_kind, dmc=False):
     """config["safety_guarantee"] -> the supervisor AbstractEnv.step runs (abstract.py:460-464): SUP_PRIORITY for "priority"
     on merge-multi-agent-v0 (mm_supervise, include/mm_supervisor.h), SUP_NONE for everything without one.  "dmc" and
     "priority" on v1 still raise NotImplementedError through check_supervisor.  merge-multi-agent-hdv-v1 runs none whatever
-    the setting: MergeEnvLCHDV.step never calls a supervisor (merge_env_v1.py:604-666)."""
+    the setting: MergeEnvLCHDV.step never calls a supervisor (merge_env_v1.py:604-666).
+    dmc=True (the caller opted in, VecMergeEnv(enable_dmc=True)): "dmc" on merge-multi-agent-v0 is SUP_DMC (mm_supervise_dmc);
+    on v1 it still raises."""
     if env_kind == ENV_HDV_V1:
         return SUP_NONE
     if value == "priority" and env_kind == ENV_V0:
         return SUP_PRIORITY
+    if dmc and value == "dmc" and env_kind == ENV_V0:
+        return SUP_DMC
     check_supervisor(value)
     return SUP_NONE
 
@@ -298,6 +304,13 @@ class CLib(object):
             lib.mm_supervise_scratch_bytes.restype = i32
             lib.mm_supervise.argtypes = [vp, i32, i32, vp, vp, i32, vp, u64, vp, vp, vp]
             lib.mm_supervise.restype = i32
+        # the "dmc" supervisor (include/mm_supervisor.h, mm_supervise_dmc): an optional export like the other late entries
+        self.has_supervisor_dmc = hasattr(lib, "mm_supervise_dmc") and hasattr(lib, "mm_supervise_dmc_scratch_bytes")
+        if self.has_supervisor_dmc:
+            lib.mm_supervise_dmc_scratch_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(u64)]
+            lib.mm_supervise_dmc_scratch_bytes.restype = i32
+            lib.mm_supervise_dmc.argtypes = [vp, i32, C.c_uint32, vp, vp, i32, vp, u64, vp, vp, vp, vp]
+            lib.mm_supervise_dmc.restype = i32
         # MAPPO_GI's shared actor-critic + sample in one launch (include/mm_policy_gi.h), also libmm_hip.so only
         self.has_policy_gi = hasattr(lib, "mm_policy_gi_act")
         if self.has_policy_gi:
@@ -388,6 +401,15 @@ class CLib(object):
         self.require_supervisor()
         b = C.c_uint64()
         self.check(self.lib.mm_supervise_scratch_bytes(E, N, n_step, sub_steps, C.byref(b)))
+        return b.value
+
+    def supervise_dmc_scratch_bytes(self, E, N, n_step, sub_steps=3):
+        """Bytes of the scratch mm_supervise_dmc needs (include/mm_supervisor.h)."""
+        if not self.has_supervisor_dmc:
+            raise NotImplementedError("%s does not export mm_supervise_dmc: safety_guarantee='dmc' needs the HIP library"
+                                      % os.path.basename(self.path))
+        b = C.c_uint64()
+        self.check(self.lib.mm_supervise_dmc_scratch_bytes(E, N, n_step, sub_steps, C.byref(b)))
         return b.value
 
     def require_supervisor(self):

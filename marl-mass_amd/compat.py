@@ -154,12 +154,15 @@ class MergeEnvCompat(object):
     metadata = {"render.modes": []}
 
     def __init__(self, env_id="merge-multi-agent-v0", config=None, backend_factory=None, device="cuda:0",
-                 store_profile=False):
-        """`store_profile=True` keeps the per-sub-step control profile of every vehicle
+                 store_profile=False, enable_dmc=False):
+        """`enable_dmc=True`: config["safety_guarantee"] = "dmc" runs safety_layer_dmc on the device (VecMergeEnv(enable_dmc=True));
+        without it the setting raises NotImplementedError from step(), as before.
+        `store_profile=True` keeps the per-sub-step control profile of every vehicle
         (`state_hist` / `action_hist`, safe_controller.py:187-227, behavior.py:505-521) -- what
         MAPPOControlEval.evaluation (marl/mappo.py:420-438) hands to log_profiles; see control_profile()."""
         self.env_id = env_id
         self.store_profile = bool(store_profile)
+        self.enable_dmc = bool(enable_dmc)
         self.config = abi.default_env_config(env_id)
         if config:
             self.config.update(config)
@@ -217,7 +220,8 @@ class MergeEnvCompat(object):
         if self._b is None:
             self._b = self._factory(E=1, N=MAX_VEHICLES, env_id=self.env_id, config=self.config,
                                     cbf_eta=CBFType.GAMMA_B, cbf_tau=CBFType.TAU, obs_f64=True,
-                                    trace=self.store_profile, qp_solver=CBFType.QP_SOLVER)
+                                    trace=self.store_profile, qp_solver=CBFType.QP_SOLVER,
+                                    **({"enable_dmc": True} if self.enable_dmc else {}))
         return self._b
 
     # -- Env API ------------------------------------------------------------------------------
@@ -298,13 +302,15 @@ class MergeEnvCompat(object):
         b = self._b
         act = torch.ones(1, MAX_VEHICLES, dtype=torch.int32)
         act[0, :n] = torch.tensor(action, dtype=torch.int32)
-        sup = abi.supervisor_id(self.config.get("safety_guarantee"), abi.ENV_V1 if self.env_id == "merge-multi-agent-v1" else abi.ENV_V0)
+        sup = abi.supervisor_id(self.config.get("safety_guarantee"), abi.ENV_V1 if self.env_id == "merge-multi-agent-v1" else abi.ENV_V0,
+                                dmc=self.enable_dmc)
         if sup != abi.SUP_NONE:
             # safety_supervisor draws np.random.rand() from the global stream (central_layer.py:58): hand the device the next
             # 9 N values, then advance the stream by exactly the number it used, so that the caller's own draws
-            # (MAPPO's np.random.choice) continue where they would in the reference
+            # (MAPPO's np.random.choice) continue where they would in the reference.  safety_layer_dmc draws n_cav + 2 n_hdv
+            # values (decentralised_dmc.py:115, idm_controller.py:67,74): 2 N cover it
             st = np.random.get_state()
-            u = np.random.random_sample(9 * b.N)
+            u = np.random.random_sample((2 if sup == abi.SUP_DMC else 9) * b.N)
             np.random.set_state(st)
             obs, reward, done, out = b.step(act.to(b.device), uniforms=torch.as_tensor(u)[None])
             n_used = int(b.n_draws[0])

@@ -5,8 +5,9 @@
 // move in place, with the crash -> best-safety-room replacement of abstract.py:242-280.  The lookahead copy (live state
 // and every stored trajectory point) lives in the caller's scratch buffer, laid out [field][slot][env] so that the lanes
 // of a wave touch consecutive doubles.  The arithmetic is the step kernel's (mm_device.h, include/mm_math.h); only the
-// integrator of mdp_controller.py:19-64 differs from Vehicle.step (no speed floor, no lane update).
-#include "mm_device.h"
+// integrator of mdp_controller.py:19-64 differs from Vehicle.step (no speed floor, no lane update).  The helpers it shares
+// with the "dmc" supervisor (mm_supervisor_dmc.hip) are in mm_supervisor_dev.h.
+#include "mm_supervisor_dev.h"
 #include "../../include/mm_supervisor.h"
 
 #include "mm_handle.h"
@@ -23,7 +24,6 @@ enum { LX = 0, LY, LH, LV, LTS, LTL, LCR, LLEN, LHS, LHA };
 // per trajectory point: x, y, heading, speed.  x = NaN: the point of a crashed HDV, whose position idm_controller
 // appends WITHOUT a copy (idm_controller.py:42-44): it reads as the vehicle's live position
 constexpr int kTraj = 4;
-constexpr uint32_t kDomain = 0x53555056u;  // Philox domain word of the supervisor's draws
 
 struct Args {
   const double *f64;  // [MM_F_COUNT][E*N]
@@ -46,72 +46,6 @@ struct View {  // one env's slice of the scratch buffer
   MM_DEV double &live(int f, int v) const { return p[((long long)f * N + v) * E]; }
   MM_DEV double &traj(int t, int f, int v) const { return p[((long long)kLive * N + ((long long)t * kTraj + f) * N + v) * E]; }
 };
-
-// surrounding_vehicles (road.py:294-346): which lanes a query on lane `q` accepts
-MM_DEV bool accepts(int q, int l) {
-  switch (q) {
-    case MM_LANE_AB0: return l == MM_LANE_AB0 || l == MM_LANE_BC0;
-    case MM_LANE_BC0: return l == MM_LANE_AB0 || l == MM_LANE_BC0 || l == MM_LANE_CD0;
-    case MM_LANE_CD0: return l == MM_LANE_BC0 || l == MM_LANE_CD0;
-    case MM_LANE_JK0: return l == MM_LANE_JK0 || l == MM_LANE_KB0;
-    case MM_LANE_KB0: return l == MM_LANE_JK0 || l == MM_LANE_KB0 || l == MM_LANE_BC1;
-    default: return l == MM_LANE_KB0 || l == MM_LANE_BC1;  // bc1
-  }
-}
-MM_DEV bool is_main(int l) { return l == MM_LANE_AB0 || l == MM_LANE_BC0 || l == MM_LANE_CD0; }
-
-// mdp_controller.py:19-64 on a state held in registers; returns nothing, advances (x, y, h, v, ts, tl)
-MM_DEV void mdp_step(double &x, double &y, double &h, double &v, double &ts, int &tl, bool crashed, int action, double dt) {
-  if (lane_after_end(tl, x)) tl = next_lane(tl, x, y);  // follow_road :67-73
-  if (action == 3) ts += 5;
-  else if (action == 4) ts -= 5;
-  else if (action == 2 || action == 0) {
-    int cand = tl;  // np.clip(_id -/+ 1, ...): only road (b,c) has two lanes
-    if (lane_road(tl) == 1) cand = action == 2 ? MM_LANE_BC1 : MM_LANE_BC0;
-    if (lane_reachable(cand, x, y)) tl = cand;
-  }
-  double ht;
-  steering_control(x, y, h, v, tl, ht);  // clipped to +-pi/3 already (:52 clips again: no-op)
-  double acc = (1 / kTauA) * (ts - v);  // speed_control :107-115
-  if (crashed) { ht = 0.0; acc = -1.0 * v; }  // clip_actions :118-127
-  if (v > kMaxSpeed) { const double c = 1.0 * (kMaxSpeed - v); acc = acc <= c ? acc : c; }
-  else if (v < -kMaxSpeed) { const double c = 1.0 * (kMaxSpeed - v); acc = acc >= c ? acc : c; }
-  double sh, ch, sb, cb;
-  mmm_sincos(h, &sh, &ch);
-  mmm_slip_sincos(ht, &sb, &cb);  // beta = arctan(1/2 tan(delta))
-  const double vx = v * mmm_cos_sum(sh, ch, sb, cb), vy = v * mmm_sin_sum(sh, ch, sb, cb);
-  x = x + vx * dt;
-  y = y + vy * dt;
-  h = h + MM_DIVC(v * sb, 2.5) * dt;  // / (LENGTH / 2)
-  v = v + acc * dt;
-}
-
-// idm_controller.py:200-227 acceleration (IDM) of `ego` behind `front` (has_front false: none); lane = ego's lane
-MM_DEV double idm_acc(int lane, double x, double h, double v, double ts, bool has_front, double fx, double fh, double fv) {
-  const double target = not_zero(ts);
-  const double q = fmax(v, 0) / target, q2 = q * q;
-  double acc = 3.0 * (1 - q2 * q2);  // np.power(., 4) as (x^2)^2, as the step kernel
-  if (has_front) {
-    const double sx = lane_sx(lane);
-    const double d = (fx - sx) - (x - sx);  // ego.lane_distance_to(front)
-    double es, ec, fs, fc;
-    mmm_sincos(h, &es, &ec);
-    mmm_sincos(fh, &fs, &fc);
-    const double dv = (v * ec - fv * fc) * ec + (v * es - fv * fs) * es;  // desired_gap :274-289, projected
-    constexpr double den = 0x1.efbdeb14f4edap+2;  // 2 * np.sqrt(15.0)
-    const double dstar = 10.0 + v * 1.5 + div_c(v * dv, den, 1.0 / den);
-    const double g = dstar / not_zero(d);
-    acc -= 3.0 * (g * g);
-  }
-  return acc;
-}
-
-// abstract.py:744-755 _is_colliding: norm > LENGTH pre-check, then the 0.9-scaled rectangles
-MM_DEV bool colliding(double ex, double ey, double eh, double ox, double oy, double oh, double ol, double ow) {
-  const double dx = ox - ex, dy = oy - ey;
-  if ((dx * dx + dy * dy) > kU5) return false;
-  return rects_intersect(ex, ey, eh, ox, oy, ol, ow, oh);
-}
 
 // PHILOX: the device draws (uniforms == NULL) -- a compile-time choice, not a branch inside draw().  As a run-time test of the
 // (wave-uniform) pointer the compiler kept the answer as a lane mask formed inside the priority-key loop, i.e. under the exec
@@ -154,31 +88,12 @@ __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
     if constexpr (!PHILOX) {
       return d < a.stride ? a.uniforms[(long long)e * a.stride + d] : 0.5;  // (at most 9 N draws: see header)
     } else {
-      uint32_t w[4];
-      philox4x32((uint32_t)d, episode, steps, kDomain, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-      return u53(w[0], w[1]);
+      return philox_draw(d, episode, steps, seed);
     }
   };
   for (int i = 0; i < n; i++) {
-    const int l = B(MM_B_LANE, i);
-    const double x = F(MM_F_X, i), sp = F(MM_F_SPEED, i);
-    double p = 0;
-    if (l == MM_LANE_BC1) {
-      p = -0.5;
-      const double dme = 420.0 - x;  // distance_to_merging_end (abstract.py:614-618): sum(ends[:3]) - x
-      p = p - MM_DIVC(100.0 - dme, 100.0);
-    }
-    // _compute_headway_distance (abstract.py:620-635) on the original env
-    double hd = 60;
-    const int nl = next_lane(l, x, F(MM_F_Y, i));
-    for (int v = 0; v < nv; v++) {
-      const int lv = B(MM_B_LANE, v);
-      const double xv = F(MM_F_X, v);
-      if (lv == l && xv > x) { const double d = xv - x; if (d < hd) hd = d; }
-      if (l != MM_LANE_BC1 && lv == nl && xv > x) { const double d = xv - x; if (d < hd) hd = d; }
-    }
-    if (sp > 0) p = p + 0.5 * mmm_log(hd / (a.headway_time * sp));
-    else p = p + 0;
+    const double p = priority_number(B(MM_B_LANE, i), F(MM_F_X, i), F(MM_F_Y, i), F(MM_F_SPEED, i), nv, a.headway_time,
+                                     [&](int v) { return B(MM_B_LANE, v); }, [&](int v) { return F(MM_F_X, v); });
     key[i] = p + draw() * 0.001;
     order[i] = i;
   }
@@ -223,22 +138,11 @@ __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
       S.live(LLEN, v) = t + 1;
       return;
     }
-    const double steer = S.live(LHS, v);
-    double acc = S.live(LHA, v);
-    // clip_actions (:230-239) writes into the action dict, which generate_actions left as vehicle.action: it persists
-    if (sp > kMaxSpeed) { const double c = 1.0 * (kMaxSpeed - sp); acc = acc <= c ? acc : c; }
-    else if (sp < -kMaxSpeed) { const double c = 1.0 * (kMaxSpeed - sp); acc = acc >= c ? acc : c; }
+    double x = S.live(LX, v), y = S.live(LY, v), hh = h, vv = sp, acc = S.live(LHA, v);
+    idm_move(x, y, hh, vv, S.live(LHS, v), acc, dt);  // (the clipped acceleration persists)
     S.live(LHA, v) = acc;
-    double s2, c2, sh, ch, sb, cb;
-    mmm_sincos(steer, &s2, &c2);
-    mmm_slip_sincos(1.0 / 2 * (s2 / c2), &sb, &cb);  // beta = arctan(1/2 tan(delta))
-    mmm_sincos(h, &sh, &ch);
-    const double vx = sp * mmm_cos_sum(sh, ch, sb, cb), vy = sp * mmm_sin_sum(sh, ch, sb, cb);
-    const double x = S.live(LX, v) + vx * dt, y = S.live(LY, v) + vy * dt;
-    S.live(LX, v) = x; S.live(LY, v) = y;
-    S.live(LH, v) = h + MM_DIVC(sp * sb, 2.5) * dt;
-    S.live(LV, v) = sp + acc * dt;
-    S.traj(t, 0, v) = x; S.traj(t, 1, v) = y; S.traj(t, 2, v) = S.live(LH, v); S.traj(t, 3, v) = S.live(LV, v);
+    S.live(LX, v) = x; S.live(LY, v) = y; S.live(LH, v) = hh; S.live(LV, v) = vv;
+    S.traj(t, 0, v) = x; S.traj(t, 1, v) = y; S.traj(t, 2, v) = hh; S.traj(t, 3, v) = vv;
     S.live(LLEN, v) = t + 1;
   };
   // generate_actions (idm_controller.py:59-76): IDM behind the front vehicle of its own (original) lane, MOBIL, and two
@@ -249,29 +153,18 @@ __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
   auto generate_actions = [&](int v) {
     const int L = B(MM_B_LANE, v);
     const double x = S.live(LX, v), y = S.live(LY, v), h = S.live(LH, v), sp = S.live(LV, v);
-    // neighbour_vehicles (:242-271): road.vehicles + road.objects on the lane, margin 1
-    double s, r;
-    lane_local(L, x, y, s, r);
-    bool hf = false;
-    double sf = 0, fx = 0, fh = 0, fv = 0;
-    for (int u = 0; u <= nv; u++) {
-      if (u == v) continue;
-      const bool obst = u == nv;
-      const double ux = obst ? kObstX : S.live(LX, u), uy = obst ? kObstY : S.live(LY, u);
-      double su, ru;
-      lane_local(L, ux, uy, su, ru);
-      if (!(fabs(ru) <= kLaneWidth / 2 + 1 && -kVehLength <= su && su < lane_len(L) + kVehLength)) continue;
-      if (s <= su && (!hf || su <= sf)) {
-        sf = su; hf = true;
-        fx = ux; fh = obst ? 0.0 : S.live(LH, u); fv = obst ? 0.0 : S.live(LV, u);
-      }
-    }
     double tl = S.live(LTL, v);
     if (lane_after_end((int)tl, x)) S.live(LTL, v) = next_lane((int)tl, x, y);  // follow_road :78-84
-    const double steer = steering_control(x, y, h, sp, L);
-    S.live(LHS, v) = clipd(steer * (draw() * 0.1 + 0.95), -kPi / 3, kPi / 3);
-    const double acc = idm_acc(L, x, h, sp, S.live(LTS, v), hf, fx, fh, fv);
-    S.live(LHA, v) = clipd(acc * (draw() * 0.1 + 0.95), -6.0, 6.0);
+    const double u1 = draw(), u2 = draw();
+    double steer, acc;
+    int front;
+    hdv_generate(v, L, nv, x, y, h, sp, S.live(LTS, v), u1, u2,
+                 [&](int u, double &ux, double &uy, double &uh, double &uv) {
+                   ux = S.live(LX, u); uy = S.live(LY, u); uh = S.live(LH, u); uv = S.live(LV, u);
+                 },
+                 steer, acc, front);
+    S.live(LHS, v) = steer;
+    S.live(LHA, v) = acc;
   };
   auto reset_live = [&](int v) {  // copy.deepcopy(env.controlled_vehicles[index]): the original, no trajectory
     S.live(LX, v) = F(MM_F_X, v); S.live(LY, v) = F(MM_F_Y, v); S.live(LH, v) = F(MM_F_HEADING, v);
@@ -298,13 +191,8 @@ __global__ void __launch_bounds__(64) supervise_kernel(Args a) {
     if ((int)S.live(LLEN, idx) == np) reset_live(idx);  // stepped before as someone's neighbour (:72-78)
     // _get_available_actions (abstract.py:219-240) of the (unstepped) ego: IDLE, side lanes, FASTER, SLOWER
     const int lane = B(MM_B_LANE, idx);
-    int avail[4], na = 0;
-    avail[na++] = 1;
-    if (lane == MM_LANE_BC1 && lane_reachable(MM_LANE_BC0, S.live(LX, idx), S.live(LY, idx))) avail[na++] = 0;
-    if (lane == MM_LANE_BC0 && lane_reachable(MM_LANE_BC1, S.live(LX, idx), S.live(LY, idx))) avail[na++] = 2;
-    const int sidx = B(MM_B_SPEED_INDEX, idx);
-    if (sidx < 5 - 1) avail[na++] = 3;
-    if (sidx > 0) avail[na++] = 4;
+    int avail[5];
+    const int na = available_actions(lane, S.live(LX, idx), S.live(LY, idx), B(MM_B_SPEED_INDEX, idx), avail);
     // neighbours by lane (:85-110): nb = {v_fl, v_rl, v_fr, v_rr}
     int nb[4] = {-1, -1, -1, -1};
     if (is_main(lane)) {

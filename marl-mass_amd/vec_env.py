@@ -31,8 +31,13 @@ class BatchedMergeEnv(object):
 
     def __init__(self, clib, E, N, env_id="merge-multi-agent-v1", config=None, device="cpu",
                  cbf_eta=0.0, cbf_tau=None, auto_reset=False, obs_f64=False, seed=0, first_env=0,
-                 trace=False, debug_flags=0, n_hdv=0, qp_solver="ipm", draw_counts=False, num_cav=0, skip_outputs=()):
+                 trace=False, debug_flags=0, n_hdv=0, qp_solver="ipm", draw_counts=False, num_cav=0, skip_outputs=(),
+                 enable_dmc=False):
         self.clib, self.E, self.N = clib, int(E), int(N)
+        # enable_dmc: config["safety_guarantee"] = "dmc" on merge-multi-agent-v0 runs the device's safety_layer_dmc
+        # (mm_supervise_dmc).  Off by default: a plain "dmc" config still raises NotImplementedError from step(), as it always
+        # has; making it the behaviour of the plain setting is a later change.
+        self.enable_dmc = bool(enable_dmc)
         self.env_id = env_id
         self.device = torch.device(device)
         self.config = abi.default_env_config(env_id)
@@ -115,31 +120,36 @@ class BatchedMergeEnv(object):
         supervise()."""
         self._sup, self._sup_err = abi.SUP_NONE, None
         try:
-            sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)
+            sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind, dmc=self.enable_dmc)
         except NotImplementedError:
             return
         if sup == abi.SUP_NONE:
             return
-        if not self.clib.has_supervisor:
-            self._sup_err = "%s does not export mm_supervise: safety_guarantee='priority' needs the HIP library" % (
-                os.path.basename(self.clib.path),)
+        if not (self.clib.has_supervisor_dmc if sup == abi.SUP_DMC else self.clib.has_supervisor):
+            self._sup_err = "%s does not export %s: safety_guarantee=%r needs the HIP library" % (
+                os.path.basename(self.clib.path), "mm_supervise_dmc" if sup == abi.SUP_DMC else "mm_supervise",
+                self.config.get("safety_guarantee"))
             return
         self._sup = sup
         self.n_step = int(self.config.get("n_step", 6))
         ratio = self._cfg.simulation_frequency // max(1, self._cfg.policy_frequency)
-        n = self.clib.supervise_scratch_bytes(self.E, self.N, self.n_step, max(1, ratio)) // 8
+        bytes_of = self.clib.supervise_dmc_scratch_bytes if sup == abi.SUP_DMC else self.clib.supervise_scratch_bytes
+        n = bytes_of(self.E, self.N, self.n_step, max(1, ratio)) // 8
         if getattr(self, "_sup_scratch", None) is None or self._sup_scratch.numel() < n:
             self._sup_scratch = torch.empty(n, dtype=torch.float64, device=self.device)
         if getattr(self, "new_action", None) is None:
             self.new_action = torch.zeros(self.E, self.N, dtype=torch.int32, device=self.device)
             self.n_draws = torch.zeros(self.E, dtype=torch.int32, device=self.device)
 
-    def supervise(self, actions, uniforms=None):
+    def supervise(self, actions, uniforms=None, literal=False, trace=False):
         """new_action = safety_supervisor(env, actions) (central_layer.py:16-178) on the current state, without stepping.
         uniforms: optional [E, >= 9 N] float64 -- the np.random.rand() values in the reference's order; None: device Philox.
-        Returns (new_action int32 [E, N], n_draws int32 [E]) -- buffers owned by the env, rewritten by the next call."""
+        Returns (new_action int32 [E, N], n_draws int32 [E]) -- buffers owned by the env, rewritten by the next call.
+        With enable_dmc and safety_guarantee = "dmc": new_action = safety_layer_dmc(env, actions) (decentralised_dmc.py:70-193,
+        mm_supervise_dmc); uniforms [E, >= 2 N].  literal: the one-lane-per-env form instead of the lane-parallel one (same
+        bits); trace: also fill self.dmc_trace, float64 [E, N, 20] (fields: include/mm_supervisor.h)."""
         if self._sup == abi.SUP_NONE:
-            abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)  # raises for dmc / v1 priority
+            abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind, dmc=self.enable_dmc)  # raises for dmc / v1 priority
             if self._sup_err:
                 raise NotImplementedError(self._sup_err)
             raise ValueError("safety_guarantee=%r has no supervisor" % (self.config.get("safety_guarantee"),))
@@ -150,6 +160,16 @@ class BatchedMergeEnv(object):
         if uniforms is not None:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float64, device=self.device).reshape(self.E, -1).contiguous()
             stride = uniforms.shape[1]
+        if self._sup == abi.SUP_DMC:
+            if trace and getattr(self, "dmc_trace", None) is None:
+                self.dmc_trace = torch.zeros(self.E, self.N, abi.DMC_TRACE_DOUBLES, dtype=torch.float64, device=self.device)
+            self.clib.check(self.clib.lib.mm_supervise_dmc(self._h, self.n_step, abi.DMC_LITERAL if literal else 0, _ptr(actions),
+                                                           _ptr(uniforms), stride, _ptr(self._sup_scratch),
+                                                           self._sup_scratch.numel() * 8, _ptr(self.new_action), _ptr(self.n_draws),
+                                                           _ptr(self.dmc_trace) if trace else None, self._stream()), self._h)
+            return self.new_action, self.n_draws
+        if literal or trace:
+            raise ValueError("literal / trace are options of the dmc supervisor")
         self.clib.check(self.clib.lib.mm_supervise(self._h, self._sup, self.n_step, _ptr(actions), _ptr(uniforms), stride,
                                                    _ptr(self._sup_scratch), self._sup_scratch.numel() * 8,
                                                    _ptr(self.new_action), _ptr(self.n_draws), self._stream()), self._h)
@@ -166,7 +186,7 @@ class BatchedMergeEnv(object):
         """env.config[k] = v after construction (run_mappo.py:145-171); CBFType globals via kw."""
         if config:
             self.config.update(config)
-        for k in ("cbf_eta", "cbf_tau", "auto_reset", "seed", "n_hdv", "qp_solver", "draw_counts", "num_cav"):
+        for k in ("cbf_eta", "cbf_tau", "auto_reset", "seed", "n_hdv", "qp_solver", "draw_counts", "num_cav", "enable_dmc"):
             if k in kw:
                 setattr(self, k, kw[k])
         self._cfg = self._make_cfg()
@@ -236,11 +256,12 @@ class BatchedMergeEnv(object):
         out: optional {key: tensor} for keys of the info dict (same shape / dtype / device as self.out[key], contiguous):
         this step writes those outputs there instead of into self.out -- a rollout hands over rewards[t], dones[t], ...
         and saves a copy kernel per quantity and step; the returned info carries the given tensors under those keys.
-        With safety_guarantee = "priority" (v0) the joint action first goes through the supervisor (supervise()) and the env
-        steps on its result, which info["new_action"] carries (int32 [E, N]); uniforms: see supervise().
+        With safety_guarantee = "priority" (v0), or "dmc" on an env built with enable_dmc=True, the joint action first goes
+        through the supervisor (supervise()) and the env steps on its result, which info["new_action"] carries (int32 [E, N]);
+        uniforms: see supervise().  Without enable_dmc a "dmc" config raises NotImplementedError here (the default for now).
         merge-multi-agent-hdv-v1 (MergeEnvLCHDV.step, merge_env_v1.py:604-666): nothing is controlled, step(None) is the call and
         actions, if given, are ignored; info holds crashed [E, N], average_speed, traffic_speed, min_headway, merge_percent."""
-        sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind)
+        sup = abi.supervisor_id(self.config.get("safety_guarantee"), self._cfg.env_kind, dmc=self.enable_dmc)
         if self.kind == abi.ENV_HDV_V1:
             actions = None
         elif actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
