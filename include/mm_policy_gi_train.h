@@ -104,6 +104,56 @@ int32_t mm_policy_gi_train_chunked(const float *obs, int64_t obs_stride, int64_t
                                    float *logp_taken, float *value, float *ratio, void *scratch, uint64_t scratch_bytes,
                                    MMStream stream, int64_t chunk);
 
+/*
+ * The same gradient over a batch that is SHARDED over ranks, in two phases (marl-mass_amd/csrc/mm_policy_sharded.hip).  Every
+ * rank runs `partial` on its own samples and leaves a shard block; the R blocks are gathered (the caller's collective) and
+ * `finish` folds them, on every rank in the same order, into the gradient of ONE loss over all ranks' samples.
+ *
+ * The shard block: MM_GI_SHARD_DOUBLES doubles on the device (mm_policy_gi_train_shard_bytes gives the size in bytes),
+ *   [0] B, the number of valid samples of the WHOLE batch   [1] this rank's own number of valid samples
+ *   [2] the configuration word n_s + 2^8 n_a + 2^16 (reference form + 2 huber) + 2^24 networks (networks = 3)   [3] 0
+ *   [4] [5] the un-normalised fp64 sums of the actor and the critic loss terms of this rank's samples
+ *   [6 .. 6 + 27 952)  the fp64 accumulator block, in the layout of a kernel-B partial block (PartialBlock<5>, mm_policy_mfma.h):
+ *       dW2 [128][160] at 0; the head rows [16][128] at 20 480 (rows 0..7 dWa, row 8 dWc); dW1 [160][32] at 22 528 (rows 0..31
+ *       fc11, whose column k is column 5 k; rows 32..95 fc12, column k at 5 (k / 2) + 1 + k % 2; rows 96..159 fc13, column k at
+ *       5 (k / 2) + 3 + k % 2); db2 [128] at 27 648; the heads' biases [16] at 27 776 (0..7 ba, 8 bc); db1 [160] at 27 792
+ *       (fc11, fc12, fc13 in the rows' order).
+ *
+ * mm_policy_gi_train_partial: mm_policy_gi_train_chunked's arguments without grads and loss, and with
+ *   count   DEV int32[1], 4-byte aligned: B of the whole batch over all ranks.  Kernel A scales by it; the entry does not compute it.
+ *   shard   DEV double[MM_GI_SHARD_DOUBLES], 16-byte aligned: WRITTEN.
+ * adv_sums (reference form) is likewise the whole batch's (S+, S-).  The entry zeroes the block, runs prep (the W2^T fragments and
+ * the rank's own count), the chunked entry's passes of `chunk` samples with the accumulation going straight into the block, and
+ * one kernel that folds the rank's loss partials (the chunked finish's tree) into [4], [5] and writes the header.  The diagnostics
+ * are written as mm_policy_gi_train_chunked writes them.  n == 0 (an empty shard: the per-sample pointers and the scratch may be
+ * NULL) writes a valid all-zero block with local count 0.  scratch: mm_policy_gi_train_chunked_scratch_bytes(n, chunk).
+ * MM_ERR_INVALID_ARG: as mm_policy_gi_train_chunked, and count or shard NULL or misaligned.  A refused call enqueues nothing.
+ *
+ * mm_policy_gi_train_finish: blocks DEV double, block r at blocks + r * block_stride (doubles; >= MM_GI_SHARD_DOUBLES),
+ * 1 <= n_blocks <= 64.  One launch: gradient element e = float(block 0's value + block 1's + ... + block R-1's, in index order,
+ * fp64), written in torch layout; loss[0] = -(sum_r [4]) / B (per-sample form) or / B^2 (reference form), loss[1] = (sum_r [5]) / B,
+ * loss[2] their float32 sum, the sums in index order.  With one block whose B is its own count these are
+ * mm_policy_gi_train_chunked's bits for the same chunk.  The launch checks the headers: every block carries the same B and
+ * configuration word, the word is that of n_s and n_a, and the local counts add up to B; if not, ALL gradients and losses are
+ * written as NaN (a wrong B never becomes a plausible gradient).  B == 0 writes zeros.  No floating-point atomics; only enqueues
+ * on `stream`.
+ * MM_ERR_INVALID_ARG: blocks, grads (or one of its twelve) or loss NULL, n_blocks outside 1..64, block_stride below the block
+ *   size, n_s outside 25..32, n_a outside 1..8.
+ */
+#define MM_GI_SHARD_DOUBLES 27958 /* 4 + 2 + 27 952 */
+
+int32_t mm_policy_gi_train_shard_bytes(uint64_t *bytes);
+
+int32_t mm_policy_gi_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                   int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                   const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a, float clip_param,
+                                   int32_t critic_loss, const float *adv_sums, const int32_t *count, double *shard,
+                                   float *logp_taken, float *value, float *ratio, void *scratch, uint64_t scratch_bytes,
+                                   MMStream stream, int64_t chunk);
+
+int32_t mm_policy_gi_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
+                                  const MMGiParams *grads, float *loss, MMStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,47 @@ int32_t mm_policy_train_chunked(const float *obs, int64_t obs_stride, int64_t n,
                                 const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, float *logp_taken,
                                 float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk);
 
+/*
+ * The same gradients over a batch that is SHARDED over ranks, in two phases (marl-mass_amd/csrc/mm_policy_sharded.hip), as
+ * mm_policy_gi_train_partial / mm_policy_gi_train_finish (include/mm_policy_gi_train.h: the protocol, the header's check and
+ * the order of every sum are described there) are to mm_policy_gi_train_chunked.
+ *
+ * The shard block: MM_PT_SHARD_DOUBLES doubles on the device (mm_policy_train_shard_bytes gives the size in bytes),
+ *   [0] B of the WHOLE batch   [1] this rank's own number of valid samples
+ *   [2] the configuration word n_s + 2^8 n_a + 2^16 (reference form + 2 huber) + 2^24 networks (1 actor + 2 critic)   [3] 0
+ *   [4] the un-normalised fp64 sum of the actor's loss terms, [5] of the critic's (0 for a network that was not given)
+ *   [6 .. 6 + 26 896) the actor's fp64 accumulator block, then [.. + 26 896) the critic's, each in the layout of a kernel-B partial
+ *       block (PartialBlock<4>, mm_policy_mfma.h): dW2 [128][160] at 0 (row pitch 160, k2 columns used); dW3 rows [16][128] at
+ *       20 480; dW1 [128][32] at 22 528; db2 [128] at 26 624; db3 [16] at 26 752; db1 [128] at 26 768.  Zeros for a network
+ *       that was not given.
+ *
+ * mm_policy_train_partial: mm_policy_train_chunked's arguments without actor_grads, critic_grads and loss, and with count (DEV
+ * int32[1], 4-byte aligned: B of the whole batch over all ranks) and shard (DEV double[MM_PT_SHARD_DOUBLES], 16-byte aligned,
+ * WRITTEN).  adv_sums is the whole batch's.  n == 0 writes a valid all-zero block with local count 0 (the per-sample pointers and
+ * the scratch may be NULL).  scratch: mm_policy_train_chunked_scratch_bytes(n, chunk).
+ * MM_ERR_INVALID_ARG: as mm_policy_train_chunked (without what concerns the gradients and loss), and count or shard NULL or
+ * misaligned.  A refused call enqueues nothing.
+ *
+ * mm_policy_train_finish: actor_grads / critic_grads: the networks whose gradients are WRITTEN (at least one; the other's tensors
+ * are not touched and its loss is 0).  loss: DEV float[2].  A requested network must be present in every block; that, and the
+ * check of mm_policy_gi_train_finish, failing writes every requested gradient and both losses as NaN.  B == 0 writes zeros.
+ * MM_ERR_INVALID_ARG: blocks or loss NULL, no gradients at all, a NULL pointer among a given network's six, n_blocks outside
+ *   1..64, block_stride below the block size, n_s outside 25..32, n_a outside 1..8.
+ */
+#define MM_PT_SHARD_DOUBLES 53798 /* 4 + 2 + 2 * 26 896 */
+
+int32_t mm_policy_train_shard_bytes(uint64_t *bytes);
+
+int32_t mm_policy_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden, int32_t n_a,
+                                float clip_param, int32_t critic_loss, const float *adv_sums, const float *advantages,
+                                const int32_t *count, double *shard, float *logp_taken, float *value, float *ratio, void *scratch,
+                                uint64_t scratch_bytes, MMStream stream, int64_t chunk);
+
+int32_t mm_policy_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
+                               const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, MMStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -357,6 +357,27 @@ class CLib(object):
             lib.mm_policy_train_chunked_scratch_bytes.restype = i32
             lib.mm_policy_train_chunked.argtypes = list(lib.mm_policy_train.argtypes) + [i64]
             lib.mm_policy_train_chunked.restype = i32
+        # the same two gradients over a batch sharded over ranks (mm_policy_sharded.hip, the same two headers): `partial` is the
+        # chunked entry without gradients and loss, with the whole batch's count and the shard block; `finish` folds R blocks
+        sharded = lambda fam: all(hasattr(lib, "mm_policy_%s_%s" % (fam, s)) for s in ("shard_bytes", "partial", "finish"))  # noqa: E731
+        self.has_policy_gi_train_sharded = self.has_policy_gi_train_chunked and sharded("gi_train")
+        if self.has_policy_gi_train_sharded:
+            a = list(lib.mm_policy_gi_train_chunked.argtypes)  # [16] grads, [17] loss -> count, shard
+            lib.mm_policy_gi_train_shard_bytes.argtypes = [C.POINTER(u64)]
+            lib.mm_policy_gi_train_shard_bytes.restype = i32
+            lib.mm_policy_gi_train_partial.argtypes = a[:16] + [vp, vp] + a[18:]
+            lib.mm_policy_gi_train_partial.restype = i32
+            lib.mm_policy_gi_train_finish.argtypes = [vp, i32, i64, i32, i32, C.POINTER(MMGiParams), vp, vp]
+            lib.mm_policy_gi_train_finish.restype = i32
+        self.has_policy_train_sharded = self.has_policy_train_chunked and sharded("train")
+        if self.has_policy_train_sharded:
+            a = list(lib.mm_policy_train_chunked.argtypes)  # [18], [19] the gradients, [20] loss -> count, shard
+            lib.mm_policy_train_shard_bytes.argtypes = [C.POINTER(u64)]
+            lib.mm_policy_train_shard_bytes.restype = i32
+            lib.mm_policy_train_partial.argtypes = a[:18] + [vp, vp] + a[21:]
+            lib.mm_policy_train_partial.restype = i32
+            lib.mm_policy_train_finish.argtypes = [vp, i32, i64, i32, i32, C.POINTER(MMMlpParams), C.POINTER(MMMlpParams), vp, vp]
+            lib.mm_policy_train_finish.restype = i32
         # the same two entries and the scratch query at hidden 512 (include/mm_policy_wide_train.h: mm_policy_eval's and
         # mm_policy_train's arguments), also libmm_hip.so only
         self.has_policy_wide_train = self.has_policy_train and all(
@@ -474,6 +495,30 @@ class CLib(object):
         b = C.c_uint64()
         self.check(self.lib.mm_policy_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
         return b.value
+
+    def require_policy_gi_train_sharded(self):
+        if not self.has_policy_gi_train_sharded:
+            raise NotImplementedError("%s does not export mm_policy_gi_train_partial / _finish: the shared actor-critic's gradient "
+                                      "over rank-sharded batches needs the HIP library" % os.path.basename(self.path))
+
+    def require_policy_train_sharded(self):
+        if not self.has_policy_train_sharded:
+            raise NotImplementedError("%s does not export mm_policy_train_partial / _finish: the separate actor's and critic's "
+                                      "gradients over rank-sharded batches need the HIP library" % os.path.basename(self.path))
+
+    def policy_gi_train_shard_doubles(self):
+        """Doubles of the shared network's shard block (include/mm_policy_gi_train.h: MM_GI_SHARD_DOUBLES)."""
+        self.require_policy_gi_train_sharded()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_gi_train_shard_bytes(C.byref(b)))
+        return b.value // 8
+
+    def policy_train_shard_doubles(self):
+        """Doubles of the separate networks' shard block (include/mm_policy_train.h: MM_PT_SHARD_DOUBLES)."""
+        self.require_policy_train_sharded()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_train_shard_bytes(C.byref(b)))
+        return b.value // 8
 
     def require_policy_wide_train(self):
         if not self.has_policy_wide_train:

@@ -1,5 +1,5 @@
-// mm_policy_chunked.h -- how mm_policy_chunked.hip reaches prep, kernel A and kernel B of the two training files.
-// Host-side launch helpers only, defined next to the kernels they launch (mm_policy_gi_train.hip, mm_policy_train.hip): the
+// mm_policy_chunked.h -- how mm_policy_chunked.hip and mm_policy_sharded.hip reach prep, kernel A and kernel B of the two training
+// files, and what those two share (below).  The launch helpers are host-side only, defined next to the kernels they launch (mm_policy_gi_train.hip, mm_policy_train.hip): the
 // chunked entries add no __global__ to those files and edit none, so their code objects stay as recorded
 // (profiles/policy_gi_train, profiles/policy_train).  A helper only enqueues on the stream; the caller reads hipGetLastError.
 #ifndef MM_POLICY_CHUNKED_H
@@ -78,5 +78,108 @@ void launch_sample(hipStream_t s, bool critic, const PassArgs &p);
 void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part);
 
 }  // namespace pt
+// ---- what the chunked entries (mm_policy_chunked.hip) and the rank-sharded ones (mm_policy_sharded.hip) share: the index maps of
+// the finish kernels, the chunked scratch layout and the accumulate launch
+namespace chunked {
+
+typedef mfma::PartialBlock<5> PartGi;  // the shared network's partial block: 27 952 floats
+typedef mfma::PartialBlock<4> PartPt;  // one separate network's: 26 896 floats
+
+constexpr int kCatGi = 160;
+constexpr int kNFixedGi = 32 * 5 + 32 + 64 * 10 + 64 + 64 * 10 + 64 + mfma::kHidden * kCatGi + mfma::kHidden;  // everything before Wa
+
+// the gradient elements of the shared network (the twelve tensors of MMGiParams in order) and of one separate network (six)
+__host__ __device__ inline int gi_elems(int n_a) { return kNFixedGi + n_a * mfma::kHidden + n_a + mfma::kHidden + 1; }
+__host__ __device__ inline int pt_elems(int n_s, int k2, int n_out) {
+  return mfma::kHidden * n_s + mfma::kHidden + mfma::kHidden * k2 + mfma::kHidden + n_out * mfma::kHidden + n_out;
+}
+
+// policy_gi_train_fold_kernel's index map (mm_policy_gi_train.hip): element t < gi_elems(n_a) of the gradients in torch layout ->
+// where it is written; src: its slot of the PartialBlock<5> accumulator
+MM_DEV float *gi_grad_slot(int t, int n_a, const MMGiParams &gr, int &src) {
+  typedef PartGi P;
+  constexpr int kHidden = mfma::kHidden;
+  if (t < 160) { const int o = t / 5, k = t % 5; src = P::kW1 + o * 32 + 5 * k; return gr.W11 + t; }
+  t -= 160;
+  if (t < 32) { src = P::kb1 + t; return gr.b11 + t; }
+  t -= 32;
+  if (t < 640) { const int o = t / 10, k = t % 10; src = P::kW1 + (32 + o) * 32 + 5 * (k >> 1) + 1 + (k & 1); return gr.W12 + t; }
+  t -= 640;
+  if (t < 64) { src = P::kb1 + 32 + t; return gr.b12 + t; }
+  t -= 64;
+  if (t < 640) { const int o = t / 10, k = t % 10; src = P::kW1 + (96 + o) * 32 + 5 * (k >> 1) + 3 + (k & 1); return gr.W13 + t; }
+  t -= 640;
+  if (t < 64) { src = P::kb1 + 96 + t; return gr.b13 + t; }
+  t -= 64;
+  if (t < kHidden * kCatGi) { src = P::kW2 + t; return gr.W2 + t; }
+  t -= kHidden * kCatGi;
+  if (t < kHidden) { src = P::kb2 + t; return gr.b2 + t; }
+  t -= kHidden;
+  if (t < n_a * kHidden) { src = P::kHd + t; return gr.Wa + t; }
+  t -= n_a * kHidden;
+  if (t < n_a) { src = P::kbh + t; return gr.ba + t; }
+  t -= n_a;
+  if (t < kHidden) { src = P::kHd + 8 * kHidden + t; return gr.Wc + t; }
+  src = P::kbh + 8;
+  return gr.bc;
+}
+
+// policy_train_fold_kernel's index map (mm_policy_train.hip) for a network with fc2 rows of k2 floats and n_out outputs: element
+// t of its six gradients -> where it is written (nullptr past the last element); src: its slot of the PartialBlock<4> accumulator
+MM_DEV float *pt_grad_slot(int t, int n_s, int k2, int n_out, const MMMlpParams &gr, int &src) {
+  typedef PartPt P;
+  constexpr int kHidden = mfma::kHidden;
+  if (t < kHidden * n_s) { const int o = t / n_s, k = t % n_s; src = P::kW1 + o * 32 + k; return gr.W1 + t; }
+  t -= kHidden * n_s;
+  if (t < kHidden) { src = P::kb1 + t; return gr.b1 + t; }
+  t -= kHidden;
+  if (t < kHidden * k2) { const int o = t / k2, k = t % k2; src = P::kW2 + o * mfma::kW2Pitch + k; return gr.W2 + t; }
+  t -= kHidden * k2;
+  if (t < kHidden) { src = P::kb2 + t; return gr.b2 + t; }
+  t -= kHidden;
+  if (t < n_out * kHidden) { src = P::kHd + t; return gr.W3 + t; }
+  t -= n_out * kHidden;
+  src = P::kbh + t;
+  return t < n_out ? gr.b3 + t : nullptr;
+}
+
+// ---- host side
+// The chunked scratch, offsets in floats: the header, the W2^T fragments and the per-sample rows as in the unchunked layout of
+// `chunk` samples; then the fp64 loss partials of all ceil(n / 32) tiles (`sums` doubles per tile), the partial blocks of one
+// pass, and `nets` fp64 accumulator blocks (the sharded entries accumulate into the caller's shard block and leave them unused).
+// The partial blocks hold the most slices any pass of at most `chunk` samples cuts: the slices of scratch_layout(chunk) up to
+// 1024 tiles, where the count grows with the size, and kMaxSlices above (a shorter last pass may cut more, never more than that).
+struct ChunkLayout {
+  mfma::Layout rows;  // the unchunked layout of `chunk` samples: frag, h1 .. xs
+  long long ntiles, lossp, part, acc, total;
+  int blocks;
+};
+
+static inline bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chunk <= 0x7FFFFFC0ll; }
+
+static inline ChunkLayout chunk_layout(const mfma::Layout &rows, long long n, int sums, int partial, int nets) {
+  ChunkLayout L;
+  L.rows = rows;
+  L.ntiles = (n + 31) / 32;
+  L.blocks = rows.ntiles <= 2 * mfma::kMaxSlices ? rows.slices : mfma::kMaxSlices;
+  L.lossp = rows.lossp;  // (where the unchunked layout's own loss partials start: the end of the rows)
+  L.part = L.lossp + 2 * sums * L.ntiles;
+  L.acc = L.part + (long long)L.blocks * partial;
+  L.total = L.acc + 2ll * nets * partial;
+  return L;
+}
+
+static inline SampleRows rows_of(float *sc, const mfma::Layout &R) {
+  SampleRows r = {sc + R.h1, sc + R.dz1, sc + R.h2, sc + R.dz2, sc + R.dh, sc + R.xs};
+  return r;
+}
+
+template <typename T>
+static inline T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
+
+// acc[off] += the `slices` partial blocks of `size` floats at part, in workgroup order, fp64 (train_chunked_accumulate_kernel)
+void accumulate(hipStream_t s, const float *part, int slices, int size, double *acc);
+
+}  // namespace chunked
 }  // namespace mm
 #endif

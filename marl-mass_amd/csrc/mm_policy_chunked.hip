@@ -25,8 +25,6 @@ namespace mm {
 namespace chunked {
 
 using namespace mfma;
-typedef PartialBlock<5> PartGi;  // the shared network's partial block: 27 952 floats
-typedef PartialBlock<4> PartPt;  // one separate network's: 26 896 floats
 
 // ---- accumulate: one thread per partial-block element; consecutive threads read consecutive floats of a block.
 // It walks the whole block, the elements no kernel B writes included (the actor's one-hot tile of dW2: columns 128..159 of its
@@ -41,16 +39,12 @@ __global__ __launch_bounds__(256) void train_chunked_accumulate_kernel(const flo
   acc[off] = s;
 }
 
-// ---- finish, shared network: policy_gi_train_fold_kernel's index map (mm_policy_gi_train.hip) on the accumulator
-constexpr int kCatGi = 160;
-constexpr int kNFixedGi = 32 * 5 + 32 + 64 * 10 + 64 + 64 * 10 + 64 + kHidden * kCatGi + kHidden;  // everything before Wa
-
+// ---- finish, shared network: gi_grad_slot's index map (mm_policy_chunked.h) on the accumulator
 __global__ __launch_bounds__(256) void policy_gi_train_chunked_finish_kernel(const double *__restrict__ acc, int n_a, MMGiParams gr,
                                                                              const double *__restrict__ lossp, long long ntiles,
                                                                              const int *__restrict__ count, int ref_form,
                                                                              float *__restrict__ loss) {
-  typedef PartGi P;
-  const int nelem = kNFixedGi + n_a * kHidden + n_a + kHidden + 1;
+  const int nelem = gi_elems(n_a);
   if (blockIdx.x == gridDim.x - 1) {
     __shared__ double ssum[2][256];  // actor, critic
     loss_tree<2>(lossp, ntiles, ssum);
@@ -63,41 +57,19 @@ __global__ __launch_bounds__(256) void policy_gi_train_chunked_finish_kernel(con
     }
     return;
   }
-  int t = blockIdx.x * 256 + threadIdx.x;
+  const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= nelem) return;
-  if (t < 160) { const int o = t / 5, k = t % 5; gr.W11[t] = (float)acc[P::kW1 + o * 32 + 5 * k]; return; }
-  t -= 160;
-  if (t < 32) { gr.b11[t] = (float)acc[P::kb1 + t]; return; }
-  t -= 32;
-  if (t < 640) { const int o = t / 10, k = t % 10; gr.W12[t] = (float)acc[P::kW1 + (32 + o) * 32 + 5 * (k >> 1) + 1 + (k & 1)]; return; }
-  t -= 640;
-  if (t < 64) { gr.b12[t] = (float)acc[P::kb1 + 32 + t]; return; }
-  t -= 64;
-  if (t < 640) { const int o = t / 10, k = t % 10; gr.W13[t] = (float)acc[P::kW1 + (96 + o) * 32 + 5 * (k >> 1) + 3 + (k & 1)]; return; }
-  t -= 640;
-  if (t < 64) { gr.b13[t] = (float)acc[P::kb1 + 96 + t]; return; }
-  t -= 64;
-  if (t < kHidden * kCatGi) { gr.W2[t] = (float)acc[P::kW2 + t]; return; }
-  t -= kHidden * kCatGi;
-  if (t < kHidden) { gr.b2[t] = (float)acc[P::kb2 + t]; return; }
-  t -= kHidden;
-  if (t < n_a * kHidden) { gr.Wa[t] = (float)acc[P::kHd + t]; return; }
-  t -= n_a * kHidden;
-  if (t < n_a) { gr.ba[t] = (float)acc[P::kbh + t]; return; }
-  t -= n_a;
-  if (t < kHidden) { gr.Wc[t] = (float)acc[P::kHd + 8 * kHidden + t]; return; }
-  gr.bc[0] = (float)acc[P::kbh + 8];
+  int src;
+  float *dst = gi_grad_slot(t, n_a, gr, src);
+  *dst = (float)acc[src];
 }
 
-// ---- finish, one separate network: policy_train_fold_kernel's index map (mm_policy_train.hip) on the accumulator
+// ---- finish, one separate network: pt_grad_slot's index map (mm_policy_chunked.h) on the accumulator
 // loss_mode 0: sum / B (critic); 1: -sum / B (actor, per-sample form); 2: -sum / B^2 (actor, reference form)
-static int pt_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
-
 __global__ __launch_bounds__(256) void policy_train_chunked_finish_kernel(const double *__restrict__ acc, int n_s, int k2, int n_out,
                                                                           MMMlpParams gr, const double *__restrict__ lossp,
                                                                           long long ntiles, const int *__restrict__ count,
                                                                           int loss_mode, float *__restrict__ loss) {
-  typedef PartPt P;
   if (blockIdx.x == gridDim.x - 1) {
     __shared__ double ssum[1][256];
     loss_tree<1>(lossp, ntiles, ssum);
@@ -107,57 +79,15 @@ __global__ __launch_bounds__(256) void policy_train_chunked_finish_kernel(const 
     }
     return;
   }
-  int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < kHidden * n_s) { const int o = t / n_s, k = t % n_s; gr.W1[t] = (float)acc[P::kW1 + o * 32 + k]; return; }
-  t -= kHidden * n_s;
-  if (t < kHidden) { gr.b1[t] = (float)acc[P::kb1 + t]; return; }
-  t -= kHidden;
-  if (t < kHidden * k2) { const int o = t / k2, k = t % k2; gr.W2[t] = (float)acc[P::kW2 + o * kW2Pitch + k]; return; }
-  t -= kHidden * k2;
-  if (t < kHidden) { gr.b2[t] = (float)acc[P::kb2 + t]; return; }
-  t -= kHidden;
-  if (t < n_out * kHidden) { gr.W3[t] = (float)acc[P::kHd + t]; return; }
-  t -= n_out * kHidden;
-  if (t < n_out) gr.b3[t] = (float)acc[P::kbh + t];
+  int src;
+  float *dst = pt_grad_slot(blockIdx.x * 256 + threadIdx.x, n_s, k2, n_out, gr, src);
+  if (dst) *dst = (float)acc[src];
 }
 
-// ---- host side
-// The chunked scratch, offsets in floats: the header, the W2^T fragments and the per-sample rows as in the unchunked layout of
-// `chunk` samples; then the fp64 loss partials of all ceil(n / 32) tiles (`sums` doubles per tile), the partial blocks of one
-// pass, and `nets` fp64 accumulator blocks.
-// The partial blocks hold the most slices any pass of at most `chunk` samples cuts: the slices of scratch_layout(chunk) up to
-// 1024 tiles, where the count grows with the size, and kMaxSlices above (a shorter last pass may cut more, never more than that).
-struct ChunkLayout {
-  Layout rows;  // the unchunked layout of `chunk` samples: frag, h1 .. xs
-  long long ntiles, lossp, part, acc, total;
-  int blocks;
-};
-
-static bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chunk <= 0x7FFFFFC0ll; }
-
-static ChunkLayout chunk_layout(const Layout &rows, long long n, int sums, int partial, int nets) {
-  ChunkLayout L;
-  L.rows = rows;
-  L.ntiles = (n + 31) / 32;
-  L.blocks = rows.ntiles <= 2 * kMaxSlices ? rows.slices : kMaxSlices;
-  L.lossp = rows.lossp;  // (where the unchunked layout's own loss partials start: the end of the rows)
-  L.part = L.lossp + 2 * sums * L.ntiles;
-  L.acc = L.part + (long long)L.blocks * partial;
-  L.total = L.acc + 2ll * nets * partial;
-  return L;
-}
-
-static SampleRows rows_of(float *sc, const Layout &R) {
-  SampleRows r = {sc + R.h1, sc + R.dz1, sc + R.h2, sc + R.dz2, sc + R.dh, sc + R.xs};
-  return r;
-}
-
-static void accumulate(hipStream_t s, const float *part, int slices, int size, double *acc) {
+// ---- host side (the scratch layout: mm_policy_chunked.h)
+void accumulate(hipStream_t s, const float *part, int slices, int size, double *acc) {
   hipLaunchKernelGGL(train_chunked_accumulate_kernel, dim3((size + 255) / 256), dim3(256), 0, s, part, slices, size, acc);
 }
-
-template <typename T>
-static T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
 
 }  // namespace chunked
 }  // namespace mm
@@ -221,7 +151,7 @@ extern "C" int32_t mm_policy_gi_train_chunked(const float *obs, int64_t obs_stri
     gi::launch_wgrad(s, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
     accumulate(s, sc + L.part, P.slices, PartGi::kSize, acc);
   }
-  const int nelem = kNFixedGi + n_a * kHidden + n_a + kHidden + 1;
+  const int nelem = gi_elems(n_a);
   hipLaunchKernelGGL(policy_gi_train_chunked_finish_kernel, dim3((nelem + 255) / 256 + 1), dim3(256), 0, s, (const double *)acc,
                      (int)n_a, G, (const double *)lossp, L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;

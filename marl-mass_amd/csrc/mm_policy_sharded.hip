@@ -1,0 +1,344 @@
+// mm_policy_sharded.hip -- one gradient over a batch that is sharded over ranks, in two phases: mm_policy_gi_train_partial /
+// mm_policy_gi_train_finish (include/mm_policy_gi_train.h) and mm_policy_train_partial / mm_policy_train_finish
+// (include/mm_policy_train.h).
+//
+// The chunked entries (mm_policy_chunked.hip) already work in stages: kernels A and B in passes, every pass's partial blocks added
+// into an fp64 accumulator block per network, one finish kernel that rounds the block to float32 in torch layout.  Here the
+// accumulator is the caller's: `partial` runs the same prep and the same passes on the rank's own samples -- the SAME kernels
+// through the launch helpers of mm_policy_chunked.h, kernel A scaled by the count B of the WHOLE batch, which the caller gives --
+// and leaves a shard block
+//
+//   [0] B   [1] the rank's own count of valid samples   [2] the configuration word   [3] 0
+//   [4] [5] the un-normalised fp64 loss sums (shared network: actor, critic heads; separate networks: actor, critic)
+//   [6 ..)  the accumulator block(s): PartialBlock<5> (shared network) | PartialBlock<4> actor, PartialBlock<4> critic
+//
+// and `finish` folds R of them: one thread per gradient element starts from block 0's value, adds blocks 1 .. R - 1 in index
+// order in fp64, rounds once to float32 and writes it through the index maps of the chunked finish kernels; the last workgroup
+// adds the R loss doubles in index order and scales them with the chunked finish's expression.  With R = 1 and B the rank's own
+// count every one of these steps is the chunked entry's, so the results are its bits.
+//
+// finish cannot refuse on the host what is wrong on the device, so every wave first reads the R headers: every block must carry
+// the same B and configuration word, the word must be that of the call (n_s, n_a) and name every requested network, and the
+// local counts must add up to B.  If not, every requested gradient and every loss is written as NaN.  B == 0 writes zeros.
+// No floating-point atomics; only enqueues on the stream.
+#include "mm_policy_chunked.h"
+
+namespace mm {
+namespace sharded {
+
+using namespace mfma;
+using namespace chunked;
+
+constexpr int kHeader = 4, kLoss = 2, kAcc = kHeader + kLoss;  // doubles
+constexpr long long kGiDoubles = kAcc + PartGi::kSize, kPtDoubles = kAcc + 2ll * PartPt::kSize;
+static_assert(kGiDoubles == MM_GI_SHARD_DOUBLES && kPtDoubles == MM_PT_SHARD_DOUBLES, "the shard blocks of the public headers");
+constexpr int kNetActor = 1, kNetCritic = 2;  // the configuration word's networks (the shared network is both)
+
+// n_s + 2^8 n_a + 2^16 (reference form + 2 huber) + 2^24 networks: an integer below 2^31, exact in a double
+static double config_word(int n_s, int n_a, bool ref_form, bool huber, int nets) {
+  return (double)(n_s + 256 * n_a + 65536 * ((ref_form ? 1 : 0) + (huber ? 2 : 0)) + 16777216 * nets);
+}
+
+// ---- the end of `partial`: the rank's loss partials folded with the chunked finish's tree, and the header.
+// interleaved (shared network): one workgroup, both sums per tile in lossp0.  Otherwise workgroup k folds network k's array
+// (NULL: the network is not there and its sum stays the memset's zero).
+__global__ __launch_bounds__(256) void train_shard_header_kernel(const double *__restrict__ lossp0, const double *__restrict__ lossp1,
+                                                                 long long ntiles, int interleaved, const int *__restrict__ count,
+                                                                 const int *__restrict__ local, double config,
+                                                                 double *__restrict__ shard) {
+  __shared__ double ssum[2][256];
+  if (interleaved) {
+    loss_tree<2>(lossp0, ntiles, ssum);
+    if (threadIdx.x == 0) {
+      shard[kHeader] = ssum[0][0];
+      shard[kHeader + 1] = ssum[1][0];
+    }
+  } else {
+    const double *lp = blockIdx.x ? lossp1 : lossp0;
+    if (lp) {
+      loss_tree<1>(lp, ntiles, *reinterpret_cast<double(*)[1][256]>(&ssum[0]));
+      if (threadIdx.x == 0) shard[kHeader + blockIdx.x] = ssum[0][0];
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    shard[0] = (double)*count;
+    shard[1] = local ? (double)*local : 0.0;
+    shard[2] = config;
+    shard[3] = 0.0;
+  }
+}
+
+// ---- finish
+struct FinishArgs {
+  const double *blocks;
+  long long stride;  // doubles from one block to the next
+  int n_blocks, shared_net, n_s, n_a, want;  // want: the networks whose gradients are written
+  int nelem_a, nelem_c;                      // gradient elements of the first / second requested network (0: not requested)
+  MMGiParams gi;
+  MMMlpParams actor, critic;
+  float *loss;
+};
+
+// What the R headers say, computed by every wave alone (lane r reads block r): 0 = inconsistent, 1 = consistent.
+MM_DEV int shard_headers(const FinishArgs &a, double &b_out, int &mode) {
+  const int lane = threadIdx.x & 63;
+  const double b0 = a.blocks[0], w0 = a.blocks[2];
+  double c = 0.0;
+  bool bad = false;
+  if (lane < a.n_blocks) {
+    const double *h = a.blocks + lane * a.stride;
+    c = h[1];
+    bad = h[0] != b0 || h[2] != w0 || !(c >= 0.0 && c <= 2147483647.0);
+    if (bad) c = 0.0;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);  // (integers below 2^37: exact in any order)
+  bad = __ballot(bad) != 0;
+  if (!(b0 >= 0.0 && b0 <= 2147483647.0) || !(w0 >= 0.0 && w0 < 2147483648.0)) bad = true;
+  const int w = bad ? 0 : (int)w0;
+  if ((double)w != w0 || (double)(int)(bad ? 0.0 : b0) != b0) bad = true;
+  if ((w & 255) != a.n_s || ((w >> 8) & 255) != a.n_a || ((w >> 24) & a.want) != a.want) bad = true;
+  if (c != b0) bad = true;
+  b_out = b0;
+  mode = (w >> 16) & 255;
+  return bad ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void train_shard_finish_kernel(const FinishArgs a) {
+  double b;
+  int mode;
+  const int ok = shard_headers(a, b, mode);
+  const float nan = __builtin_nanf("");
+  if (blockIdx.x == gridDim.x - 1) {
+    if (threadIdx.x != 0) return;
+    double s[kLoss];
+#pragma unroll
+    for (int k = 0; k < kLoss; k++) s[k] = a.blocks[kHeader + k];
+    for (int r = 1; r < a.n_blocks; r++) {
+#pragma unroll
+      for (int k = 0; k < kLoss; k++) s[k] += a.blocks[r * a.stride + kHeader + k];
+    }
+    const int nb = (int)b;
+    const double inv = nb > 0 ? 1.0 / (double)nb : 0.0;
+    const bool ref = mode & 1;
+    if (a.shared_net) {
+      const float la = (float)(-s[0] * inv * (ref ? inv : 1.0)), lc = (float)(s[1] * inv);
+      a.loss[0] = ok ? la : nan;
+      a.loss[1] = ok ? lc : nan;
+      a.loss[2] = ok ? la + lc : nan;
+    } else {
+      const float la = (a.want & kNetActor) ? (float)(ref ? -s[0] * inv * inv : -s[0] * inv) : 0.0f;
+      const float lc = (a.want & kNetCritic) ? (float)(s[1] * inv) : 0.0f;
+      a.loss[0] = ok ? la : nan;
+      a.loss[1] = ok ? lc : nan;
+    }
+    return;
+  }
+  int t = blockIdx.x * 256 + threadIdx.x, src;
+  float *dst;
+  if (a.shared_net) {
+    if (t >= a.nelem_a) return;
+    dst = gi_grad_slot(t, a.n_a, a.gi, src);
+  } else if (t < a.nelem_a) {
+    dst = pt_grad_slot(t, a.n_s, kHidden, a.n_a, a.actor, src);
+  } else {
+    t -= a.nelem_a;
+    if (t >= a.nelem_c) return;
+    dst = pt_grad_slot(t, a.n_s, kHidden + a.n_a, 1, a.critic, src);
+    src += PartPt::kSize;
+  }
+  if (!dst) return;
+  float out = nan;
+  if (ok) {
+    const double *p = a.blocks + kAcc + src;
+    double sum = p[0];
+#pragma unroll 4
+    for (int r = 1; r < a.n_blocks; r++) sum += p[r * a.stride];
+    out = b > 0.0 ? (float)sum : 0.0f;
+  }
+  *dst = out;
+}
+
+static bool aligned(const void *p, uintptr_t to) { return p && !((uintptr_t)p & (to - 1)); }
+
+static int launch_finish(hipStream_t s, FinishArgs &a, const double *blocks, int32_t n_blocks, int64_t stride, float *loss) {
+  a.blocks = blocks; a.stride = stride; a.n_blocks = n_blocks; a.loss = loss;
+  hipLaunchKernelGGL(train_shard_finish_kernel, dim3((a.nelem_a + a.nelem_c + 255) / 256 + 1), dim3(256), 0, s, a);
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+
+}  // namespace sharded
+}  // namespace mm
+
+extern "C" int32_t mm_policy_gi_train_shard_bytes(uint64_t *bytes) {
+  if (!bytes) return MM_ERR_INVALID_ARG;
+  *bytes = (uint64_t)mm::sharded::kGiDoubles * sizeof(double);
+  return MM_OK;
+}
+
+extern "C" int32_t mm_policy_train_shard_bytes(uint64_t *bytes) {
+  if (!bytes) return MM_ERR_INVALID_ARG;
+  *bytes = (uint64_t)mm::sharded::kPtDoubles * sizeof(double);
+  return MM_OK;
+}
+
+extern "C" int32_t mm_policy_gi_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                              int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                              const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a,
+                                              float clip_param, int32_t critic_loss, const float *adv_sums, const int32_t *count,
+                                              double *shard, float *logp_taken, float *value, float *ratio, void *scratch,
+                                              uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
+  using namespace mm::sharded;
+  namespace gi = mm::gi_train;
+  if (!weights || !aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
+  const MMGiParams W = *weights;  // (passed to the kernels by value)
+  float *const wp[12] = {W.W11, W.b11, W.W12, W.b12, W.W13, W.b13, W.W2, W.b2, W.Wa, W.ba, W.Wc, W.bc};
+  for (int k = 0; k < 12; k++)
+    if (!wp[k]) return MM_ERR_INVALID_ARG;
+  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
+  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
+  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool huber = critic_loss == MM_GI_CRITIC_HUBER;
+  const double config = config_word(n_s, n_a, adv_sums != nullptr, huber, kNetActor | kNetCritic);
+  // everything that can refuse the call comes before the first enqueue
+  ChunkLayout L = {};
+  if (n > 0) {
+    if (!obs || !actions || !returns || !old_logp || obs_stride < n_s) return MM_ERR_INVALID_ARG;
+    L = chunk_layout(gi::layout_of(chunk), n, 2, PartGi::kSize, 1);
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
+    const long long last = n % chunk ? n % chunk : (long long)chunk;  // the two pass sizes there are: chunk and the last pass's
+    if (gi::layout_of(n < chunk ? n : chunk).slices > L.blocks || gi::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
+  }
+  if (hipMemsetAsync(shard, 0, kGiDoubles * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
+  if (n == 0) {  // an empty shard: a valid all-zero block with local count 0
+    hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)nullptr, (const double *)nullptr, 0ll, 1,
+                       (const int *)count, (const int *)nullptr, config, shard);
+    return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+  }
+  float *sc = (float *)scratch;
+  int *local = (int *)sc;
+  double *acc = shard + kAcc, *lossp = (double *)(sc + L.lossp);
+  if (hipMemsetAsync(local, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
+  gi::launch_prep(s, W.W2, (float4 *)(sc + L.rows.frag), valid, (long long)n, local);
+  gi::PassArgs p = {};
+  p.obs_stride = obs_stride; p.act_stride = act_stride; p.ret_stride = ret_stride; p.w = W; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = huber; p.adv_sums = adv_sums; p.count = count;  // (kernel A scales by the WHOLE batch's B)
+  p.frag = (const float4 *)(sc + L.rows.frag); p.rows = rows_of(sc, L.rows);
+  for (long long c0 = 0; c0 < n; c0 += chunk) {
+    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
+    const Layout P = gi::layout_of(np);  // the pass's tiles and slices
+    p.n = np;
+    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = returns + c0 * ret_stride;
+    p.old_logp = old_logp + c0; p.valid = shifted(valid, c0);
+    p.lossp = lossp + 2 * (c0 / 32);
+    p.logp_out = shifted(logp_taken, c0); p.value_out = shifted(value, c0); p.ratio_out = shifted(ratio, c0);
+    gi::launch_sample(s, p);
+    gi::launch_wgrad(s, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
+    accumulate(s, sc + L.part, P.slices, PartGi::kSize, acc);
+  }
+  hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)lossp, (const double *)nullptr, L.ntiles, 1,
+                     (const int *)count, (const int *)local, config, shard);
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+
+extern "C" int32_t mm_policy_gi_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
+                                             const MMGiParams *grads, float *loss, MMStream stream) {
+  using namespace mm::sharded;
+  if (!grads || !loss || !aligned(blocks, 8)) return MM_ERR_INVALID_ARG;
+  const MMGiParams G = *grads;
+  float *const gp[12] = {G.W11, G.b11, G.W12, G.b12, G.W13, G.b13, G.W2, G.b2, G.Wa, G.ba, G.Wc, G.bc};
+  for (int k = 0; k < 12; k++)
+    if (!gp[k]) return MM_ERR_INVALID_ARG;
+  if (n_blocks < 1 || n_blocks > 64 || block_stride < kGiDoubles || n_s < 25 || n_s > 32 || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
+  FinishArgs a = {};
+  a.shared_net = 1; a.n_s = n_s; a.n_a = n_a; a.want = kNetActor | kNetCritic; a.nelem_a = gi_elems(n_a); a.gi = G;
+  return launch_finish((hipStream_t)stream, a, blocks, n_blocks, block_stride, loss);
+}
+
+static bool pt_complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
+
+extern "C" int32_t mm_policy_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                           int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                           const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
+                                           int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums,
+                                           const float *advantages, const int32_t *count, double *shard, float *logp_taken, float *value,
+                                           float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
+  using namespace mm::sharded;
+  namespace pt = mm::pt;
+  if ((!actor && !critic) || !aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
+  if ((actor && !pt_complete(actor)) || (critic && !pt_complete(critic))) return MM_ERR_INVALID_ARG;
+  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
+  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
+  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
+  if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int k2c = kHidden + n_a;
+  const bool huber = critic_loss == MM_PT_CRITIC_HUBER;
+  const double config = config_word(n_s, n_a, actor && adv_sums, huber, (actor ? kNetActor : 0) | (critic ? kNetCritic : 0));
+  // everything that can refuse the call comes before the first enqueue
+  ChunkLayout L = {};
+  if (n > 0) {
+    if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
+    if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;
+    L = chunk_layout(pt::layout_of(chunk), n, 2, PartPt::kSize, 2);
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
+    const long long last = n % chunk ? n % chunk : (long long)chunk;
+    if (pt::layout_of(n < chunk ? n : chunk).slices > L.blocks || pt::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
+  }
+  if (hipMemsetAsync(shard, 0, kPtDoubles * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
+  if (n == 0) {
+    hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)nullptr, (const double *)nullptr, 0ll, 0,
+                       (const int *)count, (const int *)nullptr, config, shard);
+    return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+  }
+  float *sc = (float *)scratch;
+  int *local = (int *)sc;
+  double *acc_a = shard + kAcc, *acc_c = acc_a + PartPt::kSize;
+  double *lossp_a = (double *)(sc + L.lossp), *lossp_c = lossp_a + L.ntiles;
+  if (hipMemsetAsync(local, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
+  pt::launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.rows.frag), valid, (long long)n,
+                  local);
+  pt::PassArgs p = {};
+  p.obs_stride = obs_stride; p.n_s = n_s; p.act_stride = act_stride; p.ret_stride = ret_stride; p.n_a = n_a;
+  p.clip_param = clip_param; p.huber = huber; p.adv_sums = adv_sums; p.count = count;  // (the WHOLE batch's B)
+  p.rows = rows_of(sc, L.rows);
+  for (long long c0 = 0; c0 < n; c0 += chunk) {
+    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
+    const Layout P = pt::layout_of(np);  // the pass's tiles and slices
+    p.n = np;
+    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = shifted(returns, c0 * ret_stride);
+    p.old_logp = shifted(old_logp, c0); p.valid = shifted(valid, c0); p.advantages = shifted(advantages, c0);
+    if (actor) {
+      p.w = *actor; p.frag = (const float4 *)(sc + L.rows.frag); p.lossp = lossp_a + c0 / 32;
+      p.out0 = shifted(logp_taken, c0); p.out1 = shifted(ratio, c0);
+      pt::launch_sample(s, false, p);
+      pt::launch_wgrad(s, false, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
+      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_a);
+    }
+    if (critic) {
+      p.w = *critic; p.frag = (const float4 *)(sc + L.rows.frag + pt::critic_frag_offset()); p.lossp = lossp_c + c0 / 32;
+      p.out0 = shifted(value, c0); p.out1 = nullptr;
+      pt::launch_sample(s, true, p);
+      pt::launch_wgrad(s, true, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
+      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_c);
+    }
+  }
+  hipLaunchKernelGGL(train_shard_header_kernel, dim3(2), dim3(256), 0, s, (const double *)(actor ? lossp_a : nullptr),
+                     (const double *)(critic ? lossp_c : nullptr), L.ntiles, 0, (const int *)count, (const int *)local, config, shard);
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+
+extern "C" int32_t mm_policy_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
+                                          const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss,
+                                          MMStream stream) {
+  using namespace mm::sharded;
+  if ((!actor_grads && !critic_grads) || !loss || !aligned(blocks, 8)) return MM_ERR_INVALID_ARG;
+  if ((actor_grads && !pt_complete(actor_grads)) || (critic_grads && !pt_complete(critic_grads))) return MM_ERR_INVALID_ARG;
+  if (n_blocks < 1 || n_blocks > 64 || block_stride < kPtDoubles || n_s < 25 || n_s > 32 || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
+  FinishArgs a = {};
+  a.n_s = n_s; a.n_a = n_a;
+  if (actor_grads) { a.want |= kNetActor; a.nelem_a = pt_elems(n_s, kHidden, n_a); a.actor = *actor_grads; }
+  if (critic_grads) { a.want |= kNetCritic; a.nelem_c = pt_elems(n_s, kHidden + n_a, 1); a.critic = *critic_grads; }
+  return launch_finish((hipStream_t)stream, a, blocks, n_blocks, block_stride, loss);
+}

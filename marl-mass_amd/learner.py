@@ -27,6 +27,14 @@ With `scratch_budget_bytes` a learner never holds more than that: a call whose u
 gradient of ONE loss over all its samples with `mm_policy_gi_train_chunked` / `mm_policy_train_chunked` /
 `mm_policy_wide_train_chunked` (hidden 512), in passes through the rows of the largest chunk that fits -- still one optimiser
 step, the same losses bit for bit.
+
+With `shard_group` (a torch.distributed process group, or "world") a learner trains on a batch that is SHARDED over ranks, as the
+rollout's envs are: every agent step of train() takes the gradient of ONE loss over all ranks' samples.  Each rank runs
+`shard_block` on its own samples (`mm_policy_gi_train_partial` / `mm_policy_train_partial`: the chunked entry's passes into a
+caller-visible fp64 block, scaled by the whole batch's count), the R blocks are gathered in rank order and `finish_shards`
+(`mm_policy_*_train_finish`) folds them in that order on every rank: the same bits from the same blocks, so replicas that start
+equal stay bit-equal without a broadcast (`replicas_in_sync()` checks it).  Both phases are public and need no process group.
+Limits: a sharded train() is not graph-capturable (it runs collectives), and hidden 512 with `shard_group` is a ValueError.
 """
 import copy
 import ctypes as C
@@ -181,6 +189,36 @@ def _batch(states, actions, returns, valid):
     return states, actions, returns, valid, N, S
 
 
+def gather_in_rank_order(tensor, group=None):
+    """`tensor` of every rank of `group` (None: the default group), stacked in rank order: [R, *tensor.shape] on tensor's device,
+    identical on every rank.  On the device where the backend can (nccl, which is RCCL here); under gloo a device tensor goes
+    through a host copy, as reduce_rollout_metrics does."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    src = tensor.detach().contiguous()
+    if src.is_cuda and "nccl" in str(dist.get_backend(group)):
+        out = torch.empty((world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+        dist.all_gather_into_tensor(out, src, group=group)
+        return out
+    host = src.cpu()
+    parts = [torch.empty_like(host) for _ in range(world)]
+    dist.all_gather(parts, host, group=group)
+    return torch.stack(parts).to(tensor.device)
+
+
+def fold_rank_sums(packed, with_sums):
+    """[R, 3] float64 (each rank's float32 S+, S- and its count of valid samples) -> (the whole batch's float32 [2] adv_sums, or
+    None without with_sums; its int32 [1] count), added in rank order: every rank gets the same bits."""
+    count = packed[:, 2].sum().to(torch.int32).reshape(1)
+    if not with_sums:
+        return None, count
+    parts = packed[:, :2].to(torch.float32)
+    sums = parts[0]
+    for r in range(1, parts.shape[0]):
+        sums = sums + parts[r]
+    return sums, count
+
+
 class _DeviceLearner(object):
     """What both learners need around a library call: the current stream and a scratch buffer that only grows.
     `scratch_bytes` is the library's size query of the subclass's call, n -> bytes."""
@@ -229,6 +267,70 @@ class _DeviceLearner(object):
     def _ensure_scratch(self, n):
         return self._grow(self._scratch_bytes(n))
 
+    # -- a batch sharded over ranks ------------------------------------------------------------
+    def _init_shards(self, shard_group, require_sharded, block_doubles):
+        """shard_group None: train() is the single-device one.  A process group or "world" (the default group): every agent
+        step of train() is partial + gather + finish over the group's ranks."""
+        self.sharded, self._shard_n_s = shard_group is not None, 25
+        self._shard_group = None if (shard_group is None or shard_group == "world") else shard_group
+        self._require_sharded, self._block_doubles = require_sharded, block_doubles
+        if self.sharded:
+            require_sharded()
+
+    def shard_doubles(self):
+        """K, the length of a shard block in doubles."""
+        self._require_sharded()
+        return self._block_doubles()
+
+    def _shard_plan(self, n):
+        """(chunk, scratch) of shard_block on n samples: _plan's chunk, or one pass (the multiple of 64 at or above n) where
+        _plan would take the unchunked entry."""
+        chunk, scratch = self._plan(n)
+        if chunk is None:
+            chunk = max(64, (n + 63) // 64 * 64)
+            scratch = self._grow(self._chunked_bytes(n, chunk))
+        return chunk, scratch
+
+    def _shard_out(self, out):
+        K = self.shard_doubles()
+        if out is None:
+            return torch.empty(K, dtype=torch.float64, device=self.device)
+        if out.dtype != torch.float64 or tuple(out.shape) != (K,) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous float64 [%d] tensor on the learner's device" % K)
+        return out
+
+    def _shard_blocks(self, blocks):
+        K = self.shard_doubles()
+        if (blocks.dtype != torch.float64 or blocks.dim() != 2 or blocks.shape[1] != K or not 1 <= blocks.shape[0] <= 64
+                or blocks.stride(1) != 1 or (blocks.shape[0] > 1 and blocks.stride(0) < K) or blocks.device != self.device):
+            raise ValueError("blocks must be float64 [R, %d] on the learner's device, 1 <= R <= 64, rows contiguous" % K)
+        return blocks, max(blocks.stride(0), K)
+
+    def _sharded_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, **kw):
+        """One agent step's gradient over all ranks' samples: the local (S+, S-) and count, gathered and added in rank order;
+        shard_block on the local samples; the R blocks gathered in rank order; finish_shards."""
+        packed = torch.zeros(3, dtype=torch.float64, device=self.device)
+        if adv_sums is not None:
+            packed[:2] = adv_sums.to(torch.float32).double()
+        packed[2] = obs.shape[0] if valid is None else (valid != 0).sum()
+        sums, count = fold_rank_sums(gather_in_rank_order(packed, self._shard_group), adv_sums is not None)
+        block = self.shard_block(obs, actions, returns, old_logp, count, valid=valid, adv_sums=sums, **kw)
+        return self.finish_shards(gather_in_rank_order(block, self._shard_group))
+
+    def _replica_tensors(self):
+        raise NotImplementedError
+
+    def replicas_in_sync(self):
+        """Whether every rank of the shard group holds the same parameter bytes (the networks and their targets): one gather
+        of a 64-bit checksum per rank.  Synchronises with the host.  Without a shard group there is one replica: True."""
+        if not self.sharded:
+            return True
+        words = torch.cat([t.detach().reshape(-1) for t in self._replica_tensors()]).view(torch.int32).to(torch.int64)
+        weights = torch.arange(1, words.numel() + 1, dtype=torch.int64, device=words.device) * 0x9E3779B1 + 1
+        checksum = ((words + 0x7F4A7C15) * weights).sum().reshape(1)  # (int64 arithmetic wraps: a position-dependent sum)
+        every = gather_in_rank_order(checksum, self._shard_group)
+        return bool((every == every[0]).all())
+
     def _grow(self, need):
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)  # (allocate before a graph capture)
@@ -275,9 +377,10 @@ class SharedPPOLearner(_DeviceLearner):
     float32, on the device -- typically the module a DeviceRollout acts with, so the next rollout uses the updated weights."""
 
     def __init__(self, policy, clib, lr=1e-4, optimizer_type="rmsprop", clip_param=0.2, critic_loss="mse", max_grad_norm=0.5,
-                 target_tau=1.0, target_update_steps=5, fused_step=False, scratch_budget_bytes=None):
+                 target_tau=1.0, target_update_steps=5, fused_step=False, scratch_budget_bytes=None, shard_group=None):
         # (first: a budget no call can meet is refused whatever else is passed)
         self._init_budget(scratch_budget_bytes, clib.require_policy_gi_train_chunked, clib.policy_gi_train_chunked_scratch_bytes)
+        self._init_shards(shard_group, clib.require_policy_gi_train_sharded, clib.policy_gi_train_shard_doubles)
         if type(policy) is not ActorCriticNetwork or not policy.state_split or policy.fc2.weight.shape[0] != 128:
             raise ValueError("SharedPPOLearner needs rollout.ActorCriticNetwork(state_split=True) with hidden size 128")
         p0 = policy.fc2.weight
@@ -335,14 +438,7 @@ class SharedPPOLearner(_DeviceLearner):
             adv = torch.where(valid.bool(), adv, torch.zeros_like(adv))
         return torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
 
-    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, diagnostics=False):
-        """The bare launch: writes d(actor_loss + critic_loss)/d(parameter) into every policy parameter's .grad and returns
-        the float32 [3] tensor (actor loss, critic loss, their sum); with diagnostics also (logp_taken, value, ratio) [n].
-        obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns float32 [n] (any stride),
-        old_logp float32 [n], valid uint8 / bool [n] or None.  adv_sums: float32 [2] (S+, S-) for the reference's [B, B]
-        objective, None for per-sample PPO-clip (see the module docstring).  Only enqueues work: no host synchronisation.
-        With a scratch budget that the unchunked call's scratch exceeds, the same gradient comes from
-        mm_policy_gi_train_chunked in passes of the largest chunk that fits."""
+    def _inputs(self, obs, actions, returns, old_logp, valid, adv_sums):
         n, S = obs.shape
         if obs.dtype != torch.float32 or (n and obs.stride(1) != 1):
             raise ValueError("obs must be float32 [n, S] with contiguous rows")
@@ -355,11 +451,28 @@ class SharedPPOLearner(_DeviceLearner):
             valid = valid.to(torch.uint8).contiguous()
         if adv_sums is not None:
             adv_sums = adv_sums.to(torch.float32).contiguous()
-        W, G = abi.MMGiParams(), abi.MMGiParams()
+        return n, S, old_logp, valid, adv_sums
+
+    def _structs(self, grads):
+        """(the parameters' MMGiParams, the gradients' or None)."""
+        W, G = abi.MMGiParams(), abi.MMGiParams() if grads else None
         for name, p in zip(abi.GI_PARAMS, _params(self.policy)):
-            _ensure_grad(p)
             setattr(W, name, p.detach().data_ptr())
-            setattr(G, name, p.grad.data_ptr())
+            if grads:
+                _ensure_grad(p)
+                setattr(G, name, p.grad.data_ptr())
+        return W, G
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, diagnostics=False):
+        """The bare launch: writes d(actor_loss + critic_loss)/d(parameter) into every policy parameter's .grad and returns
+        the float32 [3] tensor (actor loss, critic loss, their sum); with diagnostics also (logp_taken, value, ratio) [n].
+        obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns float32 [n] (any stride),
+        old_logp float32 [n], valid uint8 / bool [n] or None.  adv_sums: float32 [2] (S+, S-) for the reference's [B, B]
+        objective, None for per-sample PPO-clip (see the module docstring).  Only enqueues work: no host synchronisation.
+        With a scratch budget that the unchunked call's scratch exceeds, the same gradient comes from
+        mm_policy_gi_train_chunked in passes of the largest chunk that fits."""
+        n, S, old_logp, valid, adv_sums = self._inputs(obs, actions, returns, old_logp, valid, adv_sums)
+        W, G = self._structs(True)
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
         diag = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3)] if diagnostics else [None] * 3
         chunk, scratch = self._plan(n)
@@ -374,6 +487,51 @@ class SharedPPOLearner(_DeviceLearner):
         else:
             self.clib.check(self.clib.lib.mm_policy_gi_train_chunked(*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
+
+    # -- the two phases of a gradient over rank-sharded batches --------------------------------
+    def shard_block(self, obs, actions, returns, old_logp, count, valid=None, adv_sums=None, diagnostics=False, out=None):
+        """Phase one, on this rank's samples (mm_policy_gi_train_partial): the float64 [K] shard block on the device (written
+        into `out` when given); with diagnostics also (logp_taken, value, ratio) [n].  The inputs are loss_and_grad's, n == 0
+        included (an empty shard); `count` is an int32 [1] device tensor holding B, the number of valid samples of the WHOLE
+        batch over all ranks, and adv_sums is the whole batch's (S+, S-).  The passes are _plan(n)'s chunk; without a budget, or
+        where the unchunked scratch fits it, one pass.  Touches no .grad.  Only enqueues work."""
+        self.clib.require_policy_gi_train_sharded()
+        n, S, old_logp, valid, adv_sums = self._inputs(obs, actions, returns, old_logp, valid, adv_sums)
+        if count.dtype != torch.int32 or count.numel() != 1 or count.device != self.device:
+            raise ValueError("count must be an int32 tensor of one element on the learner's device")
+        block = self._shard_out(out)
+        self._shard_n_s = S
+        W, _ = self._structs(False)
+        diag = [torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3)] if diagnostics else [None] * 3
+        chunk, scratch = self._shard_plan(n)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_gi_train_partial(
+            obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
+            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), C.byref(W), self.policy.fc2.weight.shape[0], self.n_a,
+            self.clip_param, abi.GI_CRITIC_LOSS[self.critic_loss], opt(adv_sums), count.data_ptr(), block.data_ptr(), opt(diag[0]),
+            opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream(), chunk))
+        return (block, tuple(diag)) if diagnostics else block
+
+    def finish_shards(self, blocks, n_s=None):
+        """Phase two (mm_policy_gi_train_finish): blocks float64 [R, K], the R ranks' shard blocks in rank order.  Writes every
+        policy parameter's .grad -- float32 of the blocks' fp64 sum in row order -- and returns the float32 [3] loss tensor of
+        loss_and_grad.  Blocks that do not belong together (another B or configuration, local counts that do not add up to
+        B) give NaN everywhere.  n_s: the state columns the blocks were built with; None: those of this learner's last
+        shard_block."""
+        self.clib.require_policy_gi_train_sharded()
+        blocks, stride = self._shard_blocks(blocks)
+        _, G = self._structs(True)
+        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        n_s = self._shard_n_s if n_s is None else n_s  # (the network reads columns 0..24 whatever S is: only the blocks say)
+        self.clib.check(self.clib.lib.mm_policy_gi_train_finish(blocks.data_ptr(), blocks.shape[0], stride, n_s, self.n_a, C.byref(G),
+                                                                loss.data_ptr(), self._stream()))
+        return loss
+
+    def _replica_tensors(self):
+        return _params(self.policy) + _params(self.policy_target)
+
+    def _grad(self, *args, **kw):
+        return self._sharded_grad(*args, **kw) if self.sharded else self.loss_and_grad(*args, **kw)
 
     # -- MAPPO_GI.train() ----------------------------------------------------------------------
     def _step(self, n_episodes):
@@ -408,13 +566,13 @@ class SharedPPOLearner(_DeviceLearner):
                 dense = obs.contiguous()
                 old = self.old_log_probs(dense, act)
                 sums = self.advantage_sums(dense, ret, v)
-                losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, adv_sums=sums))
+                losses.append(self._grad(obs, act, ret, old, valid=v, adv_sums=sums))
                 self._step(n_episodes)
         elif form == "flat":
             obs, act, ret = states.reshape(-1, S), actions.reshape(-1), returns.reshape(-1)
             v = None if valid is None else valid.reshape(-1)
             old = self.old_log_probs(obs, act)
-            losses.append(self.loss_and_grad(obs, act, ret, old, valid=v))
+            losses.append(self._grad(obs, act, ret, old, valid=v))
             self._step(n_episodes)
         else:
             raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
@@ -457,12 +615,15 @@ class PPOLearner(_DeviceLearner):
 
     def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
-                 soft_update_every="train", scratch_budget_bytes=None):
+                 soft_update_every="train", scratch_budget_bytes=None, shard_group=None):
+        if shard_group is not None and _hidden_of(actor) == 512:
+            raise ValueError("shard_group is not supported with hidden size 512: the rank-sharded gradient entries are hidden 128")
         # (first: a budget no call can meet is refused whatever else is passed; the smallest pass is that of the hidden size)
         if _hidden_of(actor) == 512:
             self._init_budget(scratch_budget_bytes, clib.require_policy_wide_train_chunked, clib.policy_wide_train_chunked_scratch_bytes)
         else:
             self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
+        self._init_shards(shard_group, clib.require_policy_train_sharded, clib.policy_train_shard_doubles)
         if soft_update_every not in ("train", "agent_step"):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
@@ -561,17 +722,7 @@ class PPOLearner(_DeviceLearner):
         adv = self.advantages(obs, actions, returns, valid)
         return torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
 
-    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, advantages=None, diagnostics=False,
-                      networks="both"):
-        """The bare launch: writes d(actor loss)/d(actor parameter) and d(critic loss)/d(critic parameter) into every
-        parameter's .grad and returns the float32 [2] tensor (actor loss, critic loss); with diagnostics also
-        (logp_taken, value, ratio) [n].  obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns
-        float32 [n] (any stride), old_logp float32 [n], valid uint8 / bool [n] or None.  Exactly one of adv_sums -- float32
-        [2] (S+, S-): the reference's [B, B] objective -- and advantages -- float32 [n]: per-sample PPO-clip.  networks
-        "both" | "actor" | "critic": the other one's gradient and loss are left out (its .grad is not touched, its loss is 0).
-        Only enqueues work: no host synchronisation.  With a scratch budget that the unchunked call's scratch exceeds, the
-        same gradients come from mm_policy_train_chunked (hidden 512: mm_policy_wide_train_chunked) in passes of the largest chunk
-        that fits."""
+    def _inputs(self, obs, actions, returns, old_logp, valid, adv_sums, advantages, networks):
         n, S = self._check_batch(obs, actions)
         if networks not in ("both", "actor", "critic"):
             raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
@@ -586,7 +737,21 @@ class PPOLearner(_DeviceLearner):
             if advantages.shape[0] != n:
                 raise ValueError("advantages must be [n]")
             advantages = advantages.to(torch.float32).contiguous()
-        with_a, with_c = networks != "critic", networks != "actor"
+        return n, S, old_logp, valid, adv_sums, advantages, networks != "critic", networks != "actor"
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, valid=None, adv_sums=None, advantages=None, diagnostics=False,
+                      networks="both"):
+        """The bare launch: writes d(actor loss)/d(actor parameter) and d(critic loss)/d(critic parameter) into every
+        parameter's .grad and returns the float32 [2] tensor (actor loss, critic loss); with diagnostics also
+        (logp_taken, value, ratio) [n].  obs float32 [n, S] (unit column stride, any row stride), actions int32 [n] and returns
+        float32 [n] (any stride), old_logp float32 [n], valid uint8 / bool [n] or None.  Exactly one of adv_sums -- float32
+        [2] (S+, S-): the reference's [B, B] objective -- and advantages -- float32 [n]: per-sample PPO-clip.  networks
+        "both" | "actor" | "critic": the other one's gradient and loss are left out (its .grad is not touched, its loss is 0).
+        Only enqueues work: no host synchronisation.  With a scratch budget that the unchunked call's scratch exceeds, the
+        same gradients come from mm_policy_train_chunked (hidden 512: mm_policy_wide_train_chunked) in passes of the largest chunk
+        that fits."""
+        n, S, old_logp, valid, adv_sums, advantages, with_a, with_c = self._inputs(obs, actions, returns, old_logp, valid, adv_sums,
+                                                                                    advantages, networks)
         W = [_mlp_struct(self.actor) if with_a else None, _mlp_struct(self.critic) if with_c else None]
         G = [_mlp_struct(self.actor, True) if with_a else None, _mlp_struct(self.critic, True) if with_c else None]
         ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
@@ -605,6 +770,58 @@ class PPOLearner(_DeviceLearner):
         else:
             self.clib.check(self._entries[3](*args, chunk))
         return (loss, tuple(diag)) if diagnostics else loss
+
+    # -- the two phases of a gradient over rank-sharded batches --------------------------------
+    def shard_block(self, obs, actions, returns, old_logp, count, valid=None, adv_sums=None, advantages=None, diagnostics=False,
+                    out=None, networks="both"):
+        """Phase one, on this rank's samples (mm_policy_train_partial): the float64 [K] shard block on the device (written into
+        `out` when given); with diagnostics also (logp_taken, value, ratio) [n].  The inputs are loss_and_grad's, n == 0 included
+        (an empty shard); `count` is an int32 [1] device tensor holding B, the number of valid samples of the WHOLE batch over
+        all ranks, and adv_sums is the whole batch's (S+, S-).  The passes are _plan(n)'s chunk; without a budget, or where the
+        unchunked scratch fits it, one pass.  Touches no .grad.  Only enqueues work.  Hidden 128 only."""
+        if self.hidden != 128:
+            raise ValueError("the rank-sharded gradient entries are hidden 128")
+        self.clib.require_policy_train_sharded()
+        n, S, old_logp, valid, adv_sums, advantages, with_a, with_c = self._inputs(obs, actions, returns, old_logp, valid, adv_sums,
+                                                                                    advantages, networks)
+        if count.dtype != torch.int32 or count.numel() != 1 or count.device != self.device:
+            raise ValueError("count must be an int32 tensor of one element on the learner's device")
+        block = self._shard_out(out)
+        W = [_mlp_struct(self.actor) if with_a else None, _mlp_struct(self.critic) if with_c else None]
+        ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
+        new = lambda on: torch.empty(n, dtype=torch.float32, device=self.device) if (diagnostics and on) else None  # noqa: E731
+        diag = [new(with_a), new(with_c), new(with_a)]
+        chunk, scratch = self._shard_plan(n)
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_train_partial(
+            obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
+            returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), self.hidden, self.n_a, self.clip_param,
+            abi.PT_CRITIC_LOSS[self.critic_loss], opt(adv_sums) if with_a else None, opt(advantages) if with_a else None,
+            count.data_ptr(), block.data_ptr(), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(),
+            self._stream(), chunk))
+        return (block, tuple(diag)) if diagnostics else block
+
+    def finish_shards(self, blocks, networks="both"):
+        """Phase two (mm_policy_train_finish): blocks float64 [R, K], the R ranks' shard blocks in rank order.  Writes the .grad
+        of every parameter of the requested networks -- float32 of the blocks' fp64 sum in row order -- and returns the float32
+        [2] loss tensor of loss_and_grad (0 for a network that is not requested).  Blocks that do not belong together (another B
+        or configuration, local counts that do not add up to B, a requested network missing from a block) give NaN everywhere."""
+        if networks not in ("both", "actor", "critic"):
+            raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
+        self.clib.require_policy_train_sharded()
+        blocks, stride = self._shard_blocks(blocks)
+        G = [_mlp_struct(self.actor, True) if networks != "critic" else None, _mlp_struct(self.critic, True) if networks != "actor" else None]
+        ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
+        loss = torch.empty(2, dtype=torch.float32, device=self.device)
+        self.clib.check(self.clib.lib.mm_policy_train_finish(blocks.data_ptr(), blocks.shape[0], stride, self.n_s, self.n_a, ref(G[0]),
+                                                             ref(G[1]), loss.data_ptr(), self._stream()))
+        return loss
+
+    def _replica_tensors(self):
+        return [p for net in (self.actor, self.critic, self.actor_target, self.critic_target) for p in _mlp_params(net)]
+
+    def _grad(self, *args, **kw):
+        return self._sharded_grad(*args, **kw) if self.sharded else self.loss_and_grad(*args, **kw)
 
     # -- MAPPO.train() -------------------------------------------------------------------------
     def _step(self, soft=False):
@@ -655,13 +872,13 @@ class PPOLearner(_DeviceLearner):
                 old, value = self.evaluate(obs, act, actor=self.actor_target, critic=self.critic_target, valid=v)
                 adv = self._adv(ret, value, v)
                 sums = torch.stack([adv.clamp(min=0).sum(), adv.clamp(max=0).sum()])
-                losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, adv_sums=sums))
+                losses.append(self._grad(obs, act, ret, old, valid=v, adv_sums=sums))
                 self._step(carried(agent_id == N - 1))
         elif form == "flat":
             obs, act, ret = states.reshape(-1, S), actions.reshape(-1), returns.reshape(-1)
             v = None if valid is None else valid.reshape(-1)
             old, value = self.evaluate(obs, act, actor=self.actor_target, critic=self.critic_target, valid=v)
-            losses.append(self.loss_and_grad(obs, act, ret, old, valid=v, advantages=self._adv(ret, value, v)))
+            losses.append(self._grad(obs, act, ret, old, valid=v, advantages=self._adv(ret, value, v)))
             self._step(carried(True))
         else:
             raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
