@@ -1,12 +1,12 @@
-// mm_policy_chunked.h -- how mm_policy_chunked.hip and mm_policy_sharded.hip reach prep, kernel A and kernel B of the two training
-// files, and what those two share (below).  The launch helpers are host-side only, defined next to the kernels they launch (mm_policy_gi_train.hip, mm_policy_train.hip): the
-// chunked entries add no __global__ to those files and edit none, so their code objects stay as recorded
-// (profiles/policy_gi_train, profiles/policy_train).  A helper only enqueues on the stream; the caller reads hipGetLastError.
+// mm_policy_chunked.h -- how the entries of the hidden-128 training files reach prep, kernel A and kernel B, and what the chunked
+// entries (mm_policy_chunked.hip) and the rank-sharded ones (mm_policy_sharded.hip) share (below).  The launch helpers are
+// host-side only, defined next to the kernels they launch (mm_policy_gi_train.hip, mm_policy_train.hip) and used by the unchunked
+// entries of those files as by the pass loops: every launch of prep, A and B is spelled once.  The pass loops add no __global__
+// to those files and edit none, so their code objects stay as recorded (profiles/policy_gi_train, profiles/policy_train).  A
+// helper only enqueues on the stream; the caller reads hipGetLastError.
 #ifndef MM_POLICY_CHUNKED_H
 #define MM_POLICY_CHUNKED_H
-#include "mm_policy_mfma.h"
-#include "../../include/mm_policy_gi_train.h"
-#include "../../include/mm_policy_train.h"
+#include "mm_policy_mfma.h"  // and with it the two public headers
 
 namespace mm {
 
@@ -43,6 +43,7 @@ mfma::Layout layout_of(long long n);  // the unchunked scratch of n samples
 void launch_prep(hipStream_t s, const float *W2, float4 *frag, const uint8_t *valid, long long n, int *count);
 void launch_sample(hipStream_t s, const PassArgs &p);
 void launch_wgrad(hipStream_t s, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part);
+bool zero_grads(hipStream_t s, const MMGiParams &g, int n_a);  // the n == 0 path: the twelve gradients; false: an enqueue failed
 
 }  // namespace gi_train
 
@@ -79,7 +80,7 @@ void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_p
 
 }  // namespace pt
 // ---- what the chunked entries (mm_policy_chunked.hip) and the rank-sharded ones (mm_policy_sharded.hip) share: the index maps of
-// the finish kernels, the chunked scratch layout and the accumulate launch
+// the finish kernels, the chunked scratch layout, the argument checks, the pass loops and the accumulate launch
 namespace chunked {
 
 typedef mfma::PartialBlock<5> PartGi;  // the shared network's partial block: 27 952 floats
@@ -155,8 +156,6 @@ struct ChunkLayout {
   int blocks;
 };
 
-static inline bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chunk <= 0x7FFFFFC0ll; }
-
 static inline ChunkLayout chunk_layout(const mfma::Layout &rows, long long n, int sums, int partial, int nets) {
   ChunkLayout L;
   L.rows = rows;
@@ -174,11 +173,32 @@ static inline SampleRows rows_of(float *sc, const mfma::Layout &R) {
   return r;
 }
 
-template <typename T>
-static inline T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
-
 // acc[off] += the `slices` partial blocks of `size` floats at part, in workgroup order, fp64 (train_chunked_accumulate_kernel)
 void accumulate(hipStream_t s, const float *part, int slices, int size, double *acc);
+
+// one separate network of a call (NULL w: not given) and its per-sample outputs: logp_taken, ratio | value, unused
+struct PtNet {
+  const MMMlpParams *w;
+  float *out0, *out1;
+};
+
+// What the chunked and the partial entry of a family refuse alike, on the whole batch's PassArgs (n the whole batch, the
+// pointers at sample 0): the weights, the shape limits, critic_loss, clip_param, chunk, diagnostics without their network and,
+// when n > 0, the per-sample inputs, adv_sums against advantages, and the scratch: its pointer, alignment and size, and that the
+// two pass sizes there are, chunk and the last pass's, cut no more slices than the partial blocks hold.  Enqueues nothing.
+// L: the scratch layout when n > 0.
+bool gi_args_ok(const gi_train::PassArgs &batch, int32_t n_s, int32_t hidden, int32_t critic_loss, int64_t chunk, const void *scratch,
+                uint64_t scratch_bytes, ChunkLayout &L);
+bool pt_args_ok(const pt::PassArgs &batch, const PtNet (&net)[2], int32_t hidden, int32_t critic_loss, int64_t chunk,
+                const void *scratch, uint64_t scratch_bytes, ChunkLayout &L);
+
+// The passes of a batch of n > 0 samples that the checks above let through: prep once over the whole batch (its count of valid
+// samples goes to the scratch header, the int at sc, which the caller has zeroed), then per pass of `chunk` samples kernel A (scaled by batch.count), kernel B and accumulate through the
+// rows of the scratch at sc, the per-sample pointers of a copy of `batch` shifted on the host.  The separate networks take turns
+// within a pass, the actor first; the critic's accumulator follows the actor's (acc + PartPt::kSize).
+void gi_passes(hipStream_t s, const gi_train::PassArgs &batch, long long chunk, const ChunkLayout &L, float *sc, double *acc);
+void pt_passes(hipStream_t s, const pt::PassArgs &batch, const PtNet (&net)[2], long long chunk, const ChunkLayout &L, float *sc,
+               double *acc);
 
 }  // namespace chunked
 }  // namespace mm

@@ -84,9 +84,89 @@ __global__ __launch_bounds__(256) void policy_train_chunked_finish_kernel(const 
   if (dst) *dst = (float)acc[src];
 }
 
-// ---- host side (the scratch layout: mm_policy_chunked.h)
+// ---- host side (the scratch layout: mm_policy_chunked.h): the accumulate launch, then each family's argument check and pass
+// loop, which the entries below run on the whole batch and the rank-sharded ones (mm_policy_sharded.hip) on a rank's samples
 void accumulate(hipStream_t s, const float *part, int slices, int size, double *acc) {
   hipLaunchKernelGGL(train_chunked_accumulate_kernel, dim3((size + 255) / 256), dim3(256), 0, s, part, slices, size, acc);
+}
+
+static bool scratch_ok(const ChunkLayout &L, Layout (*layout_of)(long long), long long n, long long chunk, const void *scratch,
+                       uint64_t scratch_bytes) {
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return false;
+  const long long last = n % chunk ? n % chunk : chunk;  // the two pass sizes there are: chunk and the last pass's
+  return layout_of(n < chunk ? n : chunk).slices <= L.blocks && layout_of(last).slices <= L.blocks;
+}
+
+bool gi_args_ok(const gi_train::PassArgs &b, int32_t n_s, int32_t hidden, int32_t critic_loss, int64_t chunk, const void *scratch,
+                uint64_t scratch_bytes, ChunkLayout &L) {
+  L = {};
+  if (!complete(&b.w) || !shape_ok(b.n, n_s, hidden, b.n_a, kHidden)) return false;
+  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return false;
+  if (!(b.clip_param >= 0.0f) || !chunk_ok(chunk)) return false;
+  if (b.n == 0) return true;  // (empty inputs and the scratch are not looked at and may be NULL)
+  if (!b.obs || !b.actions || !b.returns || !b.old_logp || b.obs_stride < n_s) return false;
+  L = chunk_layout(gi_train::layout_of(chunk), b.n, 2, PartGi::kSize, 1);
+  return scratch_ok(L, gi_train::layout_of, b.n, chunk, scratch, scratch_bytes);
+}
+
+bool pt_args_ok(const pt::PassArgs &b, const PtNet (&net)[2], int32_t hidden, int32_t critic_loss, int64_t chunk, const void *scratch,
+                uint64_t scratch_bytes, ChunkLayout &L) {
+  L = {};
+  const bool actor = net[0].w != nullptr, critic = net[1].w != nullptr;
+  if ((!actor && !critic) || (actor && !complete(net[0].w)) || (critic && !complete(net[1].w))) return false;
+  if (!shape_ok(b.n, b.n_s, hidden, b.n_a, kHidden)) return false;
+  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return false;
+  if (!(b.clip_param >= 0.0f) || !chunk_ok(chunk)) return false;
+  if ((!actor && (net[0].out0 || net[0].out1)) || (!critic && net[1].out0)) return false;
+  if (b.n == 0) return true;  // (empty inputs, adv_sums, advantages and the scratch are not looked at and may be NULL)
+  if (!b.obs || !b.actions || b.obs_stride < b.n_s || (actor && !b.old_logp) || (critic && !b.returns)) return false;
+  if (actor && ((b.adv_sums != nullptr) == (b.advantages != nullptr))) return false;
+  // the two networks' loss partials live side by side: both are folded at the end, after the passes alternated over the rows
+  L = chunk_layout(pt::layout_of(chunk), b.n, 2, PartPt::kSize, 2);
+  return scratch_ok(L, pt::layout_of, b.n, chunk, scratch, scratch_bytes);
+}
+
+void gi_passes(hipStream_t s, const gi_train::PassArgs &b, long long chunk, const ChunkLayout &L, float *sc, double *acc) {
+  namespace gi = gi_train;
+  gi::PassArgs p = b;
+  p.frag = (const float4 *)(sc + L.rows.frag);
+  p.rows = rows_of(sc, L.rows);
+  gi::launch_prep(s, b.w.W2, (float4 *)(sc + L.rows.frag), b.valid, b.n, (int *)sc);
+  for (long long c0 = 0; c0 < b.n; c0 += chunk) {
+    p.n = b.n - c0 < chunk ? b.n - c0 : chunk;
+    const Layout P = gi::layout_of(p.n);  // the pass's tiles and slices
+    p.obs = b.obs + c0 * b.obs_stride; p.actions = b.actions + c0 * b.act_stride; p.returns = b.returns + c0 * b.ret_stride;
+    p.old_logp = b.old_logp + c0; p.valid = shifted(b.valid, c0);
+    p.lossp = (double *)(sc + L.lossp) + 2 * (c0 / 32);
+    p.logp_out = shifted(b.logp_out, c0); p.value_out = shifted(b.value_out, c0); p.ratio_out = shifted(b.ratio_out, c0);
+    gi::launch_sample(s, p);
+    gi::launch_wgrad(s, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
+    accumulate(s, sc + L.part, P.slices, PartGi::kSize, acc);
+  }
+}
+
+void pt_passes(hipStream_t s, const pt::PassArgs &b, const PtNet (&net)[2], long long chunk, const ChunkLayout &L, float *sc,
+               double *acc) {
+  pt::PassArgs p = b;
+  p.rows = rows_of(sc, L.rows);
+  pt::launch_prep(s, net[0].w ? net[0].w->W2 : nullptr, net[1].w ? net[1].w->W2 : nullptr, kHidden + b.n_a,
+                  (float4 *)(sc + L.rows.frag), b.valid, b.n, (int *)sc);
+  for (long long c0 = 0; c0 < b.n; c0 += chunk) {
+    p.n = b.n - c0 < chunk ? b.n - c0 : chunk;
+    const Layout P = pt::layout_of(p.n);  // the pass's tiles and slices
+    p.obs = b.obs + c0 * b.obs_stride; p.actions = b.actions + c0 * b.act_stride; p.returns = shifted(b.returns, c0 * b.ret_stride);
+    p.old_logp = shifted(b.old_logp, c0); p.valid = shifted(b.valid, c0); p.advantages = shifted(b.advantages, c0);
+    for (int k = 0; k < 2; k++) {  // the actor, then the critic
+      if (!net[k].w) continue;
+      p.w = *net[k].w;
+      p.frag = (const float4 *)(sc + L.rows.frag + k * pt::critic_frag_offset());
+      p.lossp = (double *)(sc + L.lossp) + k * L.ntiles + c0 / 32;
+      p.out0 = shifted(net[k].out0, c0); p.out1 = shifted(net[k].out1, c0);
+      pt::launch_sample(s, k != 0, p);
+      pt::launch_wgrad(s, k != 0, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
+      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc + k * PartPt::kSize);
+    }
+  }
 }
 
 }  // namespace chunked
@@ -106,54 +186,28 @@ extern "C" int32_t mm_policy_gi_train_chunked(const float *obs, int64_t obs_stri
                                               float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
                                               uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
   using namespace mm::chunked;
-  namespace gi = mm::gi_train;
-  if (!weights || !grads || !loss) return MM_ERR_INVALID_ARG;
-  const MMGiParams W = *weights, G = *grads;  // (passed to the kernels by value)
-  float *const wp[12] = {W.W11, W.b11, W.W12, W.b12, W.W13, W.b13, W.W2, W.b2, W.Wa, W.ba, W.Wc, W.bc};
-  float *const gp[12] = {G.W11, G.b11, G.W12, G.b12, G.W13, G.b13, G.W2, G.b2, G.Wa, G.ba, G.Wc, G.bc};
-  for (int k = 0; k < 12; k++)
-    if (!wp[k] || !gp[k]) return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
+  if (!weights || !complete(grads) || !loss) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *count = (int *)sc;  // prep's count is the one kernel A scales by
+  mm::gi_train::PassArgs p = {};  // the whole batch
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.w = *weights; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_GI_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;
+  p.logp_out = logp_taken; p.value_out = value; p.ratio_out = ratio;
+  ChunkLayout L;
+  if (!gi_args_ok(p, n_s, hidden, critic_loss, chunk, scratch, scratch_bytes, L)) return MM_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const size_t gsz[12] = {160, 32, 640, 64, 640, 64, (size_t)kHidden * kCatGi, kHidden, (size_t)n_a * kHidden, (size_t)n_a, kHidden, 1};
   if (n == 0) {
-    for (int k = 0; k < 12; k++)
-      if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    if (hipMemsetAsync(loss, 0, 3 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+    if (!mm::gi_train::zero_grads(s, *grads, n_a) || hipMemsetAsync(loss, 0, 3 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
     return MM_OK;
   }
-  if (!obs || !actions || !returns || !old_logp || obs_stride < n_s) return MM_ERR_INVALID_ARG;
-  const ChunkLayout L = chunk_layout(gi::layout_of(chunk), n, 2, PartGi::kSize, 1);
-  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
-  const long long last = n % chunk ? n % chunk : (long long)chunk;  // the two pass sizes there are: chunk and the last pass's
-  if (gi::layout_of(n < chunk ? n : chunk).slices > L.blocks || gi::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
-  float *sc = (float *)scratch;
-  int *count = (int *)sc;
-  double *acc = (double *)(sc + L.acc), *lossp = (double *)(sc + L.lossp);
+  double *acc = (double *)(sc + L.acc);
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
   if (hipMemsetAsync(acc, 0, PartGi::kSize * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
-  gi::launch_prep(s, W.W2, (float4 *)(sc + L.rows.frag), valid, (long long)n, count);
-  gi::PassArgs p = {};
-  p.obs_stride = obs_stride; p.act_stride = act_stride; p.ret_stride = ret_stride; p.w = W; p.n_a = n_a; p.clip_param = clip_param;
-  p.huber = critic_loss == MM_GI_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;
-  p.frag = (const float4 *)(sc + L.rows.frag); p.rows = rows_of(sc, L.rows);
-  for (long long c0 = 0; c0 < n; c0 += chunk) {
-    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
-    const Layout P = gi::layout_of(np);  // the pass's tiles and slices
-    p.n = np;
-    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = returns + c0 * ret_stride;
-    p.old_logp = old_logp + c0; p.valid = shifted(valid, c0);
-    p.lossp = lossp + 2 * (c0 / 32);
-    p.logp_out = shifted(logp_taken, c0); p.value_out = shifted(value, c0); p.ratio_out = shifted(ratio, c0);
-    gi::launch_sample(s, p);
-    gi::launch_wgrad(s, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-    accumulate(s, sc + L.part, P.slices, PartGi::kSize, acc);
-  }
+  gi_passes(s, p, chunk, L, sc, acc);
   const int nelem = gi_elems(n_a);
   hipLaunchKernelGGL(policy_gi_train_chunked_finish_kernel, dim3((nelem + 255) / 256 + 1), dim3(256), 0, s, (const double *)acc,
-                     (int)n_a, G, (const double *)lossp, L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
+                     (int)n_a, *grads, (const double *)(sc + L.lossp), L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
 
@@ -164,8 +218,6 @@ extern "C" int32_t mm_policy_train_chunked_scratch_bytes(int64_t n, int64_t chun
   return MM_OK;
 }
 
-static bool pt_complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
-
 extern "C" int32_t mm_policy_train_chunked(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
                                            int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
                                            const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
@@ -174,81 +226,37 @@ extern "C" int32_t mm_policy_train_chunked(const float *obs, int64_t obs_stride,
                                            float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
                                            uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
   using namespace mm::chunked;
-  namespace pt = mm::pt;
-  if ((!actor && !critic) || !loss) return MM_ERR_INVALID_ARG;
-  if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
-  if ((actor && (!pt_complete(actor) || !pt_complete(actor_grads))) || (critic && (!pt_complete(critic) || !pt_complete(critic_grads))))
-    return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
-  if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
+  // everything that can refuse the call comes before the first enqueue
+  if (!loss || (actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
+  if ((actor_grads && !complete(actor_grads)) || (critic_grads && !complete(critic_grads))) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *count = (int *)sc;  // prep's count is the one kernel A scales by
+  mm::pt::PassArgs p = {};  // the whole batch
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.n_s = n_s; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.advantages = advantages; p.count = count;
+  const PtNet net[2] = {{actor, logp_taken, ratio}, {critic, value, nullptr}};
+  ChunkLayout L;
+  if (!pt_args_ok(p, net, hidden, critic_loss, chunk, scratch, scratch_bytes, L)) return MM_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int k2c = kHidden + n_a;
-  // everything that can refuse the call comes before the first enqueue
-  ChunkLayout L = {};
-  if (n > 0) {
-    if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
-    if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;
-    // the two networks' loss partials live side by side: both are folded at the end, after the passes alternated over the rows
-    L = chunk_layout(pt::layout_of(chunk), n, 2, PartPt::kSize, 2);
-    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
-    const long long last = n % chunk ? n % chunk : (long long)chunk;
-    if (pt::layout_of(n < chunk ? n : chunk).slices > L.blocks || pt::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
-  }
   if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
-    for (int net = 0; net < 2; net++) {
-      const MMMlpParams *g = net ? critic_grads : actor_grads;
-      if (!g) continue;
-      const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
-      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
-      const size_t gsz[6] = {(size_t)kHidden * n_s, kHidden, (size_t)kHidden * k2, kHidden, (size_t)n_out * kHidden, (size_t)n_out};
-      for (int k = 0; k < 6; k++)
-        if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    }
+    if (actor && !zero_mlp_grads(s, actor_grads, kHidden, n_s, kHidden, n_a)) return MM_ERR_DEVICE;
+    if (critic && !zero_mlp_grads(s, critic_grads, kHidden, n_s, k2c, 1)) return MM_ERR_DEVICE;
     return MM_OK;
   }
-  float *sc = (float *)scratch;
-  int *count = (int *)sc;
-  double *acc_a = (double *)(sc + L.acc), *acc_c = acc_a + PartPt::kSize;
-  double *lossp_a = (double *)(sc + L.lossp), *lossp_c = lossp_a + L.ntiles;
+  double *acc = (double *)(sc + L.acc), *lossp = (double *)(sc + L.lossp);  // the actor's, then the critic's
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  if (hipMemsetAsync(acc_a, 0, 2 * PartPt::kSize * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
-  pt::launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.rows.frag), valid, (long long)n,
-                  count);
-  pt::PassArgs p = {};
-  p.obs_stride = obs_stride; p.n_s = n_s; p.act_stride = act_stride; p.ret_stride = ret_stride; p.n_a = n_a;
-  p.clip_param = clip_param; p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;
-  p.rows = rows_of(sc, L.rows);
-  for (long long c0 = 0; c0 < n; c0 += chunk) {
-    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
-    const Layout P = pt::layout_of(np);  // the pass's tiles and slices
-    p.n = np;
-    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = shifted(returns, c0 * ret_stride);
-    p.old_logp = shifted(old_logp, c0); p.valid = shifted(valid, c0); p.advantages = shifted(advantages, c0);
-    if (actor) {
-      p.w = *actor; p.frag = (const float4 *)(sc + L.rows.frag); p.lossp = lossp_a + c0 / 32;
-      p.out0 = shifted(logp_taken, c0); p.out1 = shifted(ratio, c0);
-      pt::launch_sample(s, false, p);
-      pt::launch_wgrad(s, false, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_a);
-    }
-    if (critic) {
-      p.w = *critic; p.frag = (const float4 *)(sc + L.rows.frag + pt::critic_frag_offset()); p.lossp = lossp_c + c0 / 32;
-      p.out0 = shifted(value, c0); p.out1 = nullptr;
-      pt::launch_sample(s, true, p);
-      pt::launch_wgrad(s, true, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_c);
-    }
-  }
+  if (hipMemsetAsync(acc, 0, 2 * PartPt::kSize * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
+  pt_passes(s, p, net, chunk, L, sc, acc);
   if (actor)
     hipLaunchKernelGGL(policy_train_chunked_finish_kernel, dim3((pt_elems(n_s, kHidden, n_a) + 255) / 256 + 1), dim3(256), 0, s,
-                       (const double *)acc_a, (int)n_s, kHidden, (int)n_a, *actor_grads, (const double *)lossp_a, L.ntiles,
+                       (const double *)acc, (int)n_s, kHidden, (int)n_a, *actor_grads, (const double *)lossp, L.ntiles,
                        (const int *)count, adv_sums ? 2 : 1, loss);
   if (critic)
     hipLaunchKernelGGL(policy_train_chunked_finish_kernel, dim3((pt_elems(n_s, k2c, 1) + 255) / 256 + 1), dim3(256), 0, s,
-                       (const double *)acc_c, (int)n_s, k2c, 1, *critic_grads, (const double *)lossp_c, L.ntiles, (const int *)count, 0,
-                       loss + 1);
+                       (const double *)(acc + PartPt::kSize), (int)n_s, k2c, 1, *critic_grads, (const double *)(lossp + L.ntiles),
+                       L.ntiles, (const int *)count, 0, loss + 1);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }

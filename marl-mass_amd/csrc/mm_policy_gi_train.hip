@@ -19,9 +19,7 @@
 //             wave 4 the first layer.  Each workgroup contracts one contiguous slice of samples and writes one partial block.
 //   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
-#include "mm_policy_mfma.h"
-#include "../../include/mm_policy_gi_train.h"
-#include "mm_policy_chunked.h"
+#include "mm_policy_chunked.h"  // PassArgs and the launch helpers' declarations; mm_policy_mfma.h and the public header
 
 namespace mm {
 namespace gi_train {
@@ -314,67 +312,9 @@ __global__ __launch_bounds__(256) void policy_gi_train_fold_kernel(const float *
   gr.bc[0] = fold(part, slices, Part::kbh + 8);
 }
 
-}  // namespace gi_train
-}  // namespace mm
-
-extern "C" int32_t mm_policy_gi_train_scratch_bytes(int64_t n, uint64_t *bytes) {
-  if (n < 0 || !bytes) return MM_ERR_INVALID_ARG;
-  *bytes = (uint64_t)mm::gi_train::layout(n).total * 4u;
-  return MM_OK;
-}
-
-extern "C" int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
-                                      int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
-                                      const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a,
-                                      float clip_param, int32_t critic_loss, const float *adv_sums, const MMGiParams *grads,
-                                      float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
-                                      uint64_t scratch_bytes, MMStream stream) {
-  using namespace mm::gi_train;
-  if (!weights || !grads || !loss) return MM_ERR_INVALID_ARG;
-  const MMGiParams W = *weights, G = *grads;  // (passed to the kernels by value)
-  float *const wp[12] = {W.W11, W.b11, W.W12, W.b12, W.W13, W.b13, W.W2, W.b2, W.Wa, W.ba, W.Wc, W.bc};
-  float *const gp[12] = {G.W11, G.b11, G.W12, G.b12, G.W13, G.b13, G.W2, G.b2, G.Wa, G.ba, G.Wc, G.bc};
-  for (int k = 0; k < 12; k++)
-    if (!wp[k] || !gp[k]) return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t gsz[12] = {160, 32, 640, 64, 640, 64, (size_t)kHidden * kCat, kHidden, (size_t)n_a * kHidden, (size_t)n_a, kHidden, 1};
-  if (n == 0) {
-    for (int k = 0; k < 12; k++)
-      if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    if (hipMemsetAsync(loss, 0, 3 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    return MM_OK;
-  }
-  if (!obs || !actions || !returns || !old_logp || obs_stride < n_s) return MM_ERR_INVALID_ARG;
-  const Layout L = layout(n);
-  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
-  float *sc = (float *)scratch;
-  int *count = (int *)sc;
-  if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  hipLaunchKernelGGL(gi_train_prep_kernel, dim3(5 * 4 * 4 * 64 / 256), dim3(256), 0, s, W.W2, (float4 *)(sc + L.frag), valid,
-                     (long long)n, count);
-  const unsigned gridA = persistent_grid(L.ntiles, kThreadsA / 64);
-  hipLaunchKernelGGL(policy_gi_train_sample_kernel, dim3(gridA), dim3(kThreadsA), 0, s, obs, (long long)obs_stride, (long long)n,
-                     actions, (long long)act_stride, returns, (long long)ret_stride, old_logp, valid, W, (int)n_a, clip_param,
-                     (int)(critic_loss == MM_GI_CRITIC_HUBER), adv_sums, (const int *)count, (const float4 *)(sc + L.frag),
-                     sc + L.h1, sc + L.dz1, sc + L.h2, sc + L.dz2, sc + L.dh, sc + L.xs, (double *)(sc + L.lossp), logp_taken, value,
-                     ratio);
-  hipLaunchKernelGGL(policy_gi_train_wgrad_kernel, dim3(L.slices), dim3(kThreadsB), 0, s, sc + L.h1, sc + L.dz1, sc + L.h2,
-                     sc + L.dz2, sc + L.dh, sc + L.xs, L.n_pad, L.slice_rows, sc + L.part);
-  const int nelem = kNFixed + n_a * kHidden + n_a + kHidden + 1;
-  hipLaunchKernelGGL(policy_gi_train_fold_kernel, dim3((nelem + 255) / 256 + 1), dim3(256), 0, s, sc + L.part, L.slices, (int)n_a,
-                     G, (const double *)(sc + L.lossp), L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
-  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
-}
-
-// ---- host-side launch helpers of the chunked entry (mm_policy_chunked.hip, declared in mm_policy_chunked.h): the same launches
-// as above on the samples and rows the caller points at
-namespace mm {
-namespace gi_train {
-
-mfma::Layout layout_of(long long n) { return layout(n); }
+// ---- host-side launch helpers (declared in mm_policy_chunked.h): the one spelling of each launch, on the samples and rows the
+// caller points at -- the whole batch for the entry below, one pass for the pass loops of mm_policy_chunked.hip
+Layout layout_of(long long n) { return layout(n); }
 
 void launch_prep(hipStream_t s, const float *W2, float4 *frag, const uint8_t *valid, long long n, int *count) {
   hipLaunchKernelGGL(gi_train_prep_kernel, dim3(5 * 4 * 4 * 64 / 256), dim3(256), 0, s, W2, frag, valid, n, count);
@@ -393,5 +333,55 @@ void launch_wgrad(hipStream_t s, const SampleRows &r, long long n_pad, long long
                      slice_rows, part);
 }
 
+bool zero_grads(hipStream_t s, const MMGiParams &g, int n_a) {
+  float *const gp[12] = {g.W11, g.b11, g.W12, g.b12, g.W13, g.b13, g.W2, g.b2, g.Wa, g.ba, g.Wc, g.bc};
+  const size_t gsz[12] = {160, 32, 640, 64, 640, 64, (size_t)kHidden * kCat, kHidden, (size_t)n_a * kHidden, (size_t)n_a, kHidden, 1};
+  for (int k = 0; k < 12; k++)
+    if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return false;
+  return true;
+}
+
 }  // namespace gi_train
 }  // namespace mm
+
+extern "C" int32_t mm_policy_gi_train_scratch_bytes(int64_t n, uint64_t *bytes) {
+  if (n < 0 || !bytes) return MM_ERR_INVALID_ARG;
+  *bytes = (uint64_t)mm::gi_train::layout(n).total * 4u;
+  return MM_OK;
+}
+
+extern "C" int32_t mm_policy_gi_train(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                      int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                      const uint8_t *valid, const MMGiParams *weights, int32_t hidden, int32_t n_a,
+                                      float clip_param, int32_t critic_loss, const float *adv_sums, const MMGiParams *grads,
+                                      float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
+                                      uint64_t scratch_bytes, MMStream stream) {
+  using namespace mm::gi_train;
+  if (!complete(weights) || !complete(grads) || !loss || !shape_ok(n, n_s, hidden, n_a, kHidden)) return MM_ERR_INVALID_ARG;
+  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
+  if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    if (!zero_grads(s, *grads, n_a) || hipMemsetAsync(loss, 0, 3 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+    return MM_OK;
+  }
+  if (!obs || !actions || !returns || !old_logp || obs_stride < n_s) return MM_ERR_INVALID_ARG;
+  const Layout L = layout(n);
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *count = (int *)sc;
+  if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
+  PassArgs p = {};  // the whole batch in one pass
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.w = *weights; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_GI_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;
+  p.frag = (const float4 *)(sc + L.frag); p.rows = mm::chunked::rows_of(sc, L); p.lossp = (double *)(sc + L.lossp);
+  p.logp_out = logp_taken; p.value_out = value; p.ratio_out = ratio;
+  launch_prep(s, p.w.W2, (float4 *)(sc + L.frag), valid, n, count);
+  launch_sample(s, p);
+  launch_wgrad(s, p.rows, L.n_pad, L.slice_rows, L.slices, sc + L.part);
+  const int nelem = kNFixed + n_a * kHidden + n_a + kHidden + 1;
+  hipLaunchKernelGGL(policy_gi_train_fold_kernel, dim3((nelem + 255) / 256 + 1), dim3(256), 0, s, sc + L.part, L.slices, (int)n_a,
+                     *grads, (const double *)p.lossp, L.ntiles, (const int *)count, (int)(adv_sums != nullptr), loss);
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}

@@ -1,5 +1,6 @@
-// mm_policy_mfma.h -- what the three policy kernel files share (mm_policy_gi.hip, mm_policy_gi_train.hip, mm_policy_train.hip).
-// Device-only, every helper force-inlined and parametrised by compile-time sizes alone: the kernels that use them keep their
+// mm_policy_mfma.h -- what the policy kernel files share (mm_policy_gi.hip, mm_policy_gi_train.hip, mm_policy_train.hip, the
+// hidden-512 files), and at its end the small host helpers of the training entries (argument checks, the n == 0 path).
+// The device helpers are force-inlined and parametrised by compile-time sizes alone: the kernels that use them keep their
 // names, their shared memory and their register budget (255 / 256 VGPRs, no spills), and no floating-point operation moves.
 //
 // The layout.  Every layer is computed transposed, H_out^T [feature x sample] = W [out x in] . H_in^T, one wave per 32 samples,
@@ -26,6 +27,8 @@
 #ifndef MM_POLICY_MFMA_H
 #define MM_POLICY_MFMA_H
 #include "mm_device.h"
+#include "../../include/mm_policy_gi_train.h"  // MMGiParams
+#include "../../include/mm_policy_train.h"     // MMMlpParams
 
 namespace mm {
 namespace mfma {
@@ -395,6 +398,33 @@ static Layout scratch_layout(long long n, long long frag_floats, int pitch1, int
   L.slice_rows = tiles_per * 32;
   L.total = L.part + (long long)L.slices * partial;
   return L;
+}
+
+// ---- what the training entries check alike, and their n == 0 path
+static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
+
+static bool complete(const MMGiParams *p) {
+  return p && p->W11 && p->b11 && p->W12 && p->b12 && p->W13 && p->b13 && p->W2 && p->b2 && p->Wa && p->ba && p->Wc && p->bc;
+}
+
+// `width`: the hidden size the entry is built for
+static bool shape_ok(int64_t n, int32_t n_s, int32_t hidden, int32_t n_a, int32_t width) {
+  return n >= 0 && n <= 0x7FFFFFFF && n_s >= 25 && n_s <= 32 && hidden == width && n_a >= 1 && n_a <= 8;
+}
+
+// a pass size: whole 32-sample tiles and kernel B's minimum of 2 tiles per slice
+static bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chunk <= 0x7FFFFFC0ll; }
+
+template <typename T>
+static T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
+
+// zeroes the six gradient tensors of a network with fc2 rows of k2 floats and n_out outputs; false: an enqueue failed
+static bool zero_mlp_grads(hipStream_t s, const MMMlpParams *g, int hidden, int n_s, int k2, int n_out) {
+  float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
+  const size_t gsz[6] = {(size_t)hidden * n_s, (size_t)hidden, (size_t)hidden * k2, (size_t)hidden, (size_t)n_out * hidden, (size_t)n_out};
+  for (int k = 0; k < 6; k++)
+    if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return false;
+  return true;
 }
 
 }  // namespace mfma

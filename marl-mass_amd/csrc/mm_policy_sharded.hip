@@ -4,9 +4,9 @@
 //
 // The chunked entries (mm_policy_chunked.hip) already work in stages: kernels A and B in passes, every pass's partial blocks added
 // into an fp64 accumulator block per network, one finish kernel that rounds the block to float32 in torch layout.  Here the
-// accumulator is the caller's: `partial` runs the same prep and the same passes on the rank's own samples -- the SAME kernels
-// through the launch helpers of mm_policy_chunked.h, kernel A scaled by the count B of the WHOLE batch, which the caller gives --
-// and leaves a shard block
+// accumulator is the caller's: `partial` runs the same prep and the same passes on the rank's own samples -- the chunked entries'
+// own pass loops and argument checks (mm_policy_chunked.h), kernel A scaled by the count B of the WHOLE batch, which the caller
+// gives -- and leaves a shard block
 //
 //   [0] B   [1] the rank's own count of valid samples   [2] the configuration word   [3] 0
 //   [4] [5] the un-normalised fp64 loss sums (shared network: actor, critic heads; separate networks: actor, critic)
@@ -189,74 +189,41 @@ extern "C" int32_t mm_policy_gi_train_partial(const float *obs, int64_t obs_stri
                                               double *shard, float *logp_taken, float *value, float *ratio, void *scratch,
                                               uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
   using namespace mm::sharded;
-  namespace gi = mm::gi_train;
-  if (!weights || !aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
-  const MMGiParams W = *weights;  // (passed to the kernels by value)
-  float *const wp[12] = {W.W11, W.b11, W.W12, W.b12, W.W13, W.b13, W.W2, W.b2, W.Wa, W.ba, W.Wc, W.bc};
-  for (int k = 0; k < 12; k++)
-    if (!wp[k]) return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_GI_CRITIC_MSE && critic_loss != MM_GI_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool huber = critic_loss == MM_GI_CRITIC_HUBER;
-  const double config = config_word(n_s, n_a, adv_sums != nullptr, huber, kNetActor | kNetCritic);
   // everything that can refuse the call comes before the first enqueue
-  ChunkLayout L = {};
-  if (n > 0) {
-    if (!obs || !actions || !returns || !old_logp || obs_stride < n_s) return MM_ERR_INVALID_ARG;
-    L = chunk_layout(gi::layout_of(chunk), n, 2, PartGi::kSize, 1);
-    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
-    const long long last = n % chunk ? n % chunk : (long long)chunk;  // the two pass sizes there are: chunk and the last pass's
-    if (gi::layout_of(n < chunk ? n : chunk).slices > L.blocks || gi::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
-  }
+  if (!weights || !aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *local = (int *)sc;  // prep's count: the rank's own
+  mm::gi_train::PassArgs p = {};  // the rank's samples
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.w = *weights; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_GI_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;  // (kernel A scales by the WHOLE batch's B)
+  p.logp_out = logp_taken; p.value_out = value; p.ratio_out = ratio;
+  ChunkLayout L;
+  if (!gi_args_ok(p, n_s, hidden, critic_loss, chunk, scratch, scratch_bytes, L)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const double config = config_word(n_s, n_a, adv_sums != nullptr, p.huber, kNetActor | kNetCritic);
   if (hipMemsetAsync(shard, 0, kGiDoubles * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {  // an empty shard: a valid all-zero block with local count 0
     hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)nullptr, (const double *)nullptr, 0ll, 1,
                        (const int *)count, (const int *)nullptr, config, shard);
     return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
   }
-  float *sc = (float *)scratch;
-  int *local = (int *)sc;
-  double *acc = shard + kAcc, *lossp = (double *)(sc + L.lossp);
   if (hipMemsetAsync(local, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  gi::launch_prep(s, W.W2, (float4 *)(sc + L.rows.frag), valid, (long long)n, local);
-  gi::PassArgs p = {};
-  p.obs_stride = obs_stride; p.act_stride = act_stride; p.ret_stride = ret_stride; p.w = W; p.n_a = n_a; p.clip_param = clip_param;
-  p.huber = huber; p.adv_sums = adv_sums; p.count = count;  // (kernel A scales by the WHOLE batch's B)
-  p.frag = (const float4 *)(sc + L.rows.frag); p.rows = rows_of(sc, L.rows);
-  for (long long c0 = 0; c0 < n; c0 += chunk) {
-    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
-    const Layout P = gi::layout_of(np);  // the pass's tiles and slices
-    p.n = np;
-    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = returns + c0 * ret_stride;
-    p.old_logp = old_logp + c0; p.valid = shifted(valid, c0);
-    p.lossp = lossp + 2 * (c0 / 32);
-    p.logp_out = shifted(logp_taken, c0); p.value_out = shifted(value, c0); p.ratio_out = shifted(ratio, c0);
-    gi::launch_sample(s, p);
-    gi::launch_wgrad(s, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-    accumulate(s, sc + L.part, P.slices, PartGi::kSize, acc);
-  }
-  hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)lossp, (const double *)nullptr, L.ntiles, 1,
-                     (const int *)count, (const int *)local, config, shard);
+  gi_passes(s, p, chunk, L, sc, shard + kAcc);
+  hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)(sc + L.lossp), (const double *)nullptr,
+                     L.ntiles, 1, (const int *)count, (const int *)local, config, shard);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
 
 extern "C" int32_t mm_policy_gi_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
                                              const MMGiParams *grads, float *loss, MMStream stream) {
   using namespace mm::sharded;
-  if (!grads || !loss || !aligned(blocks, 8)) return MM_ERR_INVALID_ARG;
-  const MMGiParams G = *grads;
-  float *const gp[12] = {G.W11, G.b11, G.W12, G.b12, G.W13, G.b13, G.W2, G.b2, G.Wa, G.ba, G.Wc, G.bc};
-  for (int k = 0; k < 12; k++)
-    if (!gp[k]) return MM_ERR_INVALID_ARG;
+  if (!complete(grads) || !loss || !aligned(blocks, 8)) return MM_ERR_INVALID_ARG;
   if (n_blocks < 1 || n_blocks > 64 || block_stride < kGiDoubles || n_s < 25 || n_s > 32 || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
   FinishArgs a = {};
-  a.shared_net = 1; a.n_s = n_s; a.n_a = n_a; a.want = kNetActor | kNetCritic; a.nelem_a = gi_elems(n_a); a.gi = G;
+  a.shared_net = 1; a.n_s = n_s; a.n_a = n_a; a.want = kNetActor | kNetCritic; a.nelem_a = gi_elems(n_a); a.gi = *grads;
   return launch_finish((hipStream_t)stream, a, blocks, n_blocks, block_stride, loss);
 }
-
-static bool pt_complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
 
 extern "C" int32_t mm_policy_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
                                            int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
@@ -265,67 +232,30 @@ extern "C" int32_t mm_policy_train_partial(const float *obs, int64_t obs_stride,
                                            const float *advantages, const int32_t *count, double *shard, float *logp_taken, float *value,
                                            float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
   using namespace mm::sharded;
-  namespace pt = mm::pt;
-  if ((!actor && !critic) || !aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
-  if ((actor && !pt_complete(actor)) || (critic && !pt_complete(critic))) return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kHidden || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
-  if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int k2c = kHidden + n_a;
-  const bool huber = critic_loss == MM_PT_CRITIC_HUBER;
-  const double config = config_word(n_s, n_a, actor && adv_sums, huber, (actor ? kNetActor : 0) | (critic ? kNetCritic : 0));
   // everything that can refuse the call comes before the first enqueue
-  ChunkLayout L = {};
-  if (n > 0) {
-    if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
-    if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;
-    L = chunk_layout(pt::layout_of(chunk), n, 2, PartPt::kSize, 2);
-    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
-    const long long last = n % chunk ? n % chunk : (long long)chunk;
-    if (pt::layout_of(n < chunk ? n : chunk).slices > L.blocks || pt::layout_of(last).slices > L.blocks) return MM_ERR_INVALID_ARG;
-  }
+  if (!aligned(count, 4) || !aligned(shard, 16)) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *local = (int *)sc;  // prep's count: the rank's own
+  mm::pt::PassArgs p = {};  // the rank's samples
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.n_s = n_s; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.advantages = advantages; p.count = count;  // (the WHOLE batch's B)
+  const PtNet net[2] = {{actor, logp_taken, ratio}, {critic, value, nullptr}};
+  ChunkLayout L;
+  if (!pt_args_ok(p, net, hidden, critic_loss, chunk, scratch, scratch_bytes, L)) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const double config = config_word(n_s, n_a, actor && adv_sums, p.huber, (actor ? kNetActor : 0) | (critic ? kNetCritic : 0));
   if (hipMemsetAsync(shard, 0, kPtDoubles * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
     hipLaunchKernelGGL(train_shard_header_kernel, dim3(1), dim3(256), 0, s, (const double *)nullptr, (const double *)nullptr, 0ll, 0,
                        (const int *)count, (const int *)nullptr, config, shard);
     return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
   }
-  float *sc = (float *)scratch;
-  int *local = (int *)sc;
-  double *acc_a = shard + kAcc, *acc_c = acc_a + PartPt::kSize;
-  double *lossp_a = (double *)(sc + L.lossp), *lossp_c = lossp_a + L.ntiles;
+  const double *lossp = (const double *)(sc + L.lossp);  // the actor's, then the critic's
   if (hipMemsetAsync(local, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  pt::launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.rows.frag), valid, (long long)n,
-                  local);
-  pt::PassArgs p = {};
-  p.obs_stride = obs_stride; p.n_s = n_s; p.act_stride = act_stride; p.ret_stride = ret_stride; p.n_a = n_a;
-  p.clip_param = clip_param; p.huber = huber; p.adv_sums = adv_sums; p.count = count;  // (the WHOLE batch's B)
-  p.rows = rows_of(sc, L.rows);
-  for (long long c0 = 0; c0 < n; c0 += chunk) {
-    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
-    const Layout P = pt::layout_of(np);  // the pass's tiles and slices
-    p.n = np;
-    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = shifted(returns, c0 * ret_stride);
-    p.old_logp = shifted(old_logp, c0); p.valid = shifted(valid, c0); p.advantages = shifted(advantages, c0);
-    if (actor) {
-      p.w = *actor; p.frag = (const float4 *)(sc + L.rows.frag); p.lossp = lossp_a + c0 / 32;
-      p.out0 = shifted(logp_taken, c0); p.out1 = shifted(ratio, c0);
-      pt::launch_sample(s, false, p);
-      pt::launch_wgrad(s, false, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_a);
-    }
-    if (critic) {
-      p.w = *critic; p.frag = (const float4 *)(sc + L.rows.frag + pt::critic_frag_offset()); p.lossp = lossp_c + c0 / 32;
-      p.out0 = shifted(value, c0); p.out1 = nullptr;
-      pt::launch_sample(s, true, p);
-      pt::launch_wgrad(s, true, p.rows, P.n_pad, P.slice_rows, P.slices, sc + L.part);
-      accumulate(s, sc + L.part, P.slices, PartPt::kSize, acc_c);
-    }
-  }
-  hipLaunchKernelGGL(train_shard_header_kernel, dim3(2), dim3(256), 0, s, (const double *)(actor ? lossp_a : nullptr),
-                     (const double *)(critic ? lossp_c : nullptr), L.ntiles, 0, (const int *)count, (const int *)local, config, shard);
+  pt_passes(s, p, net, chunk, L, sc, shard + kAcc);
+  hipLaunchKernelGGL(train_shard_header_kernel, dim3(2), dim3(256), 0, s, actor ? lossp : nullptr, critic ? lossp + L.ntiles : nullptr,
+                     L.ntiles, 0, (const int *)count, (const int *)local, config, shard);
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
 
@@ -334,7 +264,7 @@ extern "C" int32_t mm_policy_train_finish(const double *blocks, int32_t n_blocks
                                           MMStream stream) {
   using namespace mm::sharded;
   if ((!actor_grads && !critic_grads) || !loss || !aligned(blocks, 8)) return MM_ERR_INVALID_ARG;
-  if ((actor_grads && !pt_complete(actor_grads)) || (critic_grads && !pt_complete(critic_grads))) return MM_ERR_INVALID_ARG;
+  if ((actor_grads && !complete(actor_grads)) || (critic_grads && !complete(critic_grads))) return MM_ERR_INVALID_ARG;
   if (n_blocks < 1 || n_blocks > 64 || block_stride < kPtDoubles || n_s < 25 || n_s > 32 || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
   FinishArgs a = {};
   a.n_s = n_s; a.n_a = n_a;

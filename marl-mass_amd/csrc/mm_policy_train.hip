@@ -28,9 +28,7 @@
 //   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
 // The actor's three kernels run first, then the critic's over the same scratch (stream order).
-#include "mm_policy_mfma.h"
-#include "../../include/mm_policy_train.h"
-#include "mm_policy_chunked.h"
+#include "mm_policy_chunked.h"  // PassArgs and the launch helpers' declarations; mm_policy_mfma.h and the public header
 
 namespace mm {
 namespace pt {
@@ -341,13 +339,47 @@ __global__ __launch_bounds__(256) void policy_train_fold_kernel(const float *__r
   if (t < n_out) gr.b3[t] = fold(part, slices, Part::kbh + t);
 }
 
-static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
+static unsigned grid_a(long long ntiles) { return persistent_grid(ntiles, kThreadsA / 64); }
 
-static bool shape_ok(int64_t n, int32_t n_s, int32_t hidden, int32_t n_a) {
-  return n >= 0 && n <= 0x7FFFFFFF && n_s >= 25 && n_s <= 32 && hidden == kHidden && n_a >= 1 && n_a <= 8;
+// The code object holds the kernel templates' instances in the order of their first use, and the recorded one
+// (profiles/policy_train) has them in this order; the launch helpers below name them in another.
+[[maybe_unused]] static const void *const kKernelOrder[] = {
+    (const void *)policy_train_sample_kernel<false, false>, (const void *)policy_train_sample_kernel<true, false>,
+    (const void *)policy_train_sample_kernel<false, true>,  (const void *)policy_train_wgrad_kernel<false>,
+    (const void *)policy_train_sample_kernel<true, true>,   (const void *)policy_train_wgrad_kernel<true>};
+
+// ---- host-side launch helpers (declared in mm_policy_chunked.h): the one spelling of each training launch, on the samples and
+// rows the caller points at -- the whole batch for mm_policy_train below, one pass for the pass loops of mm_policy_chunked.hip
+Layout layout_of(long long n) { return layout(n); }
+
+long long critic_frag_offset() { return kFrag; }
+
+void launch_prep(hipStream_t s, const float *W2a, const float *W2c, int k2c, float4 *frag, const uint8_t *valid, long long n,
+                 int *count) {
+  hipLaunchKernelGGL(policy_train_prep_kernel, dim3(2 * 4096 / 256), dim3(256), 0, s, W2a, W2c, k2c, frag, valid, n, count);
 }
 
-static unsigned grid_a(long long ntiles) { return persistent_grid(ntiles, kThreadsA / 64); }
+void launch_sample(hipStream_t s, bool critic, const PassArgs &p) {
+  SampleArgs a = {};
+  a.obs = p.obs; a.obs_stride = p.obs_stride; a.n = p.n; a.n_s = p.n_s; a.actions = p.actions; a.act_stride = p.act_stride;
+  a.returns = p.returns; a.ret_stride = p.ret_stride; a.old_logp = p.old_logp; a.valid = p.valid; a.w = p.w; a.n_a = p.n_a;
+  a.clip_param = p.clip_param; a.huber = p.huber; a.adv_sums = p.adv_sums; a.advantages = p.advantages; a.count = p.count;
+  a.frag = p.frag;
+  a.s_h1 = p.rows.h1; a.s_dz1 = p.rows.dz1; a.s_h2 = p.rows.h2; a.s_dz2 = p.rows.dz2; a.s_dh = p.rows.dh; a.s_xs = p.rows.xs;
+  a.lossp = p.lossp; a.out0 = p.out0; a.out1 = p.out1;
+  const unsigned grid = grid_a((p.n + 31) / 32);
+  if (critic) hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+  else hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+}
+
+void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
+  if (critic)
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
+                       n_pad, slice_rows, part);
+  else
+    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
+                       n_pad, slice_rows, part);
+}
 
 }  // namespace pt
 }  // namespace mm
@@ -358,7 +390,7 @@ extern "C" int32_t mm_policy_eval(const float *obs, int64_t obs_stride, int64_t 
   using namespace mm::pt;
   if (!actor && !critic) return MM_ERR_INVALID_ARG;
   if ((actor && !complete(actor)) || (critic && !complete(critic))) return MM_ERR_INVALID_ARG;
-  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a, kHidden)) return MM_ERR_INVALID_ARG;
   if (n == 0) return MM_OK;  // (empty outputs may be NULL)
   if ((actor != nullptr) != (logp_taken != nullptr) || (critic != nullptr) != (value != nullptr)) return MM_ERR_INVALID_ARG;
   if (!obs || !actions || obs_stride < n_s) return MM_ERR_INVALID_ARG;
@@ -395,97 +427,44 @@ extern "C" int32_t mm_policy_train(const float *obs, int64_t obs_stride, int64_t
   if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
   if ((actor && (!complete(actor) || !complete(actor_grads))) || (critic && (!complete(critic) || !complete(critic_grads))))
     return MM_ERR_INVALID_ARG;
-  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a, kHidden)) return MM_ERR_INVALID_ARG;
   if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
   if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
   if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int k2c = kHidden + n_a;
+  if (n > 0) {  // (n == 0: the per-sample inputs, adv_sums, advantages and the scratch are not looked at and may be NULL)
+    if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
+    if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)layout(n).total * 4u) return MM_ERR_INVALID_ARG;
+  }
   if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
-    for (int net = 0; net < 2; net++) {
-      const MMMlpParams *g = net ? critic_grads : actor_grads;
-      if (!g) continue;
-      const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
-      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
-      const size_t gsz[6] = {(size_t)kHidden * n_s, kHidden, (size_t)kHidden * k2, kHidden, (size_t)n_out * kHidden, (size_t)n_out};
-      for (int k = 0; k < 6; k++)
-        if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    }
+    if (actor && !zero_mlp_grads(s, actor_grads, kHidden, n_s, kHidden, n_a)) return MM_ERR_DEVICE;
+    if (critic && !zero_mlp_grads(s, critic_grads, kHidden, n_s, k2c, 1)) return MM_ERR_DEVICE;
     return MM_OK;
   }
-  if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
-  if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;  // (n == 0: empty inputs may be NULL)
   const Layout L = layout(n);
-  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)L.total * 4u) return MM_ERR_INVALID_ARG;
   float *sc = (float *)scratch;
   int *count = (int *)sc;
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  hipLaunchKernelGGL(policy_train_prep_kernel, dim3(2 * 4096 / 256), dim3(256), 0, s, actor ? actor->W2 : nullptr,
-                     critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.frag), valid, (long long)n, count);
-  SampleArgs a = {};
-  a.obs = obs; a.obs_stride = obs_stride; a.n = n; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride;
-  a.returns = returns; a.ret_stride = ret_stride; a.old_logp = old_logp; a.valid = valid; a.n_a = n_a;
-  a.clip_param = clip_param; a.huber = critic_loss == MM_PT_CRITIC_HUBER; a.adv_sums = adv_sums; a.advantages = advantages;
-  a.count = count;
-  a.s_h1 = sc + L.h1; a.s_dz1 = sc + L.dz1; a.s_h2 = sc + L.h2; a.s_dz2 = sc + L.dz2; a.s_dh = sc + L.dh; a.s_xs = sc + L.xs;
-  a.lossp = (double *)(sc + L.lossp);
-  const unsigned grid = grid_a(L.ntiles);
-  if (actor) {
-    a.w = *actor; a.frag = (const float4 *)(sc + L.frag); a.out0 = logp_taken; a.out1 = ratio;
-    hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(L.slices), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2,
-                       a.s_dh, a.s_xs, L.n_pad, L.slice_rows, sc + L.part);
-    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, kHidden, n_a) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
-                       L.slices, (int)n_s, kHidden, (int)n_a, *actor_grads, (const double *)a.lossp, L.ntiles, (const int *)count,
-                       adv_sums ? 2 : 1, loss);
-  }
-  if (critic) {
-    a.w = *critic; a.frag = (const float4 *)(sc + L.frag + kFrag); a.out0 = value; a.out1 = nullptr;
-    hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(L.slices), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2,
-                       a.s_dh, a.s_xs, L.n_pad, L.slice_rows, sc + L.part);
-    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, k2c, 1) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
-                       L.slices, (int)n_s, k2c, 1, *critic_grads, (const double *)a.lossp, L.ntiles, (const int *)count, 0, loss + 1);
+  launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, (float4 *)(sc + L.frag), valid, n, count);
+  PassArgs p = {};  // the whole batch in one pass
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.n_s = n_s; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.advantages = advantages; p.count = count;
+  p.rows = mm::chunked::rows_of(sc, L); p.lossp = (double *)(sc + L.lossp);
+  for (int net = 0; net < 2; net++) {  // the actor's three kernels, then the critic's over the same scratch
+    const MMMlpParams *w = net ? critic : actor;
+    if (!w) continue;
+    const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
+    p.w = *w; p.frag = (const float4 *)(sc + L.frag + net * kFrag);
+    p.out0 = net ? value : logp_taken; p.out1 = net ? nullptr : ratio;
+    launch_sample(s, net != 0, p);
+    launch_wgrad(s, net != 0, p.rows, L.n_pad, L.slice_rows, L.slices, sc + L.part);
+    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, k2, n_out) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
+                       L.slices, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads, (const double *)p.lossp, L.ntiles,
+                       (const int *)count, net ? 0 : (adv_sums ? 2 : 1), loss + net);
   }
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
 }
-
-// ---- host-side launch helpers of the chunked entry (mm_policy_chunked.hip, declared in mm_policy_chunked.h): the same launches
-// as above on the samples and rows the caller points at
-namespace mm {
-namespace pt {
-
-mfma::Layout layout_of(long long n) { return layout(n); }
-
-long long critic_frag_offset() { return kFrag; }
-
-void launch_prep(hipStream_t s, const float *W2a, const float *W2c, int k2c, float4 *frag, const uint8_t *valid, long long n,
-                 int *count) {
-  hipLaunchKernelGGL(policy_train_prep_kernel, dim3(2 * 4096 / 256), dim3(256), 0, s, W2a, W2c, k2c, frag, valid, n, count);
-}
-
-void launch_sample(hipStream_t s, bool critic, const PassArgs &p) {
-  SampleArgs a = {};
-  a.obs = p.obs; a.obs_stride = p.obs_stride; a.n = p.n; a.n_s = p.n_s; a.actions = p.actions; a.act_stride = p.act_stride;
-  a.returns = p.returns; a.ret_stride = p.ret_stride; a.old_logp = p.old_logp; a.valid = p.valid; a.w = p.w; a.n_a = p.n_a;
-  a.clip_param = p.clip_param; a.huber = p.huber; a.adv_sums = p.adv_sums; a.advantages = p.advantages; a.count = p.count;
-  a.frag = p.frag;
-  a.s_h1 = p.rows.h1; a.s_dz1 = p.rows.dz1; a.s_h2 = p.rows.h2; a.s_dz2 = p.rows.dz2; a.s_dh = p.rows.dh; a.s_xs = p.rows.xs;
-  a.lossp = p.lossp; a.out0 = p.out0; a.out1 = p.out1;
-  const unsigned grid = grid_a((p.n + 31) / 32);
-  if (critic) hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
-  else hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
-}
-
-void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
-  if (critic)
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
-                       n_pad, slice_rows, part);
-  else
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
-                       n_pad, slice_rows, part);
-}
-
-}  // namespace pt
-}  // namespace mm

@@ -1,8 +1,9 @@
-// mm_policy_wide_chunked.h -- how mm_policy_wide_chunked.hip reaches prep, kernel A and kernel B of mm_policy_wide_train.hip, and
-// the layout the two files share: the scratch of n samples and the partial block of one slice.
-// Host-side launch helpers only, defined next to the kernels they launch (mm_policy_wide_train.hip): the chunked entry adds no
-// __global__ to that file and edits none, so its code object stays as recorded (profiles/policy_wide_train).  A helper only
-// enqueues on the stream; the caller reads hipGetLastError.
+// mm_policy_wide_chunked.h -- how the entries of mm_policy_wide_train.hip and mm_policy_wide_chunked.hip reach prep, kernel A and
+// kernel B of mm_policy_wide_train.hip, and the layout the two files share: the scratch of n samples and the partial block of one
+// slice.  Host-side launch helpers only, defined next to the kernels they launch (mm_policy_wide_train.hip) and the one spelling
+// of each launch, for the unchunked entry (the whole batch) as for the chunked one (a pass): the chunked entry adds no __global__
+// to that file and edits none, so its code object stays as recorded (profiles/policy_wide_train).  A helper only enqueues on the
+// stream; the caller reads hipGetLastError.
 #ifndef MM_POLICY_WIDE_CHUNKED_H
 #define MM_POLICY_WIDE_CHUNKED_H
 #include "mm_policy_mfma.h"

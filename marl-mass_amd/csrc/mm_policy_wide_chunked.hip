@@ -90,8 +90,6 @@ struct ChunkLayout {
   int blocks;
 };
 
-static bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chunk <= 0x7FFFFFC0ll; }
-
 static ChunkLayout chunk_layout(long long n, long long chunk) {
   ChunkLayout L;
   L.rows = wt::layout_of(chunk);
@@ -103,11 +101,6 @@ static ChunkLayout chunk_layout(long long n, long long chunk) {
   L.total = L.acc + 2ll * 2 * Part::kSize;  // double[2][Part::kSize]
   return L;  // (total * 4 == MM_POLICY_WIDE_TRAIN_CHUNKED_BYTES(n, chunk): tests/test_wide_chunked_host.py restates the sum)
 }
-
-template <typename T>
-static T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
-
-static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
 
 }  // namespace wide_chunked
 }  // namespace mm
@@ -132,7 +125,7 @@ extern "C" int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_st
   if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
   if ((actor && (!complete(actor) || !complete(actor_grads))) || (critic && (!complete(critic) || !complete(critic_grads))))
     return MM_ERR_INVALID_ARG;
-  if (n < 0 || n > 0x7FFFFFFF || n_s < 25 || n_s > 32 || hidden != kWide || n_a < 1 || n_a > 8) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a, kWide)) return MM_ERR_INVALID_ARG;
   if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
   if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
   if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
@@ -153,15 +146,8 @@ extern "C" int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_st
   }
   if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
-    for (int net = 0; net < 2; net++) {
-      const MMMlpParams *g = net ? critic_grads : actor_grads;
-      if (!g) continue;
-      const int k2 = net ? k2c : kWide, n_out = net ? 1 : n_a;
-      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
-      const size_t gsz[6] = {(size_t)kWide * n_s, kWide, (size_t)kWide * k2, kWide, (size_t)n_out * kWide, (size_t)n_out};
-      for (int k = 0; k < 6; k++)
-        if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    }
+    if (actor && !zero_mlp_grads(s, actor_grads, kWide, n_s, kWide, n_a)) return MM_ERR_DEVICE;
+    if (critic && !zero_mlp_grads(s, critic_grads, kWide, n_s, k2c, 1)) return MM_ERR_DEVICE;
     return MM_OK;
   }
   float *sc = (float *)scratch;

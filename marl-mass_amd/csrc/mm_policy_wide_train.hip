@@ -514,12 +514,6 @@ __global__ __launch_bounds__(256) void policy_wide_fold_kernel(const float *__re
   if (t < n_out) gr.b3[t] = fold_w(part, slices, Part::kbh + t);
 }
 
-static bool complete(const MMMlpParams *p) { return p && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3; }
-
-static bool shape_ok(int64_t n, int32_t n_s, int32_t hidden, int32_t n_a) {
-  return n >= 0 && n <= 0x7FFFFFFF && n_s >= 25 && n_s <= 32 && hidden == kWide && n_a >= 1 && n_a <= 8;
-}
-
 static unsigned grid_a(long long ntiles) { return persistent_grid(ntiles, kWavesA); }
 
 // fc2's rows can be read 16 bytes at a time
@@ -533,8 +527,8 @@ static void launch_sample(hipStream_t s, unsigned grid, const SampleArgs &a) {
     hipLaunchKernelGGL((policy_wide_sample_kernel<kCritic, kTrain, false>), dim3(grid), dim3(kThreadsA), 0, s, a);
 }
 
-// ---- host-side launch helpers of the chunked entry (mm_policy_wide_chunked.hip, declared in mm_policy_wide_chunked.h): the same
-// launches as mm_policy_wide_train's below on the samples and rows the caller points at
+// ---- host-side launch helpers (declared in mm_policy_wide_chunked.h): the one spelling of each training launch, on the samples
+// and rows the caller points at -- the whole batch for mm_policy_wide_train below, one pass for mm_policy_wide_chunked.hip
 WideLayout layout_of(long long n) { return layout(n); }
 
 void launch_prep(hipStream_t s, const float *W2a, const float *W2c, int k2c, float *w2t, float *w2p, const uint8_t *valid, long long n,
@@ -578,7 +572,7 @@ extern "C" int32_t mm_policy_wide_eval(const float *obs, int64_t obs_stride, int
   using namespace mm::wt;
   if (!actor && !critic) return MM_ERR_INVALID_ARG;
   if ((actor && !complete(actor)) || (critic && !complete(critic))) return MM_ERR_INVALID_ARG;
-  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a, kWide)) return MM_ERR_INVALID_ARG;
   if (n == 0) return MM_OK;  // (empty outputs may be NULL)
   if ((actor != nullptr) != (logp_taken != nullptr) || (critic != nullptr) != (value != nullptr)) return MM_ERR_INVALID_ARG;
   if (!obs || !actions || obs_stride < n_s) return MM_ERR_INVALID_ARG;
@@ -617,7 +611,7 @@ extern "C" int32_t mm_policy_wide_train(const float *obs, int64_t obs_stride, in
   if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
   if ((actor && (!complete(actor) || !complete(actor_grads))) || (critic && (!complete(critic) || !complete(critic_grads))))
     return MM_ERR_INVALID_ARG;
-  if (!shape_ok(n, n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (!shape_ok(n, n_s, hidden, n_a, kWide)) return MM_ERR_INVALID_ARG;
   if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
   if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
   if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
@@ -632,54 +626,30 @@ extern "C" int32_t mm_policy_wide_train(const float *obs, int64_t obs_stride, in
   const int k2c = kWide + n_a;
   if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
-    for (int net = 0; net < 2; net++) {
-      const MMMlpParams *g = net ? critic_grads : actor_grads;
-      if (!g) continue;
-      const int k2 = net ? k2c : kWide, n_out = net ? 1 : n_a;
-      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
-      const size_t gsz[6] = {(size_t)kWide * n_s, kWide, (size_t)kWide * k2, kWide, (size_t)n_out * kWide, (size_t)n_out};
-      for (int k = 0; k < 6; k++)
-        if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    }
+    if (actor && !zero_mlp_grads(s, actor_grads, kWide, n_s, kWide, n_a)) return MM_ERR_DEVICE;
+    if (critic && !zero_mlp_grads(s, critic_grads, kWide, n_s, k2c, 1)) return MM_ERR_DEVICE;
     return MM_OK;
   }
   float *sc = (float *)scratch;
   int *count = (int *)sc;
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
-  hipLaunchKernelGGL(policy_wide_prep_kernel, dim3(kPrepGrid), dim3(256), 0, s, actor ? actor->W2 : nullptr,
-                     critic ? critic->W2 : nullptr, k2c, sc + L.w2t, sc + L.w2p, valid, (long long)n, count);
-  SampleArgs a = {};
-  a.obs = obs; a.obs_stride = obs_stride; a.n = n; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride;
-  a.returns = returns; a.ret_stride = ret_stride; a.old_logp = old_logp; a.valid = valid; a.n_a = n_a;
-  a.clip_param = clip_param; a.huber = critic_loss == MM_PT_CRITIC_HUBER; a.adv_sums = adv_sums; a.advantages = advantages;
-  a.count = count;
-  a.s_xs = sc + L.xs; a.s_h1 = sc + L.h1; a.s_h2 = sc + L.h2; a.s_dz2 = sc + L.dz2; a.s_dz1 = sc + L.dz1; a.s_dh = sc + L.dh;
-  a.lossp = (double *)(sc + L.lossp);
-  const unsigned grid = grid_a(L.ntiles);
-  const dim3 grid_b(L.slices, kOutBlocks);
-  for (int net = 0; net < 2; net++) {
+  launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, sc + L.w2t, sc + L.w2p, valid, n, count);
+  PassArgs p = {};  // the whole batch in one pass
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.n_s = n_s; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.advantages = advantages; p.count = count;
+  const WideRows rows = {sc + L.xs, sc + L.h1, sc + L.h2, sc + L.dz2, sc + L.dz1, sc + L.dh};
+  p.rows = rows; p.lossp = (double *)(sc + L.lossp);
+  for (int net = 0; net < 2; net++) {  // the actor's three kernels, then the critic's over the same scratch
     const MMMlpParams *w = net ? critic : actor;
     if (!w) continue;
     const int k2 = net ? k2c : kWide, n_out = net ? 1 : n_a;
-    a.w = *w;
-    a.w2t = sc + L.w2t + net * kSquare;
-    // fc2's A operand: W2 in place where its rows take 16-byte loads, else the copy at pitch 512 that prep wrote
-    const bool in_place = vec_rows(w->W2, k2);
-    a.W2f = in_place ? w->W2 : sc + L.w2p + net * kSquare;
-    a.pitch2 = in_place ? k2 : kWide;
-    if (net) {
-      a.out0 = value; a.out1 = nullptr;
-      launch_sample<true, true>(s, grid, a);
-      hipLaunchKernelGGL((policy_wide_wgrad_kernel<true>), grid_b, dim3(kThreadsB), 0, s, a.s_xs, a.s_h1, a.s_h2, a.s_dz2, a.s_dz1,
-                         a.s_dh, L.n_pad, L.slice_rows, sc + L.part);
-    } else {
-      a.out0 = logp_taken; a.out1 = ratio;
-      launch_sample<false, true>(s, grid, a);
-      hipLaunchKernelGGL((policy_wide_wgrad_kernel<false>), grid_b, dim3(kThreadsB), 0, s, a.s_xs, a.s_h1, a.s_h2, a.s_dz2, a.s_dz1,
-                         a.s_dh, L.n_pad, L.slice_rows, sc + L.part);
-    }
+    p.w = *w; p.w2t = sc + L.w2t + net * kSquare; p.w2p = sc + L.w2p + net * kSquare;
+    p.out0 = net ? value : logp_taken; p.out1 = net ? nullptr : ratio;
+    launch_sample(s, net != 0, p);
+    launch_wgrad(s, net != 0, rows, L.n_pad, L.slice_rows, L.slices, sc + L.part);
     hipLaunchKernelGGL(policy_wide_fold_kernel, dim3((fold_elems(n_s, k2, n_out) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
-                       L.slices, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads, (const double *)a.lossp, L.ntiles,
+                       L.slices, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads, (const double *)p.lossp, L.ntiles,
                        (const int *)count, net ? 0 : (adv_sums ? 2 : 1), loss + net);
   }
   return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;

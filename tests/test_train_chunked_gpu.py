@@ -112,8 +112,11 @@ class Case(object):
         loss, diag = self.learner.loss_and_grad(self.obs, self.act, self.ret, self.old, **kw)
         return [loss.clone()] + self.grads() + list(diag)
 
-    def chunked_rc(self, form, chunk, scratch=None, scratch_bytes=None, sums=None):
-        """(status, [loss] + gradients + diagnostics) of the chunked entry; the gradients are read whatever the status."""
+    def chunked_rc(self, form, chunk, scratch=None, scratch_bytes=None, sums=None, hidden=128, clip=None, critic_loss=None,
+                   networks="both", both_adv=False, stray=None):
+        """(status, [loss] + gradients + diagnostics) of the chunked entry; the gradients are read whatever the status.
+        hidden .. stray: the arguments of SHARED_REFUSALS below (critic_loss: the raw code)."""
+        clip = self.clip if clip is None else clip
         L, clib, n, S = self.learner, self.learner.clib, self.n, self.obs.shape[1]
         sums = self.sums(form) if sums is None else sums
         loss = torch.full((3 if self.kind == "gi" else 2,), NAN, device="cuda")
@@ -125,21 +128,25 @@ class Case(object):
         obs, act, ret = self.obs, self.act, self.ret
         head = (obs.data_ptr(), obs.stride(0) if n else S, n, S, act.data_ptr(), act.stride(0) if n else 1, ret.data_ptr(),
                 ret.stride(0) if n else 1, self.old.data_ptr(), _opt(self.valid))
-        tail = (loss.data_ptr(), diag[0].data_ptr(), diag[1].data_ptr(), diag[2].data_ptr(), scratch.data_ptr(), nbytes, stream, chunk)
+        with_a, with_c = networks != "critic", networks != "actor"
+        given = [diag[i].data_ptr() if on or stray == i else None for i, on in enumerate((with_a, with_c, with_a))]
+        tail = (loss.data_ptr(), given[0], given[1], given[2], scratch.data_ptr(), nbytes, stream, chunk)
         if self.kind == "gi":
             W, G = abi.MMGiParams(), abi.MMGiParams()
             for name, p in zip(abi.GI_PARAMS, _params(L.policy)):
                 setattr(W, name, p.detach().data_ptr())
                 setattr(G, name, p.grad.data_ptr())
-            rc = clib.lib.mm_policy_gi_train_chunked(*head, C.byref(W), 128, self.n_a, self.clip, abi.GI_CRITIC_LOSS[self.critic_loss],
-                                                     _opt(sums), C.byref(G), *tail)
+            code = abi.GI_CRITIC_LOSS[self.critic_loss] if critic_loss is None else critic_loss
+            rc = clib.lib.mm_policy_gi_train_chunked(*head, C.byref(W), hidden, self.n_a, clip, code, _opt(sums), C.byref(G), *tail)
         else:
+            ref = lambda on, st: C.byref(st) if on else None  # noqa: E731
             W = [_mlp_struct(L.actor), _mlp_struct(L.critic)]
             G = [_mlp_struct(L.actor, True), _mlp_struct(L.critic, True)]
-            adv = None if sums is not None else self.adv
-            rc = clib.lib.mm_policy_train_chunked(*head, C.byref(W[0]), C.byref(W[1]), 128, self.n_a, self.clip,
-                                                  abi.PT_CRITIC_LOSS[self.critic_loss], _opt(sums), _opt(adv), C.byref(G[0]),
-                                                  C.byref(G[1]), *tail)
+            adv = self.adv if (sums is None or both_adv) else None
+            code = abi.PT_CRITIC_LOSS[self.critic_loss] if critic_loss is None else critic_loss
+            rc = clib.lib.mm_policy_train_chunked(*head, ref(with_a, W[0]), ref(with_c, W[1]), hidden, self.n_a, clip, code,
+                                                  _opt(sums) if with_a else None, _opt(adv) if with_a else None, ref(with_a, G[0]),
+                                                  ref(with_c, G[1]), *tail)
         return rc, [loss] + self.grads() + diag
 
     def chunked(self, form, chunk, **kw):
@@ -293,6 +300,18 @@ def test_graph_capturable(kind):
 
 
 # ---- refusals enqueue nothing
+def shared_refusals(separate, wrong_hidden):
+    """What the chunked and the partial entry of a family refuse through one shared check, as keyword arguments of the modules'
+    *_rc calls.  Only arguments that would be memory-safe if a broken check let them through: clip_param negative and NaN, an
+    unknown critic_loss, a hidden size the entry is not built for (the networks keep their own), and for the separate networks
+    adv_sums together with advantages and a diagnostic (0 logp_taken, 1 value, 2 ratio) without its network."""
+    table = [dict(clip=-0.125), dict(clip=NAN), dict(critic_loss=2), dict(critic_loss=-1)] + [dict(hidden=h) for h in wrong_hidden]
+    if separate:
+        table += [dict(both_adv=True), dict(networks="critic", stray=0), dict(networks="critic", stray=2),
+                  dict(networks="actor", stray=1)]
+    return table
+
+
 @pytest.mark.parametrize("kind", ENTRIES)
 def test_refusals_leave_the_gradients_alone(kind):
     case = _base(kind, 1000)
@@ -309,6 +328,13 @@ def test_refusals_leave_the_gradients_alone(kind):
         for g in out[1:13]:
             assert bool((g == -7.0).all()), kw
         assert bool(torch.isnan(out[0]).all())  # the losses were not written either
+    for kw in shared_refusals(kind == "pt", (64, 512)):
+        case.fill_grads(-7.0)
+        rc, out = case.chunked_rc("reference", 64, scratch=scratch, sums=sums, **kw)
+        torch.cuda.synchronize()
+        assert rc == abi.MM_ERR_INVALID_ARG, kw
+        assert all(bool((g == -7.0).all()) for g in out[1:13]), kw
+        assert all(bool(torch.isnan(t).all()) for t in out[:1] + out[13:]), kw  # neither losses nor diagnostics were written
     q = case.learner.clib
     for query in (q.policy_gi_train_chunked_scratch_bytes, q.policy_train_chunked_scratch_bytes):
         for chunk in (0, 32, 100, -64):

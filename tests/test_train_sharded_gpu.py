@@ -69,13 +69,15 @@ def _local(case):
 
 
 def partial_rc(case, form, chunk, count, sums=None, block=None, scratch=None, scratch_bytes=None, networks="both", count_ptr=None,
-               shard_ptr=None):
-    """(status, block, diagnostics) of the partial entry on a case's samples, straight through the binding."""
+               shard_ptr=None, hidden=128, clip=None, critic_loss=None, both_adv=False, stray=None):
+    """(status, block, diagnostics) of the partial entry on a case's samples, straight through the binding.
+    hidden .. stray: the arguments of ch.shared_refusals (critic_loss: the raw code)."""
+    clip = case.clip if clip is None else clip
     L, clib, n, S = case.learner, case.learner.clib, case.n, case.obs.shape[1]
     if block is None:
         block = torch.full((K[case.kind],), NAN, dtype=torch.float64, device="cuda")
     with_a, with_c = networks != "critic", networks != "actor"
-    diag = [torch.full((n,), NAN, device="cuda") if on else None for on in (with_a, with_c, with_a)]
+    diag = [torch.full((n,), NAN, device="cuda") if on or stray == i else None for i, on in enumerate((with_a, with_c, with_a))]
     if scratch is None:
         scratch = torch.empty(max(case.chunked_bytes(chunk), 16), dtype=torch.uint8, device="cuda")
     nbytes = scratch.numel() if scratch_bytes is None else scratch_bytes
@@ -89,15 +91,15 @@ def partial_rc(case, form, chunk, count, sums=None, block=None, scratch=None, sc
         W = abi.MMGiParams()
         for name, p in zip(abi.GI_PARAMS, _params(L.policy)):
             setattr(W, name, p.detach().data_ptr())
-        rc = clib.lib.mm_policy_gi_train_partial(*head, C.byref(W), 128, case.n_a, case.clip, abi.GI_CRITIC_LOSS[case.critic_loss],
-                                                 _opt(sums), *tail)
+        code = abi.GI_CRITIC_LOSS[case.critic_loss] if critic_loss is None else critic_loss
+        rc = clib.lib.mm_policy_gi_train_partial(*head, C.byref(W), hidden, case.n_a, clip, code, _opt(sums), *tail)
     else:
         W = [_mlp_struct(L.actor) if with_a else None, _mlp_struct(L.critic) if with_c else None]
         ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
-        adv = None if sums is not None else case.adv
-        rc = clib.lib.mm_policy_train_partial(*head, ref(W[0]), ref(W[1]), 128, case.n_a, case.clip,
-                                              abi.PT_CRITIC_LOSS[case.critic_loss], _opt(sums) if with_a else None,
-                                              _opt(adv) if with_a else None, *tail)
+        adv = case.adv if (sums is None or both_adv) else None
+        code = abi.PT_CRITIC_LOSS[case.critic_loss] if critic_loss is None else critic_loss
+        rc = clib.lib.mm_policy_train_partial(*head, ref(W[0]), ref(W[1]), hidden, case.n_a, clip, code,
+                                              _opt(sums) if with_a else None, _opt(adv) if with_a else None, *tail)
     return rc, block, diag
 
 
@@ -349,13 +351,14 @@ def test_refusals_leave_everything_alone(kind):
     torch.cuda.synchronize()
     refused = [dict(chunk=0), dict(chunk=32), dict(chunk=100), dict(chunk=64, scratch_bytes=need - 1), dict(chunk=64, count_ptr=0),
                dict(chunk=64, count_ptr=count.data_ptr() + 2), dict(chunk=64, shard_ptr=0), dict(chunk=64, shard_ptr=block.data_ptr() + 8)]
+    refused += [dict(chunk=64, **kw) for kw in ch.shared_refusals(kind == "pt", (64, 512))]  # the checks shared with the chunked entry
     for kw in refused:
         kw = dict(kw)
         rc, _, diag = partial_rc(case, form, kw.pop("chunk"), count, sums=sums, block=block, scratch=scratch, **kw)
         torch.cuda.synchronize()
         assert rc == abi.MM_ERR_INVALID_ARG, kw
         assert bool((block == -7.0).all()), kw
-        assert all(bool(torch.isnan(d).all()) for d in diag), kw
+        assert all(bool(torch.isnan(d).all()) for d in diag if d is not None), kw
     pad = torch.zeros(2, K[kind] + 2, dtype=torch.float64, device="cuda")
     for kw in (dict(n_blocks=0), dict(n_blocks=65), dict(n_blocks=2, stride=K[kind] - 1), dict(blocks_ptr=0), dict(n_blocks=-1)):
         case.fill_grads(-7.0)

@@ -19,6 +19,7 @@ from marl_mass_amd import _cabi as abi
 from marl_mass_amd.learner import PPOLearner, _mlp_struct
 from marl_mass_amd.rollout import ActorNetwork, CriticNetwork, DeviceRollout
 from policy_train_util import GRAD_NAMES, sums_of
+from test_train_chunked_gpu import shared_refusals
 
 pytestmark = pytest.mark.gpu
 
@@ -97,14 +98,17 @@ class Case(object):
         return [loss.clone()] + self.grads() + list(diag)
 
     def chunked_rc(self, form, chunk, scratch=None, scratch_ptr=None, scratch_bytes=None, sums=None, hidden=512, networks="both",
-                   loss=None, null_inputs=False):
+                   loss=None, null_inputs=False, clip=None, critic_loss=None, both_adv=False, stray=None):
         """(status, [loss] + gradients + diagnostics) of the chunked entry; the gradients are read whatever the status.
-        scratch: a uint8 tensor (default: one of the queried size); scratch_ptr / scratch_bytes override what is passed."""
+        scratch: a uint8 tensor (default: one of the queried size); scratch_ptr / scratch_bytes override what is passed.
+        clip .. stray: the arguments of test_train_chunked_gpu.shared_refusals (critic_loss: the raw code)."""
+        clip = self.clip if clip is None else clip
+        code = abi.PT_CRITIC_LOSS[self.critic_loss] if critic_loss is None else critic_loss
         L, clib, n, S = self.learner, self.learner.clib, self.n, self.obs.shape[1]
         sums = self.sums(form) if sums is None else sums
         loss = torch.full((2,), NAN, device="cuda") if loss is None else loss
         with_a, with_c = networks != "critic", networks != "actor"
-        diag = [torch.full((n,), NAN, device="cuda") if on else None for on in (with_a, with_c, with_a)]
+        diag = [torch.full((n,), NAN, device="cuda") if on or stray == i else None for i, on in enumerate((with_a, with_c, with_a))]
         if scratch is None and scratch_ptr is None:
             scratch = torch.empty(self.chunked_bytes(chunk), dtype=torch.uint8, device="cuda")
         ptr = scratch.data_ptr() if scratch_ptr is None else (scratch_ptr or None)
@@ -119,9 +123,9 @@ class Case(object):
         ref = lambda on, st: C.byref(st) if on else None  # noqa: E731
         W = [_mlp_struct(L.actor), _mlp_struct(L.critic)]
         G = [_mlp_struct(L.actor, True), _mlp_struct(L.critic, True)]
-        adv = None if (sums is not None or null_inputs) else self.adv
+        adv = None if ((sums is not None and not both_adv) or null_inputs) else self.adv
         rc = clib.lib.mm_policy_wide_train_chunked(
-            *head, ref(with_a, W[0]), ref(with_c, W[1]), hidden, L.n_a, self.clip, abi.PT_CRITIC_LOSS[self.critic_loss],
+            *head, ref(with_a, W[0]), ref(with_c, W[1]), hidden, L.n_a, clip, code,
             _opt(sums) if with_a else None, _opt(adv) if with_a else None, ref(with_a, G[0]), ref(with_c, G[1]), loss.data_ptr(),
             _opt(diag[0]), _opt(diag[1]), _opt(diag[2]), ptr, nbytes, stream, chunk)
         return rc, [loss] + self.grads() + diag
@@ -334,6 +338,12 @@ def test_refusals_between_canaries():
                                 scratch_bytes=kw.pop("scratch_bytes", need), sums=sums, loss=loss, **kw)
         assert rc == abi.MM_ERR_INVALID_ARG, kw
         assert untouched(), kw
+    for kw in shared_refusals(True, (64, 128)):  # what the small helpers shared with the hidden-128 entries refuse
+        case.fill_grads(CANARY)
+        rc, out = case.chunked_rc("reference", 64, scratch_ptr=base, scratch_bytes=need, sums=sums, loss=loss, **kw)
+        assert rc == abi.MM_ERR_INVALID_ARG, kw
+        assert untouched(), kw
+        assert all(bool(torch.isnan(d).all()) for d in out[13:] if d is not None), kw  # the diagnostics were not written either
     with pytest.raises(ValueError):  # the hidden-128 chunked entry refuses this size
         lib = case.learner.clib
         W, G = [_mlp_struct(n) for n in case.nets()], [_mlp_struct(n, True) for n in case.nets()]
