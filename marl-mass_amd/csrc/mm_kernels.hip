@@ -492,6 +492,16 @@ MM_DEV int corner_flags(double x, double y, double sh, double ch, int lane) {
 // corner bits << 6.  Kept packed in one VGPR end to end (messages, LDS park, classification) instead of
 // two ints and two lane masks.
 MM_DEV int pose_code(int lane, int nl, int off) { return lane | nl << 3 | off << 6; }
+// HB (kPoseHBits, in the kSine kernels without the trace): the owner of a pose also forms the two heading predicates that relate() reads of a
+// partner -- heading > 0.037 in bit 9, heading < -0.037 in bit 10 (bit 8 is the reader's "present" mark) -- once per pose,
+// instead of every reader loading the heading and comparing it for every partner and pass.  Both are false on a NaN, as the
+// compares in relate() are.  Code consumers other than relate<true> mask the bits off.  (-DMM_POSE_HBITS=0: A-B timing)
+#ifndef MM_POSE_HBITS
+#define MM_POSE_HBITS 1
+#endif
+constexpr bool kPoseHBits = MM_POSE_HBITS != 0;
+constexpr int kPoseHPos = 0x200, kPoseHNeg = 0x400;
+MM_DEV int pose_hbits(double h) { return ((h > 0.037) ? kPoseHPos : 0) | ((h < -0.037) ? kPoseHNeg : 0); }
 
 // Predicted post-state of Vehicle.step for a given steering (kinematics.py:122-141,
 // safe_controller.py:151-172): everything that does not depend on the acceleration.
@@ -506,7 +516,7 @@ struct Cand {
 // sin(beta), cos(psi' + beta), cos(psi') and the three corner angles -- become ONE sincos of the steering angle and ONE of
 // the new heading plus angle sums; beta itself is never formed (include/mm_math.h, "angle-sum forms").
 // GENERAL: the instantiation can meet a steering angle that did not come out of steering_control (kernels with HDVs / steer_vel)
-template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false>
+template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false, bool HB = false>
 MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double ch, double dt, bool sv = false, double *sine_out = nullptr) {
   Cand c;
   // "steer_vel" (safe_controller.py:124-150): the slip angle comes from the steering-angle STATE and the
@@ -532,6 +542,7 @@ MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double c
   c.lane = closest_lane<SINE>(c.x, c.y, c.h, sine_out);  // on_state_update kinematics.py:154-159 (sine_out: see closest_lane)
   c.pk = c.lane;
   if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags<SINE>(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
+  if constexpr (HB) c.pk |= pose_hbits(c.h);
   return c;
 }
 
@@ -642,7 +653,14 @@ MM_DEV int spawn_vehicle(Veh &v, int a, int n_cav, int n_hdv, uint64_t seed, uin
 // observation (envs/common/observation.py:181-273) + action mask (abstract.py:219-240)
 // ------------------------------------------------------------------------------------------------
 // SEL: the select forms of the neighbour order and the row masks (kScanSelects)
-template <int G, int KIND, bool LEND = false, bool SEL = kScanSelects>
+// WIDE (kObsWide, in the kSine kernels without the trace; LEND only): a full wave copies its run of float32 rows out in 16-byte pieces, every LDS
+// read issued in front of the first store, instead of one 8-byte piece per trip of a loop with a run-time bound.  The lent LDS
+// must be 16-byte aligned.  (-DMM_OBS_WIDE=0: the loop alone, for A-B timing)
+#ifndef MM_OBS_WIDE
+#define MM_OBS_WIDE 1
+#endif
+constexpr bool kObsWide = MM_OBS_WIDE != 0;
+template <int G, int KIND, bool LEND = false, bool SEL = kScanSelects, bool WIDE = false>
 MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, bool valid, void *obs,
                     uint8_t *avail, float *stage = nullptr, const double *sincos_h = nullptr) {
   constexpr int F = (KIND != MM_ENV_V0) ? 6 : 5;
@@ -782,10 +800,34 @@ MM_DEV void observe(const DevCfg &c, const Veh &v, int a, int gb, long long i, b
       nenv = nenv < 0 ? 0 : (nenv > 64 / G ? 64 / G : nenv);
       const int total = (int)nenv * c.N * S;
       float *dst = (float *)obs + e0 * c.N * S;
-      if constexpr (S % 2 == 0) {
-        for (int t = lane; t < total / 2; t += 64) ((float2 *)dst)[t] = ((const float2 *)sw)[t];
+      auto copy_loop = [&]() {
+        if constexpr (S % 2 == 0) {
+          for (int t = lane; t < total / 2; t += 64) ((float2 *)dst)[t] = ((const float2 *)sw)[t];
+        } else {
+          for (int t = lane; t < total; t += 64) dst[t] = sw[t];
+        }
+      };
+      if constexpr (WIDE && LEND && S % 2 == 0 && (64 / G) * G * S % 4 == 0) {
+        // a full wave's run is (64 / G) * G * S floats, a compile-time number: 16-byte pieces, all of them read before the first
+        // is stored.  A ragged last wave, N < G and a run that does not start on 16 bytes take the loop.
+        constexpr int kFull4 = (64 / G) * G * S / 4, kTrips = (kFull4 + 63) / 64;
+        if (nenv == 64 / G && c.N == G && ((uintptr_t)dst & 15) == 0) {  // (wave-uniform)
+          float4 q[kTrips];
+#pragma unroll
+          for (int j = 0; j < kTrips; j++) {
+            const int t = lane + 64 * j;  // (a lane past the end of the last trip re-reads its first piece and stores nothing)
+            q[j] = ((const float4 *)sw)[(64 * (j + 1) <= kFull4 || t < kFull4) ? t : lane];
+          }
+#pragma unroll
+          for (int j = 0; j < kTrips; j++) {
+            const int t = lane + 64 * j;
+            if (64 * (j + 1) <= kFull4 || t < kFull4) ((float4 *)dst)[t] = q[j];
+          }
+        } else {
+          copy_loop();
+        }
       } else {
-        for (int t = lane; t < total; t += 64) dst[t] = sw[t];
+        copy_loop();
       }
     }
   }
@@ -1084,6 +1126,8 @@ struct Rel {
   int cls;
   bool cflag;
 };
+// HB: the partner's two heading predicates come in bits 9 / 10 of `opk` (pose_hbits) and `oh` is not read
+template <bool HB = false>
 MM_DEV Rel relate(double ex, double ey, int epk, bool other, double ox, double oy, double oh, int opk, bool o_hdv = false) {
   const int elane = epk & 7, enl = (epk >> 3) & 7, olane = opk & 7, onl = (opk >> 3) & 7;
   // written with non-short-circuit logic on purpose: it runs once per (ego, partner) pair and should
@@ -1102,7 +1146,9 @@ MM_DEV Rel relate(double ex, double ey, int epk, bool other, double ox, double o
   const unsigned va_c = (rowEN >> (2 * olane)) & 3u;
   const unsigned g1 = (colE >> (2 * olane)) & 3u, g2 = (colE >> (2 * onl)) & 3u;
   const unsigned av_c = g1 != 0 ? g1 : g2;
-  const bool head = (dy < 0) ? (oh > 0.037) : (oh < -0.037);
+  bool head;
+  if constexpr (HB) head = (opk & ((dy < 0) ? kPoseHPos : kPoseHNeg)) != 0;
+  else head = (dy < 0) ? (oh > 0.037) : (oh < -0.037);
   const bool appr = (!(ld < 0)) & (fabs(dy) <= 3.5) & head;  // :46-57
   const bool adj = (!appr) & ((va_c | av_c) != 0);
   const bool same = (elane == olane) | (olane == enl);  // is_same_lane :15-20
@@ -1674,12 +1720,24 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #define MM_SINE_CARRY 0
 #endif
   constexpr bool kSineCarry = kPrimary && MM_SINE_CARRY != 0;
+  // kActSel (MM_ACT_FRAME, what is kept of it: DESIGN.md 6.2): the act phase's `live` regions around hl_act / controlled_act as
+  // selects.  In the kPrimary kernels, which have no HDVs and no split launches.  (-DMM_ACT_FRAME=0: the guarded calls)
+#ifndef MM_ACT_FRAME
+#define MM_ACT_FRAME 1
+#endif
+  constexpr bool kActSel = kPrimary && MM_ACT_FRAME != 0;
   // kEarly: the action and the env's n_merge / episode are loaded in front of the state loads, whose address they do not
   // depend on, instead of behind the `kind` load (the action) and in front of the outputs (the two counters): three
   // round trips to memory that now overlap the state's.  The CAV-only kernels need no `kind` to address actions[i]; the value
   // is masked afterwards.  The counters wait in the free high words of two cold slots of the lane's own column (the pose-code
   // and rank-word slots hold an int in their low word: !kPackMsg), not in registers.  In the kSine kernels: same register gate.
   constexpr bool kEarly = kSine && MM_EARLY_LOADS != 0;
+  // kHBits: the pose codes of this kernel -- pk_self, the pre-step mailbox and both candidate images -- carry their owner's heading
+  // predicates (pose_hbits), and the mailbox reader of the classification pass loads no heading.  In the kSine kernels, whose
+  // classification reads the mailbox (G <= 8), without the trace: the 8-lane MASS trace kernel already spills and went from 28
+  // to 36 B of scratch with this, the act selects and the wide copy-out, so the trace kernels keep all three of the earlier forms.
+  constexpr bool kHBits = kSine && !TRACE && kPoseHBits;
+  constexpr bool kWideObs = kSine && !TRACE && kObsWide;  // observe<WIDE>'s 16-byte copy-out of the float32 rows
   double car_sn = __builtin_nan("");
   (void)car_sn;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
@@ -1753,11 +1811,12 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     const bool hit = car_kx == __double_as_longlong(v.x) && car_ky == __double_as_longlong(v.y) && car_kh == __double_as_longlong(v.h) &&
                      (car_code >> 8) == ((kPoseWritten >> 8) | (MASS ? 1 : 0)) && (car_code & 7) == v.lane;
     carried = !__any(v.present && !hit);
-    if (carried && v.present) { spsi = car_s; cpsi = car_c; pk_self = car_code & 0xFF; }
+    if (carried && v.present) { spsi = car_s; cpsi = car_c; pk_self = (car_code & 0xFF) | (kHBits ? pose_hbits(v.h) : 0); }
   }
   if (!carried) {
     if (v.present) mmm_sincos(v.h, &spsi, &cpsi);
     if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, spsi, cpsi, v.lane) : 0);
+    if constexpr (kHBits) { if (v.present) pk_self |= pose_hbits(v.h); }
   }
 
   // Register relief: lane-private values that are written once and read rarely live in LDS ("cold"
@@ -1780,7 +1839,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   constexpr int C_CPSI = kColdB + G - 1, C_GVX = C_CPSI + 1;
   constexpr int kColdN = !SHIELDED ? 15 : (kSerialOnly ? 23 : kColdB + G - 1 + (kRoomy ? 2 : 0));
   static_assert(kColdN * MM_STEP_BLOCK * 8 >= (MM_STEP_BLOCK / 64) * 64 * 30 * 4, "the obs staging must fit in the cold slots");
-  __shared__ double s_cold[kColdN][MM_STEP_BLOCK];
+  __shared__ alignas(kWideObs ? 16 : 8) double s_cold[kColdN][MM_STEP_BLOCK];  // (16: observe<WIDE> reads the lent staging in 16-byte pieces)
   const int tid = threadIdx.x;
   auto cold_i = [&](int slot, int col) -> int & { return ((int *)&s_cold[slot][col])[0]; };  // an int kept in a slot's low word
   if (LC) {
@@ -1820,11 +1879,22 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       });
     }
     if (head) v.tspeed = s_cold[C_TSPEED][tid];
-    if (live && !hdv && head) {
-      if (time % c.nsub == 0) hl_act<KIND>(v, action);  // action_type.act abstract.py:516-519
+    if constexpr (kActSel) {
+      // (`live && !hdv && head` is `live` here) both acts run on a copy, unguarded, and `live` selects the five fields they write
+      Veh w = v;
+      if (time % c.nsub == 0) hl_act<KIND>(w, action);
+      controlled_act<false, kSine>(w, -1, sv, st_t);
+      v.hl = live ? w.hl : v.hl; v.sidx = live ? w.sidx : v.sidx; v.tspeed = live ? w.tspeed : v.tspeed;
+      v.tlane = live ? w.tlane : v.tlane; v.act_acc = live ? w.act_acc : v.act_acc;
+    } else {
+      if (live && !hdv && head) {
+        if (time % c.nsub == 0) hl_act<KIND>(v, action);  // action_type.act abstract.py:516-519
+      }
     }
     const int tl_pre = v.tlane;  // what an HDV acting before this vehicle still sees
-    if (live && !hdv && head) controlled_act<!MIXED && !kPrimary, kSine>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels, kPrimary: steering below)
+    if constexpr (!kActSel) {
+      if (live && !hdv && head) controlled_act<!MIXED && !kPrimary, kSine>(v, -1, sv, st_t);  // road.act road.py:269-278 (general kernels, kPrimary: steering below)
+    }
     if (head) s_cold[C_TSPEED][tid] = v.tspeed;
     if constexpr (MIXED) { STAMP(1); }  // (general kernels: "act" = the CAVs' part up to here; slots 3 / 4 / 5 split the HDVs' part)
     if constexpr (MIXED) {
@@ -1956,7 +2026,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     memset(&cA, 0, sizeof cA);
     const bool shield_on = SHIELDED && live && !hdv && v.hist_len >= 2;  // gate safe_controller.py:232-239
     if constexpr (kSineCarry) car_sn = __builtin_nan("");
-    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv, kSineCarry ? &car_sn : nullptr);
+    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine, kHBits>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv, kSineCarry ? &car_sn : nullptr);
     auto park = [&](auto base_c, const Cand &cc, double steer) {  // a candidate's LDS image (shielded kernels only)
       constexpr int base = decltype(base_c)::value;
       if constexpr (SHIELDED) {
@@ -1994,7 +2064,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
             steer_o = clipd(steer_o, -kPi / 3, kPi / 3);
             if (v.crashed) { steer_o = 0; t_o = 0; }
           }
-          park_at(mk_A ? (int)C_A : (int)C_B, predict<KIND, true, MASS, MIXED, kSine>(v, steer_o, t_o, spsi, cpsi, dt, false), steer_o);
+          park_at(mk_A ? (int)C_A : (int)C_B, predict<KIND, true, MASS, MIXED, kSine, kHBits>(v, steer_o, t_o, spsi, cpsi, dt, false), steer_o);
           haveA = true; haveB = haveB || !mk_A;
         }
       }
@@ -2005,7 +2075,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           double tB;
           double steerB = steering_control<kSine>(v.x, v.y, v.h, v.v, v.lane, tB);
           if (sv) steerB = steer_vel_command(steerB, v.sang);
-          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED, kSine>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
+          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED, kSine, kHBits>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
           haveB = true;
         }
       }
@@ -2177,7 +2247,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               i_first = live && rank < p_rank;                      // I step before this partner
               // its pose as I see it: the committed post-state if it steps before me, else the pre-step pose
               const int pb = (!i_first && p_rank < 99) ? ((pw & 256) ? (int)C_B : (int)C_A) : (int)C_PRE;
-              ox = s_cold[pb + 0][pl]; oy = s_cold[pb + 1][pl]; oh = s_cold[pb + 2][pl];
+              ox = s_cold[pb + 0][pl]; oy = s_cold[pb + 1][pl];
+              if constexpr (kHBits) oh = 0.0;  // (its predicates are in the code word)
+              else oh = s_cold[pb + 2][pl];
               opk = cold_i(pb + 3, pl) | (p_rank < 99 ? 256 : 0);
             } else {
               p_rank = dppx_i<m>(live ? rank : 99);
@@ -2189,7 +2261,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               opk = dppx_i<m>(spk | (int)live << 8);
             }
             const bool o_first = !i_first && p_rank < 99;  // partner steps before me (ranks are distinct)
-            const Rel r = relate(v.x, v.y, pk_self, ((opk >> 8) & 1) != 0, ox, oy, oh, opk);
+            const Rel r = relate<kHBits && kMailbox>(v.x, v.y, pk_self, ((opk >> 8) & 1) != 0, ox, oy, oh, opk);
             if constexpr (count5) s_cold[kColdB + m - 1][tid] = r.key;
             // running "first in sorted order" per class: smaller key, ties by creation index (selects, no branches)
             // (the slot's flags ride in the index word -- bit 4: that partner steps before me, bit 5: its corner
@@ -2256,7 +2328,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           // ---- MASS: fixed point over the decided accelerations (HSS: one evaluation) ----------
           double acc_cur = shield_on ? 0.0 : v.act_acc;  // vehicles without a shield keep their command
           if constexpr (kRoomy) v.gvx = GVX();
-          const ShieldStatic ss = shield_static<MASS>(c, v, cpsi_now, pk_self, nb);
+          const ShieldStatic ss = shield_static<MASS>(c, v, cpsi_now, kHBits ? pk_self & 0xFF : pk_self, nb);
           if constexpr (IPM) {
             // ---- interior-point mode: ONE wave-wide loop, every lane at its own iteration of its own QP ----------------
             // A follower's QP reads the acceleration its leader / front-adjacent vehicle DECIDED this sub-step, so a QP can
@@ -2540,7 +2612,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           // (absent slots contribute g*u = 0, an obstacle +0: handled in shield_dyn<.., PRE> / obstacle_override)
           obstacle_override<MASS>(nb, v.x, v.y);
           const bool mine = has && a == ai && shield_on;  // this stage's ego
-          ShieldOut s1 = shield_eval<MASS, true, IPM>(c, v, cpsi, pk_self, nb, mine);
+          ShieldOut s1 = shield_eval<MASS, true, IPM>(c, v, cpsi, kHBits ? pk_self & 0xFF : pk_self, nb, mine);
           if (hss_collab) s1.flags |= MM_FLAG_IS_COLLABORATING;  // vehicle.is_collaborating = cbf.constrain_adj
           if (IPM && mine && s1.bounds) atomicOr(c.err, MM_LATCH_QP_BOUNDS);
           if (mine) {
@@ -2933,6 +3005,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       if constexpr (kCarry) {  // what the next launch would derive for the spawned pose, by the very calls it would make
         mmm_sincos(v.h, &car_s, &car_c);
         pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, car_s, car_c, v.lane) : 0);
+        if constexpr (kHBits) pk_self |= pose_hbits(v.h);
       }
       s_cold[C_H1X][tid] = v.h1x; s_cold[C_H1VX][tid] = v.h1vx; s_cold[C_H2X][tid] = v.h2x; s_cold[C_H2VX][tid] = v.h2vx;
       s_cold[C_SSTEER][tid] = v.safe_steer; s_cold[C_SACC][tid] = v.safe_acc; s_cold[C_TSPEED][tid] = v.tspeed;
@@ -2961,7 +3034,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   __syncthreads();  // every wave is done with its cold slots: the obs staging below reuses that LDS
   STAMP(14);  // barrier (+ drain of the stores issued before it)
   const double sc_h[2] = {spsi, cpsi};
-  observe<G, KIND, true, kScan>(c, v, a, gb, i, valid, out.obs, out.action_mask, (float *)&s_cold[0][0], sc_h);
+  observe<G, KIND, true, kScan, kWideObs>(c, v, a, gb, i, valid, out.obs, out.action_mask, (float *)&s_cold[0][0], sc_h);
   STAMP(12);  // observation
 #ifdef MM_STAMPS
   {
