@@ -20,9 +20,10 @@
  * No floating-point atomics anywhere: two calls on the same inputs give bit-identical outputs.  Only enqueues work on
  * `stream` (no allocation, no synchronisation): graph-capturable.
  *
- * mm_policy_wide_train_chunked (at the end) is the same gradient in passes under a fixed scratch budget.
+ * mm_policy_wide_train_chunked (below) is the same gradient in passes under a fixed scratch budget, and
+ * mm_policy_wide_train_partial / mm_policy_wide_train_finish (at the end) over a batch that is sharded over ranks.
  *
- * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip, mm_policy_wide_chunked.hip): no oracle twin, not part of
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip, mm_policy_wide_chunked.hip, mm_policy_wide_sharded.hip): no oracle twin, not part of
  * include/mm_abi.h's symbol list or version.  torch.autograd on the two rollout modules is the CPU form.
  */
 #ifndef MM_POLICY_WIDE_TRAIN_H
@@ -151,6 +152,59 @@ int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_stride, int64
                                      const float *advantages, const MMMlpParams *actor_grads, const MMMlpParams *critic_grads,
                                      float *loss, float *logp_taken, float *value, float *ratio, void *scratch,
                                      uint64_t scratch_bytes, MMStream stream, int64_t chunk);
+
+/*
+ * The same gradients over a batch that is SHARDED over ranks, in two phases (marl-mass_amd/csrc/mm_policy_wide_sharded.hip):
+ * mm_policy_train_partial / mm_policy_train_finish's protocol (include/mm_policy_train.h; the header's check and the order of
+ * every sum: include/mm_policy_gi_train.h) at hidden == 512, as those are to mm_policy_train_chunked.  Every rank runs `partial`
+ * on its own samples, the R blocks are gathered in rank order, and every rank runs `finish` on the same R blocks: the same bits
+ * on every rank.
+ *
+ * The shard block: MM_PW_SHARD_DOUBLES doubles on the device, 16-byte aligned, 4 866 352 bytes (mm_policy_wide_train_shard_bytes),
+ *   [0] B of the WHOLE batch   [1] this rank's own number of valid samples
+ *   [2] the configuration word n_s + 2^8 n_a + 2^16 (reference form + 2 huber) + 2^24 networks (1 actor + 2 critic) + 2^26; the
+ *       2^26 bit says "hidden 512": an exact integer below 2^31, and a hidden-128 block never passes the wide finish   [3] 0
+ *   [4] the un-normalised fp64 sum of the actor's loss terms, [5] of the critic's (0 for a network that was not given)
+ *   [6 .. 6 + 304 144) the actor's fp64 accumulator block, then [.. + 304 144) the critic's, each in the layout of one kernel-B
+ *       partial block (MM_POLICY_WIDE_TRAIN_PARTIAL_BYTES / 4 slots): dW2 [512][544] at 0 (row pitch 544, k2 columns used: 512
+ *       for the actor, 512 + n_a for the critic); head rows [16][512] at 278 528 (n_a rows used, 1 for the critic); dW1 [512][32]
+ *       at 286 720 (n_s columns used); db2 [512] at 303 104; head bias [16] at 303 616; db1 [512] at 303 632.  Zeros for a
+ *       network that was not given.
+ * Every double of the block is a function of the inputs: a slot that finish does not read (a column, row or bias beyond the
+ * used ones above) is 0.0, whatever the scratch held.
+ *
+ * mm_policy_wide_train_partial: mm_policy_wide_train_chunked's arguments without actor_grads, critic_grads and loss, and with
+ * count (DEV int32[1], 4-byte aligned: B of the whole batch over all ranks) and shard (DEV double[MM_PW_SHARD_DOUBLES], 16-byte
+ * aligned, WRITTEN).  Kernel A scales by *count; adv_sums is the whole batch's.  Kernel A, the loss tree and the pass and slice
+ * order are the chunked entry's.  n == 0 writes a valid all-zero block with local count 0 (the per-sample pointers and the
+ * scratch may be NULL).  scratch: mm_policy_wide_train_chunked_scratch_bytes(n, chunk); its two accumulator blocks go unused.
+ * MM_ERR_INVALID_ARG: as mm_policy_wide_train_chunked (without what concerns the gradients and loss), count or shard NULL or
+ * misaligned, hidden != 512.  A refused call enqueues nothing.
+ *
+ * mm_policy_wide_train_finish: actor_grads / critic_grads: the networks whose gradients are WRITTEN (at least one; the other's
+ * tensors are not touched and its loss is 0).  loss: DEV float[2].  One thread per gradient element starts from block 0's
+ * value, adds blocks 1 .. n_blocks - 1 in index order in fp64 and rounds once to float32; the losses are the R loss doubles
+ * added in index order and scaled as the chunked entry scales them (-s / B, reference form -s / B^2; critic s / B).  Every block
+ * must carry the same B and configuration word, the word must be that of the call (n_s, n_a, the hidden-512 bit) and name every
+ * requested network, and the local counts must add up to B: if not, every requested gradient and both losses are NaN.
+ * B == 0 writes zeros.  With one block and B the rank's own count the results are mm_policy_wide_train_chunked's bits.
+ * MM_ERR_INVALID_ARG: blocks or loss NULL, no gradients at all, a NULL pointer among a given network's six, n_blocks outside
+ *   1..64, block_stride below MM_PW_SHARD_DOUBLES, n_s outside 25..32, n_a outside 1..8.
+ * Both: deterministic, no floating-point atomics, only enqueue on `stream`: graph-capturable.
+ */
+#define MM_PW_SHARD_DOUBLES 608294 /* 4 + 2 + 2 * 304 144 */
+
+int32_t mm_policy_wide_train_shard_bytes(uint64_t *bytes);
+
+int32_t mm_policy_wide_train_partial(const float *obs, int64_t obs_stride, int64_t n, int32_t n_s, const int32_t *actions,
+                                     int64_t act_stride, const float *returns, int64_t ret_stride, const float *old_logp,
+                                     const uint8_t *valid, const MMMlpParams *actor, const MMMlpParams *critic, int32_t hidden,
+                                     int32_t n_a, float clip_param, int32_t critic_loss, const float *adv_sums,
+                                     const float *advantages, const int32_t *count, double *shard, float *logp_taken, float *value,
+                                     float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk);
+
+int32_t mm_policy_wide_train_finish(const double *blocks, int32_t n_blocks, int64_t block_stride, int32_t n_s, int32_t n_a,
+                                    const MMMlpParams *actor_grads, const MMMlpParams *critic_grads, float *loss, MMStream stream);
 
 #ifdef __cplusplus
 }

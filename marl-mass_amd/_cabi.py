@@ -397,6 +397,17 @@ class CLib(object):
             lib.mm_policy_wide_train_chunked_scratch_bytes.restype = i32
             lib.mm_policy_wide_train_chunked.argtypes = list(lib.mm_policy_wide_train.argtypes) + [i64]
             lib.mm_policy_wide_train_chunked.restype = i32
+        # and over a batch sharded over ranks (mm_policy_wide_sharded.hip): the argument lists of mm_policy_train_partial /
+        # mm_policy_train_finish, hidden 512
+        self.has_policy_wide_train_sharded = self.has_policy_wide_train_chunked and sharded("wide_train")
+        if self.has_policy_wide_train_sharded:
+            a = list(lib.mm_policy_wide_train_chunked.argtypes)  # [18], [19] the gradients, [20] loss -> count, shard
+            lib.mm_policy_wide_train_shard_bytes.argtypes = [C.POINTER(u64)]
+            lib.mm_policy_wide_train_shard_bytes.restype = i32
+            lib.mm_policy_wide_train_partial.argtypes = a[:18] + [vp, vp] + a[21:]
+            lib.mm_policy_wide_train_partial.restype = i32
+            lib.mm_policy_wide_train_finish.argtypes = [vp, i32, i64, i32, i32, C.POINTER(MMMlpParams), C.POINTER(MMMlpParams), vp, vp]
+            lib.mm_policy_wide_train_finish.restype = i32
         # clip_grad_norm_ + RMSprop / Adam + soft target update in one launch (include/mm_opt_step.h), also libmm_hip.so only
         self.has_opt_step = hasattr(lib, "mm_opt_step")
         if self.has_opt_step:
@@ -545,6 +556,19 @@ class CLib(object):
         b = C.c_uint64()
         self.check(self.lib.mm_policy_wide_train_chunked_scratch_bytes(n, chunk, C.byref(b)))
         return b.value
+
+    def require_policy_wide_train_sharded(self):
+        if not self.has_policy_wide_train_sharded:
+            raise NotImplementedError("%s does not export mm_policy_wide_train_partial / _finish: the hidden-512 actor's and "
+                                      "critic's gradients over rank-sharded batches need the HIP library"
+                                      % os.path.basename(self.path))
+
+    def policy_wide_train_shard_doubles(self):
+        """Doubles of the hidden-512 networks' shard block (include/mm_policy_wide_train.h: MM_PW_SHARD_DOUBLES)."""
+        self.require_policy_wide_train_sharded()
+        b = C.c_uint64()
+        self.check(self.lib.mm_policy_wide_train_shard_bytes(C.byref(b)))
+        return b.value // 8
 
     def require_opt_step(self):
         if not self.has_opt_step:

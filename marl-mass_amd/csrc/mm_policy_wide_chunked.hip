@@ -20,6 +20,9 @@
 // the unchunked fold computes over its one pass, so chunk >= n gives the unchunked entry's bits.  Losses and diagnostics are per
 // tile / per sample and do not depend on the slicing at all.  No floating-point atomics; only enqueues on the stream.
 //
+// The argument check and the pass loop are host functions (wide_args_ok, wide_passes: mm_policy_wide_chunked.h) that the
+// rank-sharded entries (mm_policy_wide_sharded.hip) run too, with the caller's shard block as the accumulator.
+//
 // chunk is a positive multiple of 64: every pass but the last is whole 32-sample tiles (the loss partials and the diagnostics
 // of a pass start on a tile boundary of the global arrays) and a slice of kernel B keeps its minimum of 2 tiles.
 #include "mm_policy_wide_chunked.h"
@@ -77,19 +80,8 @@ __global__ __launch_bounds__(256) void policy_wide_chunked_finish_kernel(const d
   if (t < n_out) gr.b3[t] = (float)acc[Part::kbh + t];
 }
 
-// ---- host side
-// The chunked scratch, offsets in floats: the header, the four [512][512] blocks and the per-sample rows as in the unchunked
-// layout of `chunk` samples; then the fp64 loss partials of all ceil(n / 32) tiles of the actor and of the critic, the partial
-// blocks of one pass, and the two fp64 accumulator blocks.
-// The partial blocks hold the most slices ANY pass of at most `chunk` samples cuts, not the slices of a full pass: under the
-// header's rule a pass of t tiles cuts ceil(t / max(2, ceil(t / 48))) slices, never more than 48 nor than ceil(t / 2), and a
-// shorter last pass can cut more than a full one (98 tiles: 33 slices of 3; 96 tiles: 48 slices of 2).
-struct ChunkLayout {
-  wt::WideLayout rows;  // the unchunked layout of `chunk` samples: w2t, w2p, xs .. dh
-  long long ntiles, lossp, part, acc, total;
-  int blocks;
-};
-
+// ---- host side (the scratch layout: mm_policy_wide_chunked.h): the argument check and the pass loop, which the entry below runs
+// on the whole batch and the rank-sharded ones (mm_policy_wide_sharded.hip) on a rank's samples
 static ChunkLayout chunk_layout(long long n, long long chunk) {
   ChunkLayout L;
   L.rows = wt::layout_of(chunk);
@@ -100,6 +92,52 @@ static ChunkLayout chunk_layout(long long n, long long chunk) {
   L.acc = L.part + (long long)L.blocks * Part::kSize;
   L.total = L.acc + 2ll * 2 * Part::kSize;  // double[2][Part::kSize]
   return L;  // (total * 4 == MM_POLICY_WIDE_TRAIN_CHUNKED_BYTES(n, chunk): tests/test_wide_chunked_host.py restates the sum)
+}
+
+bool wide_args_ok(const wt::PassArgs &b, const WideNet (&net)[2], int32_t hidden, int32_t critic_loss, int64_t chunk,
+                  const void *scratch, uint64_t scratch_bytes, ChunkLayout &L) {
+  L = {};
+  const bool actor = net[0].w != nullptr, critic = net[1].w != nullptr;
+  if ((!actor && !critic) || (actor && !complete(net[0].w)) || (critic && !complete(net[1].w))) return false;
+  if (!shape_ok(b.n, b.n_s, hidden, b.n_a, kWide)) return false;
+  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return false;
+  if (!(b.clip_param >= 0.0f) || !chunk_ok(chunk)) return false;
+  if ((!actor && (net[0].out0 || net[0].out1)) || (!critic && net[1].out0)) return false;
+  if (b.n == 0) return true;  // (empty inputs, adv_sums, advantages and the scratch are not looked at and may be NULL)
+  if (!b.obs || !b.actions || b.obs_stride < b.n_s || (actor && !b.old_logp) || (critic && !b.returns)) return false;
+  if (actor && ((b.adv_sums != nullptr) == (b.advantages != nullptr))) return false;
+  L = chunk_layout(b.n, chunk);
+  if (!scratch || ((uintptr_t)scratch & (MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN - 1)) || scratch_bytes < (uint64_t)L.total * 4u) return false;
+  // the two pass sizes there are, the full one and the last one's, fit the rows and the partial blocks the size query promised
+  const long long full = b.n < chunk ? b.n : (long long)chunk, last = b.n % chunk ? b.n % chunk : (long long)chunk;
+  const wt::WideLayout F = wt::layout_of(full), E = wt::layout_of(last);
+  return F.n_pad <= L.rows.n_pad && E.n_pad <= L.rows.n_pad && F.slices <= L.blocks && E.slices <= L.blocks;
+}
+
+void wide_passes(hipStream_t s, const wt::PassArgs &b, const WideNet (&net)[2], long long chunk, const ChunkLayout &L, float *sc,
+                 double *acc) {
+  wt::PassArgs p = b;
+  const wt::WideRows rows = {sc + L.rows.xs, sc + L.rows.h1, sc + L.rows.h2, sc + L.rows.dz2, sc + L.rows.dz1, sc + L.rows.dh};
+  p.rows = rows;
+  float *part = sc + L.part;
+  wt::launch_prep(s, net[0].w ? net[0].w->W2 : nullptr, net[1].w ? net[1].w->W2 : nullptr, kWide + b.n_a, sc + L.rows.w2t,
+                  sc + L.rows.w2p, b.valid, b.n, (int *)sc);
+  for (long long c0 = 0; c0 < b.n; c0 += chunk) {
+    p.n = b.n - c0 < chunk ? b.n - c0 : chunk;
+    const wt::WideLayout P = wt::layout_of(p.n);  // the pass's tiles and slices
+    p.obs = b.obs + c0 * b.obs_stride; p.actions = b.actions + c0 * b.act_stride; p.returns = shifted(b.returns, c0 * b.ret_stride);
+    p.old_logp = shifted(b.old_logp, c0); p.valid = shifted(b.valid, c0); p.advantages = shifted(b.advantages, c0);
+    for (int k = 0; k < 2; k++) {  // the actor, then the critic
+      if (!net[k].w) continue;
+      p.w = *net[k].w; p.w2t = sc + L.rows.w2t + k * wt::kSquare; p.w2p = sc + L.rows.w2p + k * wt::kSquare;
+      p.lossp = (double *)(sc + L.lossp) + k * L.ntiles + c0 / 32;
+      p.out0 = shifted(net[k].out0, c0); p.out1 = shifted(net[k].out1, c0);
+      wt::launch_sample(s, k != 0, p);
+      wt::launch_wgrad(s, k != 0, rows, P.n_pad, P.slice_rows, P.slices, part);
+      hipLaunchKernelGGL(policy_wide_chunked_accumulate_kernel, dim3((Part::kSize + 255) / 256), dim3(256), 0, s, (const float *)part,
+                         P.slices, acc + k * Part::kSize);
+    }
+  }
 }
 
 }  // namespace wide_chunked
@@ -121,73 +159,32 @@ extern "C" int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_st
                                                 float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream, int64_t chunk) {
   using namespace mm::wide_chunked;
   namespace wt = mm::wt;
-  if ((!actor && !critic) || !loss) return MM_ERR_INVALID_ARG;
-  if ((actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
-  if ((actor && (!complete(actor) || !complete(actor_grads))) || (critic && (!complete(critic) || !complete(critic_grads))))
-    return MM_ERR_INVALID_ARG;
-  if (!shape_ok(n, n_s, hidden, n_a, kWide)) return MM_ERR_INVALID_ARG;
-  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
-  if (!(clip_param >= 0.0f) || !chunk_ok(chunk)) return MM_ERR_INVALID_ARG;
-  if ((!actor && (logp_taken || ratio)) || (!critic && value)) return MM_ERR_INVALID_ARG;
+  // everything that can refuse the call comes before the first enqueue
+  if (!loss || (actor != nullptr) != (actor_grads != nullptr) || (critic != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
+  if ((actor_grads && !complete(actor_grads)) || (critic_grads && !complete(critic_grads))) return MM_ERR_INVALID_ARG;
+  float *sc = (float *)scratch;
+  int *count = (int *)sc;  // prep's count is the one kernel A scales by
+  wt::PassArgs p = {};  // the whole batch
+  p.obs = obs; p.obs_stride = obs_stride; p.n = n; p.n_s = n_s; p.actions = actions; p.act_stride = act_stride; p.returns = returns;
+  p.ret_stride = ret_stride; p.old_logp = old_logp; p.valid = valid; p.n_a = n_a; p.clip_param = clip_param;
+  p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.advantages = advantages; p.count = count;
+  const WideNet net[2] = {{actor, logp_taken, ratio}, {critic, value, nullptr}};
+  ChunkLayout L;
+  if (!wide_args_ok(p, net, hidden, critic_loss, chunk, scratch, scratch_bytes, L)) return MM_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int k2c = kWide + n_a;
-  // everything that can refuse the call comes before the first enqueue
-  ChunkLayout L = {};
-  if (n > 0) {
-    if (!obs || !actions || obs_stride < n_s || (actor && !old_logp) || (critic && !returns)) return MM_ERR_INVALID_ARG;
-    if (actor && ((adv_sums != nullptr) == (advantages != nullptr))) return MM_ERR_INVALID_ARG;
-    L = chunk_layout(n, chunk);
-    if (!scratch || ((uintptr_t)scratch & (MM_POLICY_WIDE_TRAIN_SCRATCH_ALIGN - 1)) || scratch_bytes < (uint64_t)L.total * 4u)
-      return MM_ERR_INVALID_ARG;
-    // the two pass sizes there are, the full one and the last one's, fit the rows and the partial blocks the size query promised
-    const long long full = n < chunk ? n : (long long)chunk, last = n % chunk ? n % chunk : (long long)chunk;
-    const wt::WideLayout F = wt::layout_of(full), E = wt::layout_of(last);
-    if (F.n_pad > L.rows.n_pad || E.n_pad > L.rows.n_pad || F.slices > L.blocks || E.slices > L.blocks) return MM_ERR_INVALID_ARG;
-  }
   if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (n == 0) {
     if (actor && !zero_mlp_grads(s, actor_grads, kWide, n_s, kWide, n_a)) return MM_ERR_DEVICE;
     if (critic && !zero_mlp_grads(s, critic_grads, kWide, n_s, k2c, 1)) return MM_ERR_DEVICE;
     return MM_OK;
   }
-  float *sc = (float *)scratch;
-  int *count = (int *)sc;
   double *acc_a = (double *)(sc + L.acc), *acc_c = acc_a + Part::kSize;
   // the two networks' loss partials live side by side: both are folded at the end, after the passes alternated over the rows
   double *lossp_a = (double *)(sc + L.lossp), *lossp_c = lossp_a + L.ntiles;
   if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) return MM_ERR_DEVICE;
   if (hipMemsetAsync(acc_a, 0, 2 * (size_t)Part::kSize * sizeof(double), s) != hipSuccess) return MM_ERR_DEVICE;
-  wt::launch_prep(s, actor ? actor->W2 : nullptr, critic ? critic->W2 : nullptr, k2c, sc + L.rows.w2t, sc + L.rows.w2p, valid,
-                  (long long)n, count);
-  wt::PassArgs p = {};
-  p.obs_stride = obs_stride; p.n_s = n_s; p.act_stride = act_stride; p.ret_stride = ret_stride; p.n_a = n_a;
-  p.clip_param = clip_param; p.huber = critic_loss == MM_PT_CRITIC_HUBER; p.adv_sums = adv_sums; p.count = count;
-  const wt::WideRows rows = {sc + L.rows.xs, sc + L.rows.h1, sc + L.rows.h2, sc + L.rows.dz2, sc + L.rows.dz1, sc + L.rows.dh};
-  p.rows = rows;
-  float *part = sc + L.part;
-  for (long long c0 = 0; c0 < n; c0 += chunk) {
-    const long long np = n - c0 < chunk ? n - c0 : (long long)chunk;
-    const wt::WideLayout P = wt::layout_of(np);  // the pass's tiles and slices
-    p.n = np;
-    p.obs = obs + c0 * obs_stride; p.actions = actions + c0 * act_stride; p.returns = shifted(returns, c0 * ret_stride);
-    p.old_logp = shifted(old_logp, c0); p.valid = shifted(valid, c0); p.advantages = shifted(advantages, c0);
-    if (actor) {
-      p.w = *actor; p.w2t = sc + L.rows.w2t; p.w2p = sc + L.rows.w2p; p.lossp = lossp_a + c0 / 32;
-      p.out0 = shifted(logp_taken, c0); p.out1 = shifted(ratio, c0);
-      wt::launch_sample(s, false, p);
-      wt::launch_wgrad(s, false, rows, P.n_pad, P.slice_rows, P.slices, part);
-      hipLaunchKernelGGL(policy_wide_chunked_accumulate_kernel, dim3((Part::kSize + 255) / 256), dim3(256), 0, s, (const float *)part,
-                         P.slices, acc_a);
-    }
-    if (critic) {
-      p.w = *critic; p.w2t = sc + L.rows.w2t + wt::kSquare; p.w2p = sc + L.rows.w2p + wt::kSquare; p.lossp = lossp_c + c0 / 32;
-      p.out0 = shifted(value, c0); p.out1 = nullptr;
-      wt::launch_sample(s, true, p);
-      wt::launch_wgrad(s, true, rows, P.n_pad, P.slice_rows, P.slices, part);
-      hipLaunchKernelGGL(policy_wide_chunked_accumulate_kernel, dim3((Part::kSize + 255) / 256), dim3(256), 0, s, (const float *)part,
-                         P.slices, acc_c);
-    }
-  }
+  wide_passes(s, p, net, chunk, L, sc, acc_a);
   if (actor)
     hipLaunchKernelGGL(policy_wide_chunked_finish_kernel, dim3((finish_elems(n_s, kWide, n_a) + 255) / 256 + 1), dim3(256), 0, s,
                        (const double *)acc_a, (int)n_s, kWide, (int)n_a, *actor_grads, (const double *)lossp_a, L.ntiles,

@@ -30,11 +30,12 @@ step, the same losses bit for bit.
 
 With `shard_group` (a torch.distributed process group, or "world") a learner trains on a batch that is SHARDED over ranks, as the
 rollout's envs are: every agent step of train() takes the gradient of ONE loss over all ranks' samples.  Each rank runs
-`shard_block` on its own samples (`mm_policy_gi_train_partial` / `mm_policy_train_partial`: the chunked entry's passes into a
-caller-visible fp64 block, scaled by the whole batch's count), the R blocks are gathered in rank order and `finish_shards`
+`shard_block` on its own samples (`mm_policy_gi_train_partial` / `mm_policy_train_partial`, hidden 512:
+`mm_policy_wide_train_partial`: the chunked entry's passes into a caller-visible fp64 block, scaled by the whole batch's count), the R blocks are gathered in rank order and `finish_shards`
 (`mm_policy_*_train_finish`) folds them in that order on every rank: the same bits from the same blocks, so replicas that start
 equal stay bit-equal without a broadcast (`replicas_in_sync()` checks it).  Both phases are public and need no process group.
-Limits: a sharded train() is not graph-capturable (it runs collectives), and hidden 512 with `shard_group` is a ValueError.
+At hidden 512 a block is 4.9 MB per rank and agent step, and one pass of a whole shard is 8 384 bytes per sample: a sharded
+learner there wants `scratch_budget_bytes`.  Limit: a sharded train() is not graph-capturable (it runs collectives).
 """
 import copy
 import ctypes as C
@@ -616,14 +617,15 @@ class PPOLearner(_DeviceLearner):
     def __init__(self, actor, critic, clib, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
                  soft_update_every="train", scratch_budget_bytes=None, shard_group=None):
-        if shard_group is not None and _hidden_of(actor) == 512:
-            raise ValueError("shard_group is not supported with hidden size 512: the rank-sharded gradient entries are hidden 128")
         # (first: a budget no call can meet is refused whatever else is passed; the smallest pass is that of the hidden size)
         if _hidden_of(actor) == 512:
             self._init_budget(scratch_budget_bytes, clib.require_policy_wide_train_chunked, clib.policy_wide_train_chunked_scratch_bytes)
         else:
             self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
-        self._init_shards(shard_group, clib.require_policy_train_sharded, clib.policy_train_shard_doubles)
+        if _hidden_of(actor) == 512:
+            self._init_shards(shard_group, clib.require_policy_wide_train_sharded, clib.policy_wide_train_shard_doubles)
+        else:
+            self._init_shards(shard_group, clib.require_policy_train_sharded, clib.policy_train_shard_doubles)
         if soft_update_every not in ("train", "agent_step"):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
@@ -639,20 +641,26 @@ class PPOLearner(_DeviceLearner):
         for p in list(actor.parameters()) + list(critic.parameters()):
             if p.dtype != torch.float32 or p.device.type != "cuda":
                 raise ValueError(("scratch_budget_bytes is a budget of device memory: " if scratch_budget_bytes is not None else "")
+                                 + ("shard_group gathers device blocks: " if shard_group is not None else "")
                                  + "PPOLearner needs float32 networks on the device")
         if critic_loss not in abi.PT_CRITIC_LOSS:
             raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
         opt = _optimizer_class(optimizer_type)
-        # the library's entries for this hidden size: (gradient, evaluation, scratch query, the gradient in passes)
+        # the library's entries for this hidden size: (gradient, evaluation, scratch query, the gradient in passes, and the two
+        # phases over rank-sharded batches where the library has them: without a shard group nothing requires them)
         chunked = scratch_budget_bytes is not None  # (_init_budget required the entry)
         if hid == 512:
             clib.require_policy_wide_train()
             self._entries = (clib.lib.mm_policy_wide_train, clib.lib.mm_policy_wide_eval, clib.policy_wide_train_scratch_bytes,
-                             clib.lib.mm_policy_wide_train_chunked if chunked else None)
+                             clib.lib.mm_policy_wide_train_chunked if chunked else None,
+                             clib.lib.mm_policy_wide_train_partial if clib.has_policy_wide_train_sharded else None,
+                             clib.lib.mm_policy_wide_train_finish if clib.has_policy_wide_train_sharded else None)
         else:
             clib.require_policy_train()
             self._entries = (clib.lib.mm_policy_train, clib.lib.mm_policy_eval, clib.policy_train_scratch_bytes,
-                             clib.lib.mm_policy_train_chunked if chunked else None)
+                             clib.lib.mm_policy_train_chunked if chunked else None,
+                             clib.lib.mm_policy_train_partial if clib.has_policy_train_sharded else None,
+                             clib.lib.mm_policy_train_finish if clib.has_policy_train_sharded else None)
         _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, self._entries[2])
         self.actor, self.critic = actor, critic
         self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)
@@ -774,14 +782,13 @@ class PPOLearner(_DeviceLearner):
     # -- the two phases of a gradient over rank-sharded batches --------------------------------
     def shard_block(self, obs, actions, returns, old_logp, count, valid=None, adv_sums=None, advantages=None, diagnostics=False,
                     out=None, networks="both"):
-        """Phase one, on this rank's samples (mm_policy_train_partial): the float64 [K] shard block on the device (written into
-        `out` when given); with diagnostics also (logp_taken, value, ratio) [n].  The inputs are loss_and_grad's, n == 0 included
+        """Phase one, on this rank's samples (mm_policy_train_partial; hidden 512: mm_policy_wide_train_partial): the float64 [K]
+        shard block on the device (written into `out` when given); with diagnostics also (logp_taken, value, ratio) [n].  The inputs are loss_and_grad's, n == 0 included
         (an empty shard); `count` is an int32 [1] device tensor holding B, the number of valid samples of the WHOLE batch over
         all ranks, and adv_sums is the whole batch's (S+, S-).  The passes are _plan(n)'s chunk; without a budget, or where the
-        unchunked scratch fits it, one pass.  Touches no .grad.  Only enqueues work.  Hidden 128 only."""
-        if self.hidden != 128:
-            raise ValueError("the rank-sharded gradient entries are hidden 128")
-        self.clib.require_policy_train_sharded()
+        unchunked scratch fits it, one pass (at hidden 512 one pass of a whole shard is 8 384 bytes per sample: a sharded learner
+        there wants a budget).  Touches no .grad.  Only enqueues work."""
+        self._require_sharded()
         n, S, old_logp, valid, adv_sums, advantages, with_a, with_c = self._inputs(obs, actions, returns, old_logp, valid, adv_sums,
                                                                                     advantages, networks)
         if count.dtype != torch.int32 or count.numel() != 1 or count.device != self.device:
@@ -793,7 +800,7 @@ class PPOLearner(_DeviceLearner):
         diag = [new(with_a), new(with_c), new(with_a)]
         chunk, scratch = self._shard_plan(n)
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self.clib.check(self.clib.lib.mm_policy_train_partial(
+        self.clib.check(self._entries[4](
             obs.data_ptr(), obs.stride(0) if n else S, n, S, actions.data_ptr(), actions.stride(0) if n else 1, returns.data_ptr(),
             returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), ref(W[0]), ref(W[1]), self.hidden, self.n_a, self.clip_param,
             abi.PT_CRITIC_LOSS[self.critic_loss], opt(adv_sums) if with_a else None, opt(advantages) if with_a else None,
@@ -802,19 +809,20 @@ class PPOLearner(_DeviceLearner):
         return (block, tuple(diag)) if diagnostics else block
 
     def finish_shards(self, blocks, networks="both"):
-        """Phase two (mm_policy_train_finish): blocks float64 [R, K], the R ranks' shard blocks in rank order.  Writes the .grad
+        """Phase two (mm_policy_train_finish; hidden 512: mm_policy_wide_train_finish): blocks float64 [R, K], the R ranks' shard
+        blocks in rank order, K = shard_doubles() (53 798; hidden 512: 608 294, 4.9 MB).  Writes the .grad
         of every parameter of the requested networks -- float32 of the blocks' fp64 sum in row order -- and returns the float32
         [2] loss tensor of loss_and_grad (0 for a network that is not requested).  Blocks that do not belong together (another B
         or configuration, local counts that do not add up to B, a requested network missing from a block) give NaN everywhere."""
         if networks not in ("both", "actor", "critic"):
             raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
-        self.clib.require_policy_train_sharded()
+        self._require_sharded()
         blocks, stride = self._shard_blocks(blocks)
         G = [_mlp_struct(self.actor, True) if networks != "critic" else None, _mlp_struct(self.critic, True) if networks != "actor" else None]
         ref = lambda st: None if st is None else C.byref(st)  # noqa: E731
         loss = torch.empty(2, dtype=torch.float32, device=self.device)
-        self.clib.check(self.clib.lib.mm_policy_train_finish(blocks.data_ptr(), blocks.shape[0], stride, self.n_s, self.n_a, ref(G[0]),
-                                                             ref(G[1]), loss.data_ptr(), self._stream()))
+        self.clib.check(self._entries[5](blocks.data_ptr(), blocks.shape[0], stride, self.n_s, self.n_a, ref(G[0]), ref(G[1]),
+                                         loss.data_ptr(), self._stream()))
         return loss
 
     def _replica_tensors(self):

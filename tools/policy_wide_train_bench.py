@@ -13,6 +13,12 @@ calls as fill 0.5 s, timed by device events; medians and the spread of the windo
 
     python tools/policy_wide_train_bench.py [--sizes 102400 524288] [--json out.json] [--fused]
     python tools/policy_wide_train_bench.py --sizes 524288 --kernel-stats stats.csv --json out.json
+    python tools/policy_wide_train_bench.py --sharded [--chunk 65536] --json profiles/wide_sharded/bench.json
+
+--sharded times the rank-sharded entries instead, per size on the same inputs and in passes of --chunk samples: (c) the chunked
+entry (PPOLearner.loss_and_grad under the budget of that chunk), (d) shard_block + finish_shards with one block whose B is its
+own count (mm_policy_wide_train_partial + mm_policy_wide_train_finish at R = 1: the same results bit for bit) and (e)
+finish_shards alone over R = 8 copies of that block (B set to the eight local counts' sum), with the same windows.
 
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python
 tools/policy_wide_train_bench.py --sizes N --profile-run` run; pass its *_kernel_stats.csv back with --kernel-stats and the
@@ -142,8 +148,74 @@ def paths(n, fused):
             "library_loss_and_grad": grad_only}
 
 
+def sharded_paths(n, chunk):
+    """The three timings of --sharded on one batch of n samples in passes of `chunk` (the budget of exactly that chunk)."""
+    torch.manual_seed(0)
+    clib = hip_library()
+    actor, critic = ActorNetwork(S, H, A).cuda(), CriticNetwork(S, A, H, 1).cuda()
+    budget = clib.policy_wide_train_chunked_scratch_bytes(n, chunk)
+    learner = PPOLearner(actor, critic, clib, scratch_budget_bytes=budget)
+    with torch.no_grad():
+        for p in list(actor.parameters()) + list(critic.parameters()):
+            p.add_(0.01 * torch.randn_like(p))
+    obs = torch.randn(n, S, device="cuda")
+    act = torch.randint(0, A, (n,), device="cuda", dtype=torch.int32)
+    ret = torch.randn(n, device="cuda")
+    old = learner.old_log_probs(obs, act)
+    adv = learner.advantages(obs, act, ret)
+    count = torch.tensor([n], dtype=torch.int32, device="cuda")
+    block = torch.empty(1, learner.shard_doubles(), dtype=torch.float64, device="cuda")
+
+    def chunked():
+        learner.loss_and_grad(obs, act, ret, old, advantages=adv)
+
+    def partial_finish():
+        learner.shard_block(obs, act, ret, old, count, advantages=adv, out=block[0])
+        learner.finish_shards(block)
+
+    chunked()
+    want = [p.grad.clone() for p in list(actor.parameters()) + list(critic.parameters())]
+    partial_finish()
+    torch.cuda.synchronize()
+    assert chunk >= n or learner._chunks[n][0] == chunk, learner._chunks
+    same = all(torch.equal(p.grad, w) for p, w in zip(list(actor.parameters()) + list(critic.parameters()), want))
+    eight = block.repeat(8, 1)
+    eight[:, 0] = 8 * n  # B: the eight local counts add up to it
+
+    def finish_8():
+        learner.finish_shards(eight)
+
+    loss = learner.finish_shards(eight)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(loss).all()), "the eight blocks must pass the header check"
+    fns = {"chunked": chunked, "partial_plus_finish_r1": partial_finish, "finish_r8": finish_8}
+    return fns, {"chunk": learner._chunks[n][0], "passes": (n + chunk - 1) // chunk, "r1_bits_equal_chunked": same,
+                 "scratch_MB": budget / 2 ** 20, "block_MB": block.numel() * 8 / 1e6}
+
+
+def sharded_main(args):
+    res = {"n_s": S, "n_a": A, "hidden": H, "window_s": WINDOW_S, "chunk": args.chunk, "sizes": {}}
+    for n in args.sizes:
+        fns, info = sharded_paths(n, args.chunk)
+        r = alternate(fns, args.windows)
+        r.update(info)
+        spread = lambda v: (v["max_ms"] - v["min_ms"]) / v["median_ms"]  # noqa: E731
+        r["spread"] = {k: spread(r[k]) for k in fns}
+        r["r1_over_chunked"] = r["partial_plus_finish_r1"]["median_ms"] / r["chunked"]["median_ms"]
+        r["finish_r8_over_chunked"] = r["finish_r8"]["median_ms"] / r["chunked"]["median_ms"]
+        res["sizes"][str(n)] = r
+        del fns
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sharded", action="store_true", help="time the chunked entry, partial + finish at R = 1 and finish at R = 8")
+    ap.add_argument("--chunk", type=int, default=65536, help="--sharded: samples per pass")
     ap.add_argument("--sizes", nargs="+", type=int, default=[102400, 524288])
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--fused", action="store_true", help="the tail as one mm_opt_step launch (fused_step=True)")
@@ -151,6 +223,8 @@ def main():
     ap.add_argument("--profile-run", action="store_true", help="a few calls of each path only: the run to put under rocprofv3")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3's *_kernel_stats.csv of a --profile-run at ONE size")
     args = ap.parse_args()
+    if args.sharded:
+        return sharded_main(args)
     res = {"n_s": S, "n_a": A, "hidden": H, "fused_step": args.fused, "window_s": WINDOW_S, "sizes": {}}
     for n in args.sizes:
         fns = paths(n, args.fused)
