@@ -413,6 +413,11 @@ class CLib(object):
         if self.has_opt_step:
             lib.mm_opt_step.argtypes = [C.POINTER(MMOptGroup), i32, vp]
             lib.mm_opt_step.restype = i32
+        # per-env cbf_eta / cbf_tau / HEADWAY_TIME planes (include/mm_env_params.h), also libmm_hip.so only
+        self.has_env_params = hasattr(lib, "mm_set_env_params")
+        if self.has_env_params:
+            lib.mm_set_env_params.argtypes = [vp, vp]
+            lib.mm_set_env_params.restype = i32
         if lib.mm_abi_version() != MM_ABI_VERSION:
             raise RuntimeError("ABI version mismatch in %s" % path)
 
@@ -443,6 +448,11 @@ class CLib(object):
         b = C.c_uint64()
         self.check(self.lib.mm_supervise_dmc_scratch_bytes(E, N, n_step, sub_steps, C.byref(b)))
         return b.value
+
+    def require_env_params(self):
+        if not self.has_env_params:
+            raise NotImplementedError("%s does not export mm_set_env_params: per-env cbf_eta / cbf_tau / HEADWAY_TIME need the "
+                                      "HIP library" % os.path.basename(self.path))
 
     def require_supervisor(self):
         if not self.has_supervisor:

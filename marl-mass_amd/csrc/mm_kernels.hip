@@ -32,6 +32,7 @@
 #define MM_COUNTS_FN __host__ __device__ inline
 #include "../../include/mm_counts.h"
 #include "../../include/mm_policy_wide.h"  // mm_policy_act forwards hidden = 512 to it
+#include "../../include/mm_env_params.h"
 
 using namespace mm;
 
@@ -44,6 +45,9 @@ struct DevCfg {
   int steer_vel;  // lateral_control == "steer_vel" (v1 CAVs; handled by the MIXED = general instantiations)
   int *err;       // device error latch of the handle (MM_LATCH_* bits), read by mm_poll_errors
   int traffic_density, mixed_traffic, num_cav;  // per-episode vehicle-count draw (MergeEnv._num_vehicles); 0 = fixed counts
+  // per-env eta / tau / headway_time (include/mm_env_params.h: [MM_ENVP_COUNT][E], the caller's) or NULL; read by the PENV
+  // instantiations of step_kernel only, which then read none of the three uniform values above
+  const double *envp;
 };
 // conditions the reference raises from inside step(); a launch can only latch them (include/mm_abi.h: mm_poll_errors)
 constexpr int kMetricsAccBit = 30;  // internal bit of DevCfg::debug_flags (set by dev_cfg, never by the caller): metrics partials accumulate
@@ -117,6 +121,7 @@ struct PoseBuf {
 //            cvxopt's interior-point algorithm, include/mm_qp.h), same flags as TU 2.
 //   MM_TU=4 / 5  only the exact-mode / the interior-point step kernels in the 6- / 12-lane rotation layouts (kPow2 below).
 //   MM_TU=8  only the reset / step kernels of merge-multi-agent-hdv-v1 (MM_ENV_HDV_V1: every vehicle an IDM / MOBIL HDV).
+//   MM_TU=9 / 10  only the exact-mode / the interior-point step kernels with per-env eta / tau / headway_time (PENV below).
 // MM_TU=0 (default) is the single-TU form used by the tuning / diagnostic builds.
 #ifndef MM_TU
 #define MM_TU 0
@@ -1645,6 +1650,21 @@ __global__ __launch_bounds__(64, 1) void sweep_kernel(DevCfg c, DevState st, Swe
 #ifndef MM_SPLIT_WAVES
 #define MM_SPLIT_WAVES 2  // phase form of the step kernel (split interior-point step): 168 registers (3 waves) spill 85 of them
 #endif
+// The configuration as a lane's env has it (step_kernel, PENV): c with the env's eta / tau / headway_time, loaded here, at the
+// use; lanes without an env (e >= E: the launch's round-up, the rotation layouts' tail) read the last env's, inside the planes.
+// Not PENV: c itself.
+template <bool PENV>
+MM_DEV std::conditional_t<PENV, DevCfg, const DevCfg &> env_cfg(const DevCfg &c, long long e, int E) {
+  if constexpr (PENV) {
+    const long long ep = e < E ? e : (long long)E - 1;
+    DevCfg l = c;
+    l.eta = c.envp[(long long)MM_ENVP_ETA * E + ep]; l.tau = c.envp[(long long)MM_ENVP_TAU * E + ep];
+    l.headway_time = c.envp[(long long)MM_ENVP_HEADWAY_TIME * E + ep];
+    return l;
+  } else {
+    return c;
+  }
+}
 template <int G, int SHIELD, bool MIXED>
 #ifndef MM_GENERAL_NONE_WAVES
 #define MM_GENERAL_NONE_WAVES 3  // mixed-traffic unshielded: 0.49 (2 waves) / 0.445 (3) / 0.51 ms (4)
@@ -1661,7 +1681,12 @@ constexpr int step_min_waves(bool ipm = false) { return SHIELD == MM_SHIELD_NONE
 // state from launch to launch; everything else a sub-step keeps in registers / LDS between its two halves goes through
 // the SweepBuf planes.  Same code as the fused form, statement for statement: only the shield sweep between the halves
 // is replaced by the hand-off.
-template <int G, int KIND, int SHIELD, bool MIXED, bool IPM = false, bool TRACE = false, bool SPLIT = false>
+// PENV: eta, tau and headway_time are the lane's env's (DevCfg::envp) instead of the launch's.  A lane loads them where the
+// uniform kernel reads c.eta / c.tau / c.headway_time -- shield_static, shield_post and the headway term of the agent reward, the
+// same expressions -- and nowhere else: these kernels sit at their register limit, and a value held across the sub-steps
+// costs two VGPRs where a load at its use costs a cached read (three planes of E doubles, read by every lane of an env).
+// Shielded v1 kernels without TRACE / SPLIT only (translation units 9 and 10).
+template <int G, int KIND, int SHIELD, bool MIXED, bool IPM = false, bool TRACE = false, bool SPLIT = false, bool PENV = false>
 #ifndef MM_STEP_BLOCK
 #define MM_STEP_BLOCK 64  // one wave per workgroup: waves of a 256-thread block drifted ~12 % apart and the block held its LDS until the slowest was done (0.355 -> 0.333 ms)
 #endif
@@ -1674,6 +1699,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   constexpr bool MASS = (SHIELD == MM_SHIELD_MASS);
   static_assert(!IPM || SHIELDED, "the IPM mode lives in shielded kernels");
   static_assert(!SPLIT || IPM, "the split form exists for the interior-point kernels");
+  static_assert(!PENV || (SHIELDED && KIND == MM_ENV_V1 && !TRACE && !SPLIT), "per-env parameters: fused shielded v1 kernels without the trace");
   // Form of the shield sweep.  Every CAV-only shielded kernel (HSS and MASS) runs the parallel fixed-point form with the
   // literal front-to-back sweep compiled in as fallback (a vehicle moving backwards in x) and as the validation form
   // (debug_flags bit0); the general kernels (HDVs / steer_vel) and the MASS IPM kernels carry the literal sweep ONLY
@@ -2328,7 +2354,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           // ---- MASS: fixed point over the decided accelerations (HSS: one evaluation) ----------
           double acc_cur = shield_on ? 0.0 : v.act_acc;  // vehicles without a shield keep their command
           if constexpr (kRoomy) v.gvx = GVX();
-          const ShieldStatic ss = shield_static<MASS>(c, v, cpsi_now, kHBits ? pk_self & 0xFF : pk_self, nb);
+          const ShieldStatic ss = shield_static<MASS>(env_cfg<PENV>(c, e, st.E), v, cpsi_now, kHBits ? pk_self & 0xFF : pk_self, nb);
           if constexpr (IPM) {
             // ---- interior-point mode: ONE wave-wide loop, every lane at its own iteration of its own QP ----------------
             // A follower's QP reads the acceleration its leader / front-adjacent vehicle DECIDED this sub-step, so a QP can
@@ -2360,7 +2386,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               if (__any(done_now)) {
                 if (done_now) {
                   double us0 = ss.u0 + q.x0;
-                  if (MASS && slow_lc) us0 = shield_post<MASS>(c, v, ss, shield_rows<true>(c, ss, nb), q.x0, opt, true).us0;
+                  if (MASS && slow_lc) us0 = shield_post<MASS>(env_cfg<PENV>(c, e, st.E), v, ss, shield_rows<true>(c, ss, nb), q.x0, opt, true).us0;
                   acc_cur = div_c(us0 - ss.evx, dt, c.inv_dt);  // derived_acceleration :80-82 (== shield_post's)
                   fin = true;
                   qc_d = q.x0; qc_meta = (ss.cadj ? 4 : 3) | (opt ? 8 : 0);
@@ -2399,7 +2425,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               }
               more = any_run || __any(!fin);  // (nothing iterating but lanes not final: they waited for this trip's decisions)
             }
-            if (shield_on) so = shield_post<MASS>(c, v, ss, shield_rows<true>(c, ss, nb), qc_d, (qc_meta & 8) != 0, true);
+            if (shield_on) so = shield_post<MASS>(env_cfg<PENV>(c, e, st.E), v, ss, shield_rows<true>(c, ss, nb), qc_d, (qc_meta & 8) != 0, true);
           } else {
           if constexpr (MASS && kRoundsLite) {
             // The rounds need the decided ACCELERATION only: rows, the QP and derived_acceleration.  Status, is_lc_allowed, veto and
@@ -2446,7 +2472,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               d_cur = qp_exact(ss, rr);
               double acc_next = v.act_acc;
               if (shield_on) {
-                if (slow_lc) acc_next = shield_post<true>(c, v, ss, rr, d_cur, true, false).acc;
+                if (slow_lc) acc_next = shield_post<true>(env_cfg<PENV>(c, e, st.E), v, ss, rr, d_cur, true, false).acc;
                 else acc_next = div_c((ss.u0 + d_cur) - ss.evx, dt, c.inv_dt);  // derived_acceleration :80-82 (shield_post's expression)
               }
               const bool changed = __double_as_longlong(acc_next) != __double_as_longlong(acc_cur);
@@ -2456,7 +2482,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               // profiles/r04/variants.jsonl; rounds per pass: profiles/rounds_prior/)
               if (!__any(changed)) break;
             }
-            so = shield_post<true>(c, v, ss, rr, d_cur, true, false);
+            so = shield_post<true>(env_cfg<PENV>(c, e, st.E), v, ss, rr, d_cur, true, false);
             STAMP(MM_CS_ROUND_CYCLES);  // the round loop alone
           } else {
           for (int round = 0; round <= st.N; round++) {
@@ -2466,7 +2492,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               if (ol_dyn) nb.ol_gu = da;
               if (oa_dyn) nb.oa_gu = db;
             }
-            so = shield_dyn<MASS, true, false>(c, v, ss, nb, shield_on);
+            so = shield_dyn<MASS, true, false>(env_cfg<PENV>(c, e, st.E), v, ss, nb, shield_on);
             const double acc_next = shield_on ? so.acc : v.act_acc;
             const bool changed = __double_as_longlong(acc_next) != __double_as_longlong(acc_cur);
             acc_cur = acc_next;
@@ -2612,7 +2638,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           // (absent slots contribute g*u = 0, an obstacle +0: handled in shield_dyn<.., PRE> / obstacle_override)
           obstacle_override<MASS>(nb, v.x, v.y);
           const bool mine = has && a == ai && shield_on;  // this stage's ego
-          ShieldOut s1 = shield_eval<MASS, true, IPM>(c, v, cpsi, kHBits ? pk_self & 0xFF : pk_self, nb, mine);
+          ShieldOut s1 = shield_eval<MASS, true, IPM>(env_cfg<PENV>(c, e, st.E), v, cpsi, kHBits ? pk_self & 0xFF : pk_self, nb, mine);
           if (hss_collab) s1.flags |= MM_FLAG_IS_COLLABORATING;  // vehicle.is_collaborating = cbf.constrain_adj
           if (IPM && mine && s1.bounds) atomicOr(c.err, MM_LATCH_QP_BOUNDS);
           if (mine) {
@@ -2863,7 +2889,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
       double t = v.x - 420;
       merging = -mmm_exp(MM_DIVC(-(t * t), 1000.0));
     }
-    double hc = v.v > 0 ? mmm_log(hd / (c.headway_time * v.v)) : 0;
+    double hc = v.v > 0 ? mmm_log(hd / (env_cfg<PENV>(c, e, st.E).headway_time * v.v)) : 0;
     if (xrew) hc = -1 * hc;  // srew / mrew flip the sign of the headway term (:465-466)
     local = c.collision_reward * (-1 * v.crashed) + (c.high_speed_reward * clipd(scaled, 0, 1)) +
             c.merging_lane_cost * merging + c.headway_cost * (hc < 0 ? hc : 0);
@@ -3325,8 +3351,11 @@ struct MMHandle_ : MMHandleHead {  // cfg, E, N, device, state, lay, first_env: 
   PoseBuf pose;
   void *pose_mem;
   int n_simd;  // SIMDs of the handle's device (4 per CU), read at mm_create
+  const double *envp;  // mm_set_env_params: the caller's [MM_ENVP_COUNT][E] planes, or NULL
   char err[256];
 };
+// what the per-env planes exist for: the shielded v1 step (include/mm_env_params.h)
+static bool envp_scope(const MMConfig *c) { return c->env_kind == MM_ENV_V1 && (c->shield == MM_SHIELD_HSS || c->shield == MM_SHIELD_MASS); }
 static bool needs_general(const MMHandle_ *h) {  // HDVs can appear, or steer_vel lateral control: the kernels that carry IDM / MOBIL
   return h->cfg.env_kind == MM_ENV_HDV_V1 || h->cfg.n_hdv > 0 || (h->cfg.traffic_density > 0 && h->cfg.mixed_traffic != 0) ||
          (h->cfg.env_kind == MM_ENV_V1 && h->cfg.lateral_control == MM_LATERAL_STEER_VEL);
@@ -3341,6 +3370,7 @@ static bool needs_general(const MMHandle_ *h) {  // HDVs can appear, or steer_ve
 // (validation / A-B timing: same results either way).
 static bool steps_split(const MMHandle_ *h) {
   if (!(h->cfg.env_kind == MM_ENV_V1 && h->cfg.shield != MM_SHIELD_NONE && h->cfg.qp_solver == MM_QP_IPM)) return false;
+  if (h->envp) return false;  // per-env parameters: the sweep kernel reads the uniform values, the fused kernel steps such a batch
   if (h->cfg.debug_flags & 4) return false;
   if (h->cfg.debug_flags & 8) return true;
   const int g = h->N <= 2 ? 2 : (h->N <= 4 ? 4 : (h->N <= 8 ? 8 : 16));
@@ -3588,6 +3618,11 @@ extern "C" int32_t mm_set_config(MMHandle h, const MMConfig *cfg) {
   if (!h) return MM_ERR_INVALID_ARG;
   int rc = check_cfg(cfg, h->N, h->err);
   if (rc != MM_OK) return rc;
+  if (h->envp && !envp_scope(cfg)) {
+    snprintf(h->err, sizeof h->err, "mm_set_config: per-env parameters are set (mm_set_env_params) and exist for merge-multi-agent-v1 with the "
+             "HSS or MASS shield only (env_kind %d, shield %d); clear them first", cfg->env_kind, cfg->shield);
+    return MM_ERR_INVALID_ARG;
+  }
   h->cfg = *cfg;
   DeviceGuard dg(h->device);  // (the new configuration may step in the split form: its hand-off planes are allocated here)
   hipError_t hrc = dg.rc;
@@ -3595,6 +3630,20 @@ extern "C" int32_t mm_set_config(MMHandle h, const MMConfig *cfg) {
   if (hrc != hipSuccess) return hip_fail(h, hrc, "hand-off planes of the split interior-point step");
   hrc = ensure_pose(h);
   return hrc == hipSuccess ? MM_OK : hip_fail(h, hrc, "carried pose planes");
+}
+extern "C" int32_t mm_set_env_params(MMHandle h, const double *params) {  // include/mm_env_params.h
+  if (!h) return MM_ERR_INVALID_ARG;
+  if (params && !envp_scope(&h->cfg)) {
+    snprintf(h->err, sizeof h->err, "mm_set_env_params: per-env cbf_eta / cbf_tau / HEADWAY_TIME exist for merge-multi-agent-v1 with the "
+             "HSS or MASS shield only (env_kind %d, shield %d)", h->cfg.env_kind, h->cfg.shield);
+    return MM_ERR_INVALID_ARG;
+  }
+  h->envp = params;
+  if (params) return MM_OK;
+  DeviceGuard dg(h->device);  // (off: the configuration may step in the split form again, whose planes are allocated outside mm_step)
+  hipError_t hrc = dg.rc;
+  if (hrc == hipSuccess) hrc = ensure_sweep(h);
+  return hrc == hipSuccess ? MM_OK : hip_fail(h, hrc, "hand-off planes of the split interior-point step");
 }
 extern "C" int32_t mm_set_metrics_buffer(MMHandle h, double *metrics) {
   if (!h) return MM_ERR_INVALID_ARG;
@@ -3638,6 +3687,7 @@ static DevCfg dev_cfg(const MMHandle h) {
   d.steer_vel = (c.env_kind == MM_ENV_V1 && c.lateral_control == MM_LATERAL_STEER_VEL) ? 1 : 0;
   d.err = h->dev_err + MM_LW_STEP;
   d.traffic_density = c.traffic_density; d.mixed_traffic = c.mixed_traffic; d.num_cav = c.num_cav;
+  d.envp = h->envp;
   return d;
 }
 static DevState dev_state(const MMHandle h) {
@@ -3715,6 +3765,50 @@ static void launch_step_t(MMHandle h, const int32_t *actions, const MMStepOut *o
     hipLaunchKernelGGL((step_kernel<G, KIND, SHIELD, MIXED, IPM, false>), dim3(grid), dim3(MM_STEP_BLOCK), 0, s, dev_cfg(h), dev_state(h),
                        actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0, h->pose);
 }
+// Per-env parameters (include/mm_env_params.h): the PENV instantiations of the fused kernel, shielded v1 without the trace, in
+// translation units of their own -- MM_TU=9 the exact-mode kernels (mm_penv.o), MM_TU=10 the interior-point ones (mm_penv_ipm.o) --
+// for every layout step_group() picks, CAV-only and general.
+#if MM_TU == 0 || MM_TU == 9 || MM_TU == 10
+template <int G, int SHIELD, bool MIXED, bool IPM>
+static void launch_step_penv_t(MMHandle h, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
+  const long long threads = (long long)h->E * G;
+  const unsigned grid = kPow2<G> ? (unsigned)((threads + MM_STEP_BLOCK - 1) / MM_STEP_BLOCK)
+                                 : (unsigned)((h->E + 64 / G - 1) / (64 / G));  // rotation layouts: 64 / G whole groups per wave
+  hipLaunchKernelGGL((step_kernel<G, MM_ENV_V1, SHIELD, MIXED, IPM, false, false, true>), dim3(grid), dim3(MM_STEP_BLOCK), 0, s, dev_cfg(h),
+                     dev_state(h), actions, *out, h->metrics ? h->metrics_partial : nullptr, h->sweep, 0, h->pose);
+}
+template <bool IPM>
+static void launch_step_penv_all(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
+  const bool mass = h->cfg.shield == MM_SHIELD_MASS, general = needs_general(h);
+  switch (g) {
+#define MM_PENV_CASE(GG) case GG: \
+      if (mass) { if (general) launch_step_penv_t<GG, MM_SHIELD_MASS, true, IPM>(h, actions, out, s); else launch_step_penv_t<GG, MM_SHIELD_MASS, false, IPM>(h, actions, out, s); } \
+      else { if (general) launch_step_penv_t<GG, MM_SHIELD_HSS, true, IPM>(h, actions, out, s); else launch_step_penv_t<GG, MM_SHIELD_HSS, false, IPM>(h, actions, out, s); } \
+      break;
+#ifdef MM_ONLY_G
+    MM_PENV_CASE(MM_ONLY_G)
+#else
+    MM_PENV_CASE(2) MM_PENV_CASE(4) MM_PENV_CASE(6) MM_PENV_CASE(8) MM_PENV_CASE(12) MM_PENV_CASE(16)
+#endif
+#undef MM_PENV_CASE
+    default: break;
+  }
+}
+#endif
+#if MM_TU == 10
+void mm_launch_step_penv_ipm(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s) { launch_step_penv_all<true>(h, g, actions, out, s); }
+#elif MM_TU == 9
+void mm_launch_step_penv_ipm(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s);
+void mm_launch_step_penv(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
+  if (h->cfg.qp_solver == MM_QP_IPM) mm_launch_step_penv_ipm(h, g, actions, out, s);
+  else launch_step_penv_all<false>(h, g, actions, out, s);
+}
+#elif MM_TU == 0  // single-TU tuning build
+static void mm_launch_step_penv(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
+  if (h->cfg.qp_solver == MM_QP_IPM) launch_step_penv_all<true>(h, g, actions, out, s);
+  else launch_step_penv_all<false>(h, g, actions, out, s);
+}
+#endif
 #if MM_TU == 0 || MM_TU == 6 || MM_TU == 7
 // The split interior-point step (SweepBuf, sweep_kernel): nsub + 1 phase launches with a sweep launch after each act half.
 // All on the caller's stream: each launch reads what the previous one wrote.  (MIXED: the general kernels -- HDVs / steer_vel.)
@@ -3808,6 +3902,7 @@ void mm_launch_step_ipm(MMHandle h, const int32_t *actions, const MMStepOut *out
 void mm_launch_step_lanes(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s);
 void mm_launch_step_lanes_ipm(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s);
 void mm_launch_step_split(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s);
+void mm_launch_step_penv(MMHandle h, int g, const int32_t *actions, const MMStepOut *out, hipStream_t s);
 #endif
 #if MM_TU == 0 || MM_TU == 5
 #if MM_TU == 0
@@ -3858,7 +3953,7 @@ void mm_launch_step_idm(MMHandle h, int g, const MMStepOut *out, hipStream_t s) 
   }
 }
 #endif
-#if MM_TU == 4 || MM_TU == 5 || MM_TU == 6 || MM_TU == 7 || MM_TU == 8
+#if MM_TU == 4 || MM_TU == 5 || MM_TU == 6 || MM_TU == 7 || MM_TU == 8 || MM_TU == 9 || MM_TU == 10
 #elif MM_TU == 2
 void mm_launch_step_general(MMHandle h, const int32_t *actions, const MMStepOut *out, hipStream_t s) {
   switch (group_size(h->N)) {
@@ -3907,6 +4002,10 @@ static void launch_step_g(MMHandle h, const int32_t *actions, const MMStepOut *o
 extern "C" int32_t mm_step(MMHandle h, const int32_t *actions, const MMStepOut *out, MMStream stream) {
   if (!h || !out || (!actions && h->cfg.env_kind != MM_ENV_HDV_V1)) return MM_ERR_INVALID_ARG;  // (hdv-v1: step(None))
   hipStream_t s = (hipStream_t)stream;
+  if (h->envp && out->trace) {  // (the trace-carrying kernels read the uniform values: refused, never a quiet fall-back)
+    snprintf(h->err, sizeof h->err, "mm_step: no trace while per-env parameters are set (mm_set_env_params)");
+    return MM_ERR_INVALID_ARG;
+  }
   if (out->trace) {
     // NaN = "sub-step did not run"; 0xFF bytes are a NaN pattern
     hipError_t rc = hipMemsetAsync(out->trace, 0xFF, (size_t)3 * MM_T_COUNT * h->E * h->N * sizeof(double), s);
@@ -3920,6 +4019,8 @@ extern "C" int32_t mm_step(MMHandle h, const int32_t *actions, const MMStepOut *
   } else if (carries_pose(h) && !h->pose_mem) {
     snprintf(h->err, sizeof h->err, "mm_step: the carried pose planes are missing");
     return MM_ERR_DEVICE;
+  } else if (h->envp) {  // per-env eta / tau / headway_time: the PENV kernels (mm_penv.o, mm_penv_ipm.o), fused at every batch size
+    mm_launch_step_penv(h, step_group(h), actions, out, s);
   } else
 #ifdef MM_ONLY_G  // tuning builds: one group size, seconds to compile
   launch_step_g<MM_ONLY_G>(h, actions, out, s);
@@ -3962,6 +4063,10 @@ static void launch_shield_g(MMHandle h, const double *as, const double *aa, doub
 extern "C" int32_t mm_shield_actions(MMHandle h, const double *act_steer, const double *act_acc, double *safe_steer,
                                      double *safe_acc, uint8_t *status, double *margin, double *headway, MMStream stream) {
   if (!h || !act_steer || !act_acc || !safe_steer || !safe_acc) return MM_ERR_INVALID_ARG;
+  if (h->envp) {  // (the stand-alone shield kernel reads the uniform values: refused, never a quiet fall-back)
+    snprintf(h->err, sizeof h->err, "mm_shield_actions: not available while per-env parameters are set (mm_set_env_params)");
+    return MM_ERR_INVALID_ARG;
+  }
   hipStream_t s = (hipStream_t)stream;
 #ifdef MM_ONLY_G
   launch_shield_g<MM_ONLY_G>(h, act_steer, act_acc, safe_steer, safe_acc, status, margin, headway, s);

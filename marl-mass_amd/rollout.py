@@ -405,6 +405,27 @@ class DeviceRollout(object):
             self._sample_counter.copy_(saved_counter)
 
 
+def group_ext_info(ext_info, groups, n_groups=None):
+    """Per-group means of evaluate()'s per-env results, for a batch whose envs fall into groups -- the points of a per-env
+    cbf_eta / cbf_tau / HEADWAY_TIME grid (VecMergeEnv(env_params=...)), each with several seeds.
+
+    ext_info: evaluate()'s dict; groups: int [E], the group index of every env (0 .. n_groups - 1; n_groups defaults to
+    max + 1).  Returns {"count": int64 [G], "steps", "avg_speeds", "crash_rate", "traffic_speeds", "merge_percents": float64 [G]}
+    on the device of the inputs: the mean over the group's envs (crash_rate: the fraction of its episodes that ended with a
+    crashed vehicle), NaN for a group without envs."""
+    groups = torch.as_tensor(groups, device=ext_info["steps"].device).long().flatten()
+    G = int(groups.max()) + 1 if n_groups is None else int(n_groups)
+    if groups.numel() != ext_info["steps"].numel() or int(groups.min()) < 0 or int(groups.max()) >= G:
+        raise ValueError("groups must hold one index in 0..%d per env" % (G - 1))
+    count = torch.zeros(G, dtype=torch.int64, device=groups.device).index_add_(0, groups, torch.ones_like(groups))
+    out = {"count": count}
+    for key, src in (("steps", "steps"), ("avg_speeds", "avg_speeds"), ("crash_rate", "crash_count"),
+                     ("traffic_speeds", "traffic_speeds"), ("merge_percents", "merge_percents")):
+        v = ext_info[src].to(torch.float64).flatten()
+        out[key] = torch.zeros(G, dtype=torch.float64, device=groups.device).index_add_(0, groups, v) / count  # (0 / 0: NaN)
+    return out
+
+
 def idm_evaluation(env, seeds):
     """eval_idm.py:70-160 (idm_evaluation of merge-multi-agent-hdv-v1) for a batch of episodes at once.
 

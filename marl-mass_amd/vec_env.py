@@ -22,6 +22,34 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.environ.get("MM_HIP_LIB") or os.path.join(_HERE, "csrc", "libmm_hip.so")
 
 
+# per-env shield parameters (include/mm_env_params.h): plane order of the [3, E] tensor and the MMConfig field each one replaces
+ENV_PARAM_KEYS = ("cbf_eta", "cbf_tau", "HEADWAY_TIME")
+_ENV_PARAM_FIELDS = ("cbf_eta", "cbf_tau", "headway_time")
+
+
+def env_param_planes(params, E, cfg):
+    """{"cbf_eta" | "cbf_tau" | "HEADWAY_TIME": scalar or [E]} -> float64 [3, E] on the host, missing keys filled from the
+    MMConfig `cfg`.  ValueError: a config that is not merge-multi-agent-v1 with the HSS or MASS shield, an unknown key, a
+    shape other than scalar / [E], a value that is not finite, cbf_tau <= 0 or HEADWAY_TIME <= 0."""
+    if not (cfg.env_kind == abi.ENV_V1 and cfg.shield in (abi.SHIELD_HSS, abi.SHIELD_MASS)):
+        raise ValueError("per-env cbf_eta / cbf_tau / HEADWAY_TIME exist for merge-multi-agent-v1 with a cbf-avs_cint (HSS) or "
+                         "cbf-cav (MASS) shield only")
+    unknown = sorted(set(params) - set(ENV_PARAM_KEYS))
+    if unknown:
+        raise ValueError("unknown env_params key(s) %r: expected some of %r" % (unknown, ENV_PARAM_KEYS))
+    planes = torch.empty(len(ENV_PARAM_KEYS), int(E), dtype=torch.float64)
+    for p, (key, field) in enumerate(zip(ENV_PARAM_KEYS, _ENV_PARAM_FIELDS)):
+        v = torch.as_tensor(params[key] if key in params else getattr(cfg, field), dtype=torch.float64).cpu()
+        if v.dim() > 1 or (v.dim() == 1 and v.numel() != E):
+            raise ValueError("env_params[%r] must be a scalar or have shape [%d], got %s" % (key, E, tuple(v.shape)))
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("env_params[%r] must be finite" % key)
+        if key != "cbf_eta" and not bool((v > 0).all()):
+            raise ValueError("env_params[%r] must be > 0" % key)
+        planes[p] = v
+    return planes
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -32,8 +60,12 @@ class BatchedMergeEnv(object):
     def __init__(self, clib, E, N, env_id="merge-multi-agent-v1", config=None, device="cpu",
                  cbf_eta=0.0, cbf_tau=None, auto_reset=False, obs_f64=False, seed=0, first_env=0,
                  trace=False, debug_flags=0, n_hdv=0, qp_solver="ipm", draw_counts=False, num_cav=0, skip_outputs=(),
-                 enable_dmc=False):
+                 enable_dmc=False, env_params=None):
         self.clib, self.E, self.N = clib, int(E), int(N)
+        # env_params: per-env cbf_eta / cbf_tau / HEADWAY_TIME (set_env_params below); the HIP library only
+        self.env_params = None
+        if env_params is not None:
+            clib.require_env_params()
         # enable_dmc: config["safety_guarantee"] = "dmc" on merge-multi-agent-v0 runs the device's safety_layer_dmc
         # (mm_supervise_dmc).  Off by default: a plain "dmc" config still raises NotImplementedError from step(), as it always
         # has; making it the behaviour of the plain setting is a later change.
@@ -111,6 +143,39 @@ class BatchedMergeEnv(object):
         clib.check(clib.lib.mm_create(C.byref(self._cfg), self.E, self.N, index or 0,
                                       _ptr(self.state), lay.total_bytes, int(first_env),
                                       C.byref(self._h)))
+        if env_params is not None:
+            self.set_env_params(**env_params)
+
+    # -- per-env shield parameters (include/mm_env_params.h) ------------------------------------
+    _ENVP_GUARD = 32  # doubles behind the planes that nothing may write (NaN pattern; the tests read them back)
+
+    def set_env_params(self, **planes):
+        """Give every env its own cbf_eta / cbf_tau / HEADWAY_TIME: each a scalar or [E]; keys not given keep the planes'
+        current values, or the config's when no planes are set yet.  merge-multi-agent-v1 with an HSS or MASS shield on the
+        HIP library only.  self.env_params is then the float64 [3, E] device tensor the steps read (ENV_PARAM_KEYS order):
+        writing into it takes effect at the next step, also inside a captured rollout graph.  While set, a large
+        interior-point batch steps in the fused kernel instead of the split form, and trace / shield_actions() raise."""
+        self.clib.require_env_params()
+        if self.env_params is not None:
+            cur = self.env_params.cpu()
+            planes = dict({k: cur[p] for p, k in enumerate(ENV_PARAM_KEYS)}, **planes)
+        host = env_param_planes(planes, self.E, self._cfg)
+        if self.env_params is None:
+            n = host.numel()
+            raw = torch.full((n + self._ENVP_GUARD,), float("nan"), dtype=torch.float64, device=self.device)
+            raw[:n] = host.reshape(-1).to(self.device)
+            self.clib.check(self.clib.lib.mm_set_env_params(self._h, _ptr(raw)), self._h)
+            self._env_params_raw = raw
+            self.env_params = raw[:n].view(len(ENV_PARAM_KEYS), self.E)
+        else:
+            self.env_params.copy_(host.to(self.device))
+        return self.env_params
+
+    def clear_env_params(self):
+        """Back to the config's uniform cbf_eta / cbf_tau / HEADWAY_TIME."""
+        if self.env_params is not None:
+            self.clib.check(self.clib.lib.mm_set_env_params(self._h, None), self._h)
+            self.env_params = self._env_params_raw = None
 
     # -- safety supervisor (safety_guarantee = "priority", include/mm_supervisor.h) ------------
     def _setup_supervisor(self):
@@ -304,6 +369,8 @@ class BatchedMergeEnv(object):
              "state": self.state.clone(), "obs": self.obs.clone(), "avail": self.avail.clone()}
         if self.metrics is not None:
             d["metrics"] = self.flush_metrics().clone()  # (deferred metrics: what the partials hold belongs to the snapshot)
+        if self.env_params is not None:  # (only when set: a dict without the key is what an env without planes writes and reads)
+            d["env_params"] = self.env_params.clone()
         return d
 
     def load_state_dict(self, d):
@@ -315,6 +382,8 @@ class BatchedMergeEnv(object):
         if "metrics" in d and self.metrics is not None:
             self.flush_metrics()  # (pending deferred sums belong to the state that is being replaced)
             self.metrics.copy_(d["metrics"].to(self.device))
+        if "env_params" in d:  # (a dict without the key leaves this env's planes, or their absence, as they are)
+            self.set_env_params(**{k: d["env_params"][p] for p, k in enumerate(ENV_PARAM_KEYS)})
 
     def enable_metrics(self, deferred=False):
         """Device-side rollout metric accumulator: 7 sums + 1 min.
