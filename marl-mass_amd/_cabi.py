@@ -88,6 +88,9 @@ class MMMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in MLP_PARAMS]
 
 
+BANK_MAX_GROUPS = 64  # MM_BANK_MAX_GROUPS (include/mm_policy_bank.h): members of one mm_policy_bank_act launch
+
+
 OPT_RMSPROP, OPT_ADAM, OPT_BLEND = 0, 1, 2  # MM_OPT_* (include/mm_opt_step.h)
 OPT_MAX_TENSORS, OPT_MAX_GROUPS = 16, 4
 
@@ -322,6 +325,14 @@ class CLib(object):
         if self.has_policy_wide:
             lib.mm_policy_wide_act.argtypes = list(lib.mm_policy_act.argtypes)
             lib.mm_policy_wide_act.restype = i32
+        # K hidden-128 actors on the K contiguous groups of one batch + sample in one launch (include/mm_policy_bank.h), also
+        # libmm_hip.so only; mm_policy_bank_grid is its host-side grid split
+        self.has_policy_bank = hasattr(lib, "mm_policy_bank_act") and hasattr(lib, "mm_policy_bank_grid")
+        if self.has_policy_bank:
+            lib.mm_policy_bank_act.argtypes = [vp, i64, i32, C.POINTER(MMMlpParams), i32, C.POINTER(i64), i32, i32, u64, vp, vp, vp, vp]
+            lib.mm_policy_bank_act.restype = i32
+            lib.mm_policy_bank_grid.argtypes = [i32, C.POINTER(i64), C.POINTER(i32)]
+            lib.mm_policy_bank_grid.restype = i32
         # the shared actor-critic's loss + parameter gradient (include/mm_policy_gi_train.h), also libmm_hip.so only
         self.has_policy_gi_train = hasattr(lib, "mm_policy_gi_train")
         if self.has_policy_gi_train:
@@ -467,6 +478,11 @@ class CLib(object):
     def require_policy_wide(self):
         if not self.has_policy_wide:
             raise NotImplementedError("%s does not export mm_policy_wide_act: the fused hidden-512 actor needs the HIP library"
+                                      % os.path.basename(self.path))
+
+    def require_policy_bank(self):
+        if not self.has_policy_bank:
+            raise NotImplementedError("%s does not export mm_policy_bank_act: the one-launch policy bank needs the HIP library"
                                       % os.path.basename(self.path))
 
     def require_policy_gi_train(self):

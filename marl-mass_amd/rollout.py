@@ -21,6 +21,10 @@ steer_vel configurations, 512: both have a fused act launch on the device;
 critic takes the one-hot action after the first layer) and, for MAPPO_GI with shared_network = True,
 marl/single_agent/Model_gi.py:137-216 (ActorCriticNetwork: split first layer, shared trunk, actor and
 critic heads; fused on the device as `mm_policy_gi_act`, include/mm_policy_gi.h).
+
+Bank mode: the reference trains one model per configuration and seed; a list of K actors with `group_envs` drives the K
+contiguous env groups of one batch, hidden-128 ActorNetworks in ONE launch (`mm_policy_bank_act`, include/mm_policy_bank.h,
+on the stacked copies a `PolicyBank` keeps).
 """
 import torch
 from torch import nn
@@ -128,16 +132,68 @@ def discount_rewards(rewards, dones, final_value, gamma):
     return out
 
 
+class PolicyBank(object):
+    """K ActorNetworks of one shape as six stacked float32 tensors, the operand of mm_policy_bank_act
+    (include/mm_policy_bank.h): W1 [K, H, n_s], b1 [K, H], W2 [K, H, H], b2 [K, H], W3 [K, n_a, H], b3 [K, n_a], on the
+    members' device.  The stack is a COPY of the members' parameters: refresh() brings it up to date in place (the addresses
+    never change, so a captured graph that reads the stack sees what the last refresh() wrote)."""
+
+    NAMES = ("W1", "b1", "W2", "b2", "W3", "b3")
+
+    def __init__(self, actors):
+        self.actors = list(actors)
+        if not self.actors:
+            raise ValueError("a policy bank needs at least one member")
+        if len(self.actors) > abi.BANK_MAX_GROUPS:
+            raise ValueError("a policy bank has at most %d members, got %d" % (abi.BANK_MAX_GROUPS, len(self.actors)))
+        shapes = [tuple(tuple(p.shape) for p in self._params(a)) for a in self.actors]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("the members of a policy bank must have one shape, got %s" % sorted(set(shapes)))
+        first = self._params(self.actors[0])
+        self.K, self.hidden = len(self.actors), first[2].shape[0]
+        self.n_s, self.n_a = first[0].shape[1], first[4].shape[0]
+        dev = first[0].device
+        self.tensors = [torch.empty((self.K,) + tuple(p.shape), dtype=torch.float32, device=dev) for p in first]
+        for name, t in zip(self.NAMES, self.tensors):
+            setattr(self, name, t)
+        self.params = abi.MMMlpParams(*[t.data_ptr() for t in self.tensors])
+        self.refresh()
+
+    @staticmethod
+    def _params(a):
+        return (a.fc1.weight, a.fc1.bias, a.fc2.weight, a.fc2.bias, a.fc3.weight, a.fc3.bias)
+
+    @torch.no_grad()
+    def refresh(self):
+        """Copies every member's current parameters into the stack, in place: one launch per stacked tensor."""
+        for j, t in enumerate(self.tensors):
+            torch.stack([self._params(a)[j].detach().to(t.dtype) for a in self.actors], out=t)
+
+
 class DeviceRollout(object):
-    """MAPPO.interact for a whole env batch; see the module docstring."""
+    """MAPPO.interact for a whole env batch; see the module docstring.
+
+    Bank mode: `actor` a list of K modules (and `critic` None or a list of K critics), `group_envs` the K env counts of the
+    contiguous blocks of envs, in env order, that each member drives (they sum to env.E; zeros are allowed) -- the layout of a
+    group-major env_params grid, or of K independent training runs stepped as one batch.  act() is then ONE
+    mm_policy_bank_act launch when every member is an ActorNetwork of hidden 128 in float32 on the device, `generator` is
+    None, `fused_policy` is on and the library has the entry; otherwise each member's forward writes its slice of one
+    log-probability buffer and ONE mm_sample_actions draws for the whole batch (given the same rows, the same draws).
+    `group_index` ([E], for group_ext_info) and group_slice(k) (of the E axis: batch["states"][:, roll.group_slice(k)]) say
+    which env belongs to whom."""
 
     def __init__(self, env, actor, critic=None, roll_out_n_steps=100, reward_gamma=0.99, reward_scale=20.0,
-                 reward_type="regionalR", generator=None, use_graph=False, sample_seed=0, fused_policy=True):
+                 reward_type="regionalR", generator=None, use_graph=False, sample_seed=0, fused_policy=True, group_envs=None):
         assert reward_type in ("regionalR", "global_R")  # marl/mappo.py:39
+        self.bank_mode, self.bank = isinstance(actor, (list, tuple)), None
+        if self.bank_mode:
+            actor, critic = self._init_bank(env, list(actor), critic, group_envs)
+        elif group_envs is not None:
+            raise ValueError("group_envs belongs to bank mode: pass the members as a list")
         # shared mode (MAPPO_GI, shared_network = True): one ActorCriticNetwork is the actor (out_type "p") and the
         # critic (out_type "v"); pass it as `actor`, with critic None or the same module
-        self.shared = isinstance(actor, ActorCriticNetwork)
-        if self.shared:
+        self.shared = isinstance(actor[0] if self.bank_mode else actor, ActorCriticNetwork)
+        if self.shared and not self.bank_mode:
             if critic is not None and critic is not actor:
                 raise ValueError("an ActorCriticNetwork is its own critic: pass critic=None or the same module")
             critic = None
@@ -150,8 +206,14 @@ class DeviceRollout(object):
         self.obs = self.obs.clone()
         # fused actor + sampling launch for the reference's ActorNetwork (hidden 128 or 512), and for its state-split
         # ActorCriticNetwork (hidden 128) on the device; anything else goes through the module's own forward
-        f32 = next(actor.parameters()).dtype == torch.float32
-        if self.shared:
+        f32 = all(next(a.parameters()).dtype == torch.float32 for a in (actor if self.bank_mode else [actor]))
+        if self.bank_mode:
+            # mm_policy_bank_act is a HIP-library entry at hidden 128; hidden 512, shared members and the CPU oracle take
+            # the members' own forwards
+            b = self.bank
+            self.fused_policy = bool(fused_policy) and b is not None and f32 and b.hidden == 128 and b.W1.device == self.obs.device \
+                and self.obs.device.type == "cuda" and env.clib.has_policy_bank
+        elif self.shared:
             # mm_policy_gi_act is a HIP-library entry (the CPU oracle has no twin: there the module is the CPU form)
             self.fused_policy = bool(fused_policy) and type(actor) is ActorCriticNetwork and actor.state_split and f32 \
                 and actor.fc2.weight.shape[0] == 128 and self.obs.device.type == "cuda"
@@ -171,6 +233,42 @@ class DeviceRollout(object):
             if generator is not None:
                 raise ValueError("use_graph samples from the default CUDA generator (captured Philox offset)")
         self._graph, self._static = None, None
+
+    def _init_bank(self, env, actors, critics, group_envs):
+        """Bank mode's argument checks and group tables; returns the member lists."""
+        K = len(actors)
+        if K < 1:
+            raise ValueError("bank mode needs at least one member")
+        kinds = {isinstance(a, ActorCriticNetwork) for a in actors}
+        if len(kinds) != 1:
+            raise ValueError("the members are either all ActorCriticNetworks (each its own critic) or none of them is")
+        if critics is not None:
+            if kinds == {True}:
+                raise ValueError("ActorCriticNetwork members are their own critics: pass critic=None")
+            if not isinstance(critics, (list, tuple)) or len(critics) != K:
+                raise ValueError("bank mode takes critic=None or one critic per member (%d)" % K)
+            critics = list(critics)
+        if group_envs is None or len(group_envs) != K:
+            raise ValueError("group_envs must hold one env count per member (%d)" % K)
+        group_envs = [int(e) for e in group_envs]
+        if min(group_envs) < 0 or sum(group_envs) != env.E:
+            raise ValueError("group_envs must be non-negative and sum to the batch's %d envs, got %s" % (env.E, group_envs))
+        # the fused launch's operand: ActorNetwork members only (a ValueError for more than 64 members or differing shapes)
+        self.bank = PolicyBank(actors) if all(type(a) is ActorNetwork for a in actors) else None
+        self.group_envs = group_envs
+        self._env_start = [sum(group_envs[:k]) for k in range(K + 1)]
+        self._group_start = (abi.C.c_int64 * (K + 1))(*[e * env.N for e in self._env_start])  # in agents, for the launch
+        self.group_index = torch.repeat_interleave(torch.arange(K), torch.tensor(group_envs)).to(env.device)
+        return actors, critics
+
+    def group_slice(self, k):
+        """The envs of member k, as a slice of the E axis."""
+        return slice(self._env_start[k], self._env_start[k + 1])
+
+    def _agent_slices(self, N):
+        """(k, slice of the flat [E * N] agent axis) of every non-empty group."""
+        return [(k, slice(self._env_start[k] * N, self._env_start[k + 1] * N)) for k in range(len(self.actor))
+                if self._env_start[k + 1] > self._env_start[k]]
 
     def state_dict(self):
         """Resume point of a rollout stream: env batch + carried observation + sampler counter."""
@@ -209,8 +307,25 @@ class DeviceRollout(object):
                                              self._sample_counter.data_ptr() if actions is not None else None, opt(actions),
                                              None, opt(value), self.env._stream()))
 
+    def _bank_logp(self, obs):
+        """Bank mode without the fused launch: each member's forward on its slice, into one [E*N, n_a] buffer."""
+        E, N, S = obs.shape
+        flat = obs.reshape(E * N, S).float()
+        logp = torch.empty(E * N, self.n_a, dtype=torch.float32, device=obs.device)
+        for k, s in self._agent_slices(N):
+            logp[s] = self.actor[k](flat[s])
+        return logp
+
     def _act(self, obs, dst):
         E, N, S = obs.shape
+        if self.bank_mode and self.generator is None and self.fused_policy and obs.dtype == torch.float32:
+            # every group's actor forward + sampling in ONE launch (mm_policy_bank_act on the stack bank.refresh() keeps)
+            b, clib = self.bank, self.env.clib
+            actions = dst if dst is not None else torch.empty(E * N, dtype=torch.int32, device=obs.device)
+            clib.check(clib.lib.mm_policy_bank_act(obs.contiguous().data_ptr(), E * N, S, abi.C.byref(b.params), b.K,
+                                                   self._group_start, b.hidden, self.n_a, self.sample_seed,
+                                                   self._sample_counter.data_ptr(), actions.data_ptr(), None, self.env._stream()))
+            return actions.view(E, N)
         if self.generator is None and self.fused_policy and self.shared and obs.dtype == torch.float32:
             # shared actor-critic forward + sampling in ONE launch (mm_policy_gi_act)
             actions = dst if dst is not None else torch.empty(E * N, dtype=torch.int32, device=obs.device)
@@ -226,7 +341,7 @@ class DeviceRollout(object):
                                               a.fc2.weight.shape[0], self.n_a, self.sample_seed,
                                               self._sample_counter.data_ptr(), actions.data_ptr(), None, self.env._stream()))
             return actions.view(E, N)
-        logp = self.actor(obs.reshape(E * N, S).float())
+        logp = self._bank_logp(obs) if self.bank_mode else self.actor(obs.reshape(E * N, S).float())
         # np.random.choice(n_a, p=softmax) (marl/mappo.py:229) is inverse-CDF sampling: cdf.searchsorted(u, "right").
         if self.generator is None:
             # fused in the library (mm_sample_actions): softmax -> cdf -> search, Philox uniform per agent, one
@@ -254,6 +369,8 @@ class DeviceRollout(object):
         Returns states [T,E,N,S], actions [T,E,N], discounted returns [T,E,N], dones [T,E] and the
         per-step info means the reference logs (average speed, min headway).  With `use_graph` the
         returned tensors are the graph's static buffers: consume them before the next call."""
+        if self.bank is not None:
+            self.bank.refresh()  # outside the capture: a replayed graph reads the stack this call has just updated
         if not self.use_graph:
             return self._interact()
         if self._graph is None:
@@ -307,7 +424,18 @@ class DeviceRollout(object):
         self.obs = obs.clone()
         # bootstrap value for envs still mid-episode (marl/mappo.py:147-150); 0 where the last step ended one
         final_value = torch.zeros(E, N, dtype=torch.float64, device=dev)
-        if self.shared:
+        if self.bank_mode:
+            # each group's own critic on its slice (the value path stays torch); the final actions are drawn as in act()
+            if self.shared or self.critic is not None:
+                fa = self.act(obs)
+                flat = obs.reshape(E * N, S).float()
+                one_hot = (fa.unsqueeze(-1) == torch.arange(self.n_a, device=dev, dtype=fa.dtype)).float().view(E * N, self.n_a)
+                val = torch.zeros(E * N, dtype=torch.float64, device=dev)
+                for k, s in self._agent_slices(N):
+                    v = self.actor[k](flat[s], out_type="v") if self.shared else self.critic[k](flat[s], one_hot[s])
+                    val[s] = v.view(-1).double()
+                final_value = torch.where(dones[-1].bool().unsqueeze(-1), final_value, val.view(E, N))
+        elif self.shared:
             # MAPPO_GI.action(final_state) then .value (marl/mappo_gi.py:371-395): the final actions are drawn (the stream
             # advances as in act()) but the shared critic does not read them
             if self.generator is None and self.fused_policy and obs.dtype == torch.float32:
@@ -350,6 +478,8 @@ class DeviceRollout(object):
         if missing:  # MAPPO.evaluation reads info["vehicle_speed"/"vehicle_position"] and env.is_crashed() (:300-330)
             raise ValueError("evaluate() needs the step outputs %s: this env was built with skip_outputs" % ", ".join(missing))
         was_auto = env.auto_reset
+        if self.bank is not None:
+            self.bank.refresh()
         # The reference evaluates on a SEPARATE env (env_eval, run_mappo.py:146-171,300-306) and its training env keeps
         # its own seed sequence and in-progress episode.  Here the batch is borrowed: snapshot everything an evaluation
         # touches (state planes, episode counters, per-env RNG seeds, carried observation) and put it back afterwards,
