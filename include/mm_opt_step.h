@@ -79,6 +79,22 @@ typedef struct MMOptGroup {        /* one network = one clipping group = one opt
  */
 int32_t mm_opt_step(const MMOptGroup *groups /* HOST */, int32_t n_groups /* 1..4 */, MMStream stream);
 
+/*
+ * The same tail for K stacked members per group, in ONE launch of n_groups * K workgroups (marl-mass_amd/csrc/
+ * mm_opt_step_bank.hip): the policy bank's optimiser step (include/mm_policy_bank_train.h).  Every group is a PROTOTYPE: tensor i
+ * of member k (param, grad, state1, state2, target alike) sits at the prototype's pointer + k * count[i] elements -- the stacked
+ * [K][...] storage of the bank -- `step` is DEV int32[K] and `grad_norm` an optional DEV float[K], member k's at index k.  The
+ * hyperparameters are shared by the members.  soft_mask: bit k says whether member k blends its target this call; the
+ * prototype's soft_update field is not looked at (an MM_OPT_BLEND prototype blends the members whose bit is set and leaves the
+ * others alone).  1 <= K <= 64 (MM_BANK_MAX_GROUPS); bits of soft_mask at and above K are ignored.
+ * The defining property: member k's parameters, state, targets, step and norm after the call are bit for bit what mm_opt_step
+ * gives on member k's tensors alone with soft_update = bit k.  Deterministic, only enqueues on `stream`: graph-capturable.
+ * MM_ERR_INVALID_ARG, with the reason in mm_last_error(NULL): K outside 1..64 and everything mm_opt_step refuses, a prototype
+ *   being checked as a group with soft_update = (some member blends).  Nothing is enqueued when any group is refused.
+ */
+int32_t mm_opt_step_bank(const MMOptGroup *groups /* HOST */, int32_t n_groups /* 1..4 */, int32_t K, uint64_t soft_mask,
+                         MMStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,10 @@ class MMMlpParams(C.Structure):
 
 
 BANK_MAX_GROUPS = 64  # MM_BANK_MAX_GROUPS (include/mm_policy_bank.h): members of one mm_policy_bank_act launch
+PT_FORM = {"reference": 0, "per_sample": 1}  # MM_PT_FORM_* (include/mm_policy_bank_train.h)
+# the scratch figures of mm_policy_bank_train_scratch_bytes (MM_PBT_*_BYTES): header, per member, per padded sample, per tile,
+# per partial block
+PBT_HEADER_BYTES, PBT_MEMBER_BYTES, PBT_SAMPLE_BYTES, PBT_TILE_BYTES, PBT_PARTIAL_BYTES = 1024, 131072, 2240, 32, 107584
 
 
 OPT_RMSPROP, OPT_ADAM, OPT_BLEND = 0, 1, 2  # MM_OPT_* (include/mm_opt_step.h)
@@ -424,6 +428,22 @@ class CLib(object):
         if self.has_opt_step:
             lib.mm_opt_step.argtypes = [C.POINTER(MMOptGroup), i32, vp]
             lib.mm_opt_step.restype = i32
+        # the policy bank's training half: K actor / critic pairs on the K column groups of one batch (include/
+        # mm_policy_bank_train.h) and the K optimiser tails (mm_opt_step_bank, include/mm_opt_step.h), also libmm_hip.so only
+        self.has_policy_bank_train = self.has_policy_train and self.has_opt_step and all(
+            hasattr(lib, s) for s in ("mm_policy_bank_eval", "mm_policy_bank_train", "mm_policy_bank_train_scratch_bytes",
+                                      "mm_opt_step_bank"))
+        if self.has_policy_bank_train:
+            f32, pp, pi64 = C.c_float, C.POINTER(MMMlpParams), C.POINTER(i64)
+            lib.mm_policy_bank_eval.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, pp, pp, i32, pi64, i32, i32, vp, vp, vp]
+            lib.mm_policy_bank_eval.restype = i32
+            lib.mm_policy_bank_train_scratch_bytes.argtypes = [i64, i64, i32, pi64, C.POINTER(u64)]
+            lib.mm_policy_bank_train_scratch_bytes.restype = i32
+            lib.mm_policy_bank_train.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, i64, vp, vp, pp, pp, i32, pi64, i32, i32, f32,
+                                                 i32, i32, vp, vp, pp, pp, vp, vp, vp, vp, vp, vp, u64, vp]
+            lib.mm_policy_bank_train.restype = i32
+            lib.mm_opt_step_bank.argtypes = [C.POINTER(MMOptGroup), i32, i32, u64, vp]
+            lib.mm_opt_step_bank.restype = i32
         # per-env cbf_eta / cbf_tau / HEADWAY_TIME planes (include/mm_env_params.h), also libmm_hip.so only
         self.has_env_params = hasattr(lib, "mm_set_env_params")
         if self.has_env_params:
@@ -595,6 +615,25 @@ class CLib(object):
         b = C.c_uint64()
         self.check(self.lib.mm_policy_wide_train_shard_bytes(C.byref(b)))
         return b.value // 8
+
+    def require_policy_bank_train(self):
+        if not self.has_policy_bank_train:
+            raise NotImplementedError("%s does not export mm_policy_bank_train: training the policy bank's members in one "
+                                      "launch set needs the HIP library" % os.path.basename(self.path))
+
+    def policy_bank_train_scratch_bytes(self, rows, row_len, col_start):
+        """Bytes of scratch mm_policy_bank_train needs (include/mm_policy_bank_train.h); col_start: the K + 1 column prefix."""
+        self.require_policy_bank_train()
+        b = C.c_uint64()
+        cs = (C.c_int64 * len(col_start))(*col_start)
+        self.check(self.lib.mm_policy_bank_train_scratch_bytes(rows, row_len, len(col_start) - 1, cs, C.byref(b)))
+        return b.value
+
+    def opt_step_bank(self, groups, K, soft_mask, stream):
+        """mm_opt_step_bank on a sequence of prototype MMOptGroup (include/mm_opt_step.h)."""
+        self.require_policy_bank_train()
+        arr = (MMOptGroup * len(groups))(*groups)
+        self.check(self.lib.mm_opt_step_bank(arr, len(groups), K, soft_mask, stream))
 
     def require_opt_step(self):
         if not self.has_opt_step:

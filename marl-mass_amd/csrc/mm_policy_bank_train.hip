@@ -1,0 +1,644 @@
+// mm_policy_bank_train.hip -- K actor / critic pairs of one shape, each on its own column group of one batch: the forward
+// evaluation (mm_policy_bank_eval) and the loss and full gradient (mm_policy_bank_train) of include/mm_policy_bank_train.h.
+//
+// The arithmetic is mm_policy_train.hip's, from the pieces of mm_policy_mfma.h, and the decomposition of every group is
+// mm_policy_train's on that group's n_k samples; what differs is where a tile's inputs and scratch rows live and whose weights
+// a workgroup stages.  The per-tile body of kernel A is written out here rather than shared with policy_train_sample_kernel:
+// that kernel sits at the register limit with recorded figures (profiles/policy_train), and its body is not moved.  Kernel B is
+// wgrad_rows and kernel C fold / loss_tree of the header, on the group's own rows, partial blocks and tiles.
+//
+//   frag      W2[:, :128]^T of every member's given networks in MFMA A-fragment order (128 KB per member).
+//   stats     per 32-sample tile of a group, in fp64: the number of valid samples and the sums of the non-negative and of the
+//             negative advantages (a fixed butterfly); stats_fold: one workgroup per group folds its tiles in loss_tree's
+//             fixed tree into B_k and the float S+_k, S-_k.
+//   kernel A  a workgroup belongs to ONE group (the block prefix table of mm_policy_bank_grid on the n_k): it stages that
+//             member's fragments once -- the staging and the LDS layout are policy_train_sample_kernel's, conflict-free
+//             ds_read_b128 per four MFMAs -- and walks the group's tiles, counted from the group's own start.  Member-local
+//             sample i = 32 tile + lane sits at row i / w_k, column col_start[k] + i % w_k of the batch; its scratch rows at
+//             32 tile_start[k] + i.
+//   kernel B  grid = the sum of the groups' slices; a workgroup finds its group from the slice prefix table.
+//   kernel C  grid (elements, K): member k folds its own partial blocks in workgroup order, the last workgroup its loss tree.
+// The tables ride in the by-value argument blocks (uniform lookups: scalar loads from the kernel-argument segment).
+#include "mm_policy_mfma.h"
+#include "../../include/mm_policy_bank_train.h"
+
+namespace mm {
+namespace bank_train {
+
+using namespace mfma;
+constexpr int kCat = kW2Pitch;
+constexpr int kOhPitch = 136;
+constexpr int kThreadsA = 64 * MM_BANK_WAVES;  // 8 waves, as policy_train_sample_kernel and policy_bank_kernel
+constexpr int kWavesA = MM_BANK_WAVES;
+constexpr int kThreadsB = 320;
+constexpr int kG = MM_BANK_MAX_GROUPS;
+constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network, in floats
+typedef PartialBlock<4> Part;
+static_assert(MM_BANK_TILE == 32, "one wave per 32 samples: the MFMA tile");
+static_assert(2 * kFrag * 4 == MM_PBT_MEMBER_BYTES && Part::kSize * 4 == MM_PBT_PARTIAL_BYTES, "the header's scratch figures");
+static_assert((4 * kHidden + kDh + kXs) * 4 == MM_PBT_SAMPLE_BYTES && MM_PBT_HEADER_BYTES == 4 * 4 * kG, "the header's scratch figures");
+
+// The group tables of a call; entries past K repeat the last one.
+struct Tables {
+  int col_start[kG + 1];    // member k owns columns [col_start[k], col_start[k + 1]) of every row
+  int tile_start[kG + 1];   // prefix of the groups' 32-sample tiles: scratch rows of group k start at 32 tile_start[k]
+  int slice_start[kG + 1];  // prefix of the groups' kernel-B slices = partial blocks
+  int block_start[kG + 1];  // prefix of kernel A's workgroups
+  int rows, row_len;
+};
+
+MM_DEV int group_of(const int (&start)[kG + 1], int b) {
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < kG; k++) g += start[k] <= b ? 1 : 0;
+  return g;
+}
+
+// mm_policy_train's slicing of a group of nt tiles: whole tiles, at least 2 per slice, at most kMaxSlices slices
+MM_DEV int tiles_per_slice(int nt) {
+  const int per = (nt + kMaxSlices - 1) / kMaxSlices;
+  return per < 2 ? 2 : per;
+}
+
+// member-local sample i of a group of width w starting at column c0 -> the batch's sample index
+MM_DEV unsigned sample_of(unsigned i, unsigned w, unsigned c0, unsigned row_len) {
+  const unsigned r = i / w;
+  return r * row_len + c0 + (i - r * w);
+}
+
+// ---- frag: W2[:, :128]^T fragments of member blockIdx.y's given networks
+__global__ __launch_bounds__(256) void bank_frag_kernel(const float *__restrict__ W2a, const float *__restrict__ W2c, int k2c,
+                                                        float4 *__restrict__ frag) {
+  const int t = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+  const bool crit = t >= 4096;
+  const float *W2 = crit ? W2c : W2a;
+  const int k2 = crit ? k2c : kHidden;
+  if (W2) frag[(long long)k * 2 * 4096 + t] = w2t_fragment(W2 + (long long)k * kHidden * k2, k2, t & 4095);
+}
+
+struct StatArgs {
+  const uint8_t *valid;
+  const float *advantages, *target_value, *returns;
+  long long ret_stride;
+  int sums;  // reference form with actors: S+ / S- are wanted
+  double *stats;
+};
+
+// ---- stats: one wave per tile, lanes 0..31 one sample each
+__global__ __launch_bounds__(256) void bank_stats_kernel(const StatArgs p, const Tables tb, int total_tiles) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int t = blockIdx.x * 4 + wave; t < total_tiles; t += gridDim.x * 4) {
+    const int g = group_of(tb.tile_start, t);
+    const unsigned c0 = tb.col_start[g], w = tb.col_start[g + 1] - c0;
+    const long long ng = (long long)w * tb.rows;
+    const long long local = (long long)(t - tb.tile_start[g]) * 32 + lane;
+    double cnt = 0.0, sp = 0.0, sn = 0.0;
+    if (lane < 32 && local < ng) {
+      const unsigned gj = sample_of((unsigned)local, w, c0, (unsigned)tb.row_len);
+      if (!p.valid || p.valid[gj] != 0) {
+        cnt = 1.0;
+        if (p.sums) {
+          const float adv = p.advantages ? p.advantages[gj] : p.returns[gj * p.ret_stride] - p.target_value[gj];
+          if (adv >= 0.0f) sp = (double)adv;
+          else if (adv < 0.0f) sn = (double)adv;
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) {
+      cnt += __shfl_xor(cnt, o, 64);
+      sp += __shfl_xor(sp, o, 64);
+      sn += __shfl_xor(sn, o, 64);
+    }
+    if (lane == 0) {
+      p.stats[3ll * t + 0] = cnt;
+      p.stats[3ll * t + 1] = sp;
+      p.stats[3ll * t + 2] = sn;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void bank_stats_fold_kernel(const double *__restrict__ stats, const Tables tb, int *__restrict__ count,
+                                                              float *__restrict__ sums, float *__restrict__ sums_out) {
+  __shared__ double s[3][256];
+  const int k = blockIdx.x;
+  loss_tree<3>(stats + 3ll * tb.tile_start[k], tb.tile_start[k + 1] - tb.tile_start[k], s);
+  if (threadIdx.x == 0) {
+    count[k] = (int)s[0][0];
+    sums[2 * k] = (float)s[1][0];
+    sums[2 * k + 1] = (float)s[2][0];
+    if (sums_out) {
+      sums_out[2 * k] = (float)s[1][0];
+      sums_out[2 * k + 1] = (float)s[2][0];
+    }
+  }
+}
+
+struct SampleArgs {
+  const float *obs;
+  long long obs_stride;
+  int n_s;
+  const int32_t *actions;
+  long long act_stride;
+  const float *returns;
+  long long ret_stride;
+  const float *old_logp;
+  const uint8_t *valid;
+  MMMlpParams w;  // the six stacked bases
+  int n_a;
+  float clip_param;
+  int huber, ref_form;
+  const float *adv_sums;  // [K][2]
+  const float *advantages, *target_value;
+  const int *count;    // [K]
+  const float4 *frag;  // this network's fragments of member 0; member k 2 * 4096 float4 further
+  float *s_h1, *s_dz1, *s_h2, *s_dz2, *s_dh, *s_xs;
+  double *lossp;
+  float *out0, *out1;  // actor: logp_taken, ratio; critic: value, unused
+};
+
+// ---- kernel A
+template <bool kCritic, bool kTrain>
+__global__ __launch_bounds__(kThreadsA) void bank_sample_kernel(const SampleArgs p, const Tables tb) {
+  __shared__ float4 sW1[4][4][64];   // [out tile][k-step / 4][lane]: 16 KB
+  __shared__ float4 sW2[4][16][64];  // [out tile][k-step / 4][lane]: 64 KB
+  __shared__ __attribute__((aligned(16))) float sWh[8][kHidden];
+  __shared__ __attribute__((aligned(16))) float sOh[kCritic ? 8 : 1][kOhPitch];
+  __shared__ __attribute__((aligned(16))) float sB1[kHidden], sB2[kHidden];
+  __shared__ float sBh[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 31, h = lane >> 5;
+  const int n_s = p.n_s, n_a = p.n_a;
+  const int k2 = kCritic ? kHidden + n_a : kHidden;
+  const int n_out = kCritic ? 1 : n_a;
+  // ---- the workgroup's group and that member's tensors
+  const int b = (int)blockIdx.x;
+  const int g = group_of(tb.block_start, b);
+  const int lb = b - tb.block_start[g], nblk = tb.block_start[g + 1] - tb.block_start[g];
+  const unsigned c0 = tb.col_start[g], gw = tb.col_start[g + 1] - c0, row_len = tb.row_len;
+  const long long n = (long long)gw * tb.rows;
+  const long long row_base = 32ll * tb.tile_start[g];
+  const float *__restrict__ W1 = p.w.W1 + (long long)g * kHidden * n_s;
+  const float *__restrict__ W2 = p.w.W2 + (long long)g * kHidden * k2;
+  const float *__restrict__ W3 = p.w.W3 + g * n_out * kHidden;
+  for (int t = tid; t < 4 * 4 * 64; t += kThreadsA) {
+    const int l = t & 63, q = (t >> 6) & 3, m = t >> 8;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int k = 2 * (4 * q + u) + (l >> 5);
+      v[u] = k < n_s ? W1[(32 * m + (l & 31)) * n_s + k] : 0.0f;
+    }
+    sW1[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int t = tid; t < 4 * 16 * 64; t += kThreadsA) {
+    const int l = t & 63, q = (t >> 6) & 15, m = t >> 10;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int s = 4 * q + u;
+      v[u] = W2[(32 * m + (l & 31)) * k2 + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
+    }
+    sW2[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int t = tid; t < 8 * kHidden; t += kThreadsA) {
+    const int o = t / kHidden, c = t % kHidden;
+    sWh[o][c] = o < n_out ? W3[o * kHidden + c] : 0.0f;
+    if constexpr (kCritic) sOh[o][c] = o < n_a ? W2[c * k2 + kHidden + o] : 0.0f;
+  }
+  if (tid < kHidden) {
+    sB1[tid] = p.w.b1[g * kHidden + tid];
+    sB2[tid] = p.w.b2[g * kHidden + tid];
+  }
+  if (tid < 8) sBh[tid] = tid < n_out ? p.w.b3[g * n_out + tid] : 0.0f;
+  __syncthreads();
+  int nb = 0;
+  if (kTrain) nb = p.count[g];
+  const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
+  const bool ref_form = p.ref_form != 0;
+  const double sp_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[2 * g] : 0.0;
+  const double sn_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[2 * g + 1] : 0.0;
+  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
+  const float lo = 1.0f - p.clip_param, hi = 1.0f + p.clip_param;
+  const long long ntiles = (n + 31) / 32;
+  const float4 *const frag = p.frag + (long long)g * 2 * 4096;
+  double *const lossp = p.lossp + tb.tile_start[g];
+  for (long long tile = (long long)lb * kWavesA + wave; tile < ntiles; tile += (long long)nblk * kWavesA) {
+    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
+    const long long local = tile * 32 + j;
+    const bool inr = local < n;
+    const long long ag = inr ? (long long)sample_of((unsigned)local, gw, c0, row_len) : 0;  // the batch's sample index
+    const long long sr = row_base + local;                                                  // the scratch row
+    bool live = inr;
+    if (live && p.valid) live = p.valid[ag] != 0;
+    const float *row = p.obs + (live ? ag : 0) * p.obs_stride;
+    int act = live ? p.actions[ag * p.act_stride] : 0;
+    act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
+    float x[16];
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+      const int k = 2 * s + h;
+      x[s] = (live && k < n_s) ? row[k] : 0.0f;
+    }
+    if (kTrain) {
+      float4 *dst = reinterpret_cast<float4 *>(p.s_xs + sr * kXs + 16 * h);
+#pragma unroll
+      for (int gq = 0; gq < 4; gq++) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const int c = 16 * h + 4 * gq + u;
+          v[u] = (live && c < n_s) ? row[c] : 0.0f;
+        }
+        dst[gq] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+    f32x16 h1[4], h2[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      f32x16 acc;
+#pragma unroll
+      for (int gq = 0; gq < 4; gq++) {
+        const float4 bq = *reinterpret_cast<const float4 *>(&sB1[32 * m + 8 * gq + 4 * h]);
+        acc[4 * gq] = bq.x; acc[4 * gq + 1] = bq.y; acc[4 * gq + 2] = bq.z; acc[4 * gq + 3] = bq.w;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) acc = mfma4(sW1[m][q][lane], x[4 * q + 0], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3], acc);
+      h1[m] = relu(acc);
+      if (kTrain) store_tile(p.s_h1 + sr * kHidden + 32 * m + 4 * h, h1[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      f32x16 acc;
+#pragma unroll
+      for (int gq = 0; gq < 4; gq++) {
+        float4 bq = *reinterpret_cast<const float4 *>(&sB2[32 * m + 8 * gq + 4 * h]);
+        if constexpr (kCritic) {  // the one-hot block of fc2: column 128 + act
+          const float4 o = *reinterpret_cast<const float4 *>(&sOh[act][32 * m + 8 * gq + 4 * h]);
+          bq.x += o.x; bq.y += o.y; bq.z += o.z; bq.w += o.w;
+        }
+        acc[4 * gq] = bq.x; acc[4 * gq + 1] = bq.y; acc[4 * gq + 2] = bq.z; acc[4 * gq + 3] = bq.w;
+      }
+      h2[m] = relu(fc2_tile<4>(sW2[m], h1, lane, acc));
+      if (kTrain) store_tile(p.s_h2 + sr * kHidden + 32 * m + 4 * h, h2[m]);
+    }
+    // ---- head, the objective's per-sample terms, dhead (both lane halves compute the same numbers)
+    float dhead[8];
+    double t_loss = 0.0;
+    if (kCritic) {
+      float v = 0.0f;
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[0][32 * m + frag_row(r, h)], v);
+      v = v + __shfl_xor(v, 32, 64) + sBh[0];
+      if (h == 0 && inr && p.out0) p.out0[ag] = live ? v : 0.0f;
+      if (!kTrain) continue;
+      const float ret = live ? p.returns[ag * p.ret_stride] : 0.0f;
+      const float d = v - ret;
+      float t_critic, dv;
+      critic_term(d, p.huber, t_critic, dv);
+      t_loss = (double)t_critic;
+      dhead[0] = live ? dv * inv_b : 0.0f;
+#pragma unroll
+      for (int o = 1; o < 8; o++) dhead[o] = 0.0f;
+    } else {
+      float logit[8];
+#pragma unroll
+      for (int o = 0; o < 8; o++) {
+        const float s = head_dot(h2, sWh[o], h, o < n_a);
+        logit[o] = o < n_a ? s + sBh[o] : -INFINITY;
+      }
+      const float mx = max8(logit);
+      float se = 0.0f;
+#pragma unroll
+      for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
+      const float lse = mx + logf(se);
+      const float lp_a = logp_taken(logit, lse, act);
+      if (!kTrain) {
+        if (h == 0 && inr && p.out0) p.out0[ag] = live ? lp_a : 0.0f;
+        continue;
+      }
+      const float olp = live ? p.old_logp[ag] : 0.0f;
+      const float r = expf(lp_a - olp);
+      const float c = fminf(fmaxf(r, lo), hi);
+      float wsel;
+      if (ref_form) {
+        ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_loss, wsel);
+      } else {
+        float adv = 0.0f;
+        if (live) adv = p.advantages ? p.advantages[ag] : p.returns[ag * p.ret_stride] - p.target_value[ag];
+        ppo_clip_flat(adv, lo, hi, r, c, t_loss, wsel);
+      }
+      const float g_lp = live ? -inv_b * wsel * r : 0.0f;  // d loss / d logp_taken
+#pragma unroll
+      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
+      if (h == 0 && inr) {
+        if (p.out0) p.out0[ag] = live ? lp_a : 0.0f;
+        if (p.out1) p.out1[ag] = live ? r : 0.0f;
+      }
+    }
+    {
+      float4 *dst = reinterpret_cast<float4 *>(p.s_dh + sr * kDh + 8 * h);
+      if (h == 0) {
+        dst[0] = make_float4(dhead[0], dhead[1], dhead[2], dhead[3]);
+        dst[1] = make_float4(dhead[4], dhead[5], dhead[6], dhead[7]);
+      } else {
+        dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        dst[1] = make_float4(0.0f, 0.0f, 0.0f, kCritic ? (float)act : 0.0f);  // column kActCol
+      }
+    }
+    {
+      double pl = (live && h == 0) ? t_loss : 0.0;
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) pl += __shfl_xor(pl, o, 64);
+      if (lane == 0) lossp[tile] = pl;
+    }
+    // ---- dz2 = (W3^T dhead) . [h2 > 0], in accumulator form (reuses h2's registers)
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+#pragma unroll
+      for (int gq = 0; gq < 4; gq++) {
+        const int f = 32 * m + 8 * gq + 4 * h;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+        for (int o = 0; o < (kCritic ? 1 : 8); o++) {
+          const float4 wa = *reinterpret_cast<const float4 *>(&sWh[o][f]);
+          s0 = fmaf(dhead[o], wa.x, s0);
+          s1 = fmaf(dhead[o], wa.y, s1);
+          s2 = fmaf(dhead[o], wa.z, s2);
+          s3 = fmaf(dhead[o], wa.w, s3);
+        }
+        h2[m][4 * gq + 0] = h2[m][4 * gq + 0] > 0.0f ? s0 : 0.0f;
+        h2[m][4 * gq + 1] = h2[m][4 * gq + 1] > 0.0f ? s1 : 0.0f;
+        h2[m][4 * gq + 2] = h2[m][4 * gq + 2] > 0.0f ? s2 : 0.0f;
+        h2[m][4 * gq + 3] = h2[m][4 * gq + 3] > 0.0f ? s3 : 0.0f;
+      }
+      store_tile(p.s_dz2 + sr * kHidden + 32 * m + 4 * h, h2[m]);
+    }
+    // ---- dz1 = (W2[:, :128]^T dz2) . [h1 > 0]: 4 output tiles x 64 k-steps, A fragments from global memory
+    const unsigned vlane = opaque_lane(lane);
+#pragma unroll
+    for (int mt = 0; mt < 4; mt++) {
+      const f32x16 acc = dz1_tile(frag, mt, vlane, h2);
+#pragma unroll
+      for (int gq = 0; gq < 4; gq++) {
+        float4 *dst = reinterpret_cast<float4 *>(p.s_dz1 + sr * kHidden + 32 * mt + 4 * h);
+        dst[2 * gq] = make_float4(h1[mt][4 * gq] > 0.0f ? acc[4 * gq] : 0.0f, h1[mt][4 * gq + 1] > 0.0f ? acc[4 * gq + 1] : 0.0f,
+                                  h1[mt][4 * gq + 2] > 0.0f ? acc[4 * gq + 2] : 0.0f, h1[mt][4 * gq + 3] > 0.0f ? acc[4 * gq + 3] : 0.0f);
+      }
+    }
+  }
+}
+
+// ---- kernel B: workgroup b = slice b - slice_start[g] of group g
+template <bool kCritic>
+__global__ __launch_bounds__(kThreadsB) void bank_wgrad_kernel(const float *__restrict__ s_h1, const float *__restrict__ s_dz1,
+                                                               const float *__restrict__ s_h2, const float *__restrict__ s_dz2,
+                                                               const float *__restrict__ s_dh, const float *__restrict__ s_xs,
+                                                               const Tables tb, float *__restrict__ part) {
+  const int b = (int)blockIdx.x;
+  const int g = group_of(tb.slice_start, b);
+  const int nt = tb.tile_start[g + 1] - tb.tile_start[g];
+  const long long slice_rows = 32ll * tiles_per_slice(nt);
+  const long long row0 = 32ll * tb.tile_start[g] + (long long)(b - tb.slice_start[g]) * slice_rows;
+  long long row1 = row0 + slice_rows;
+  if (row1 > 32ll * tb.tile_start[g + 1]) row1 = 32ll * tb.tile_start[g + 1];
+  wgrad_rows<4, kCritic>(s_h1, s_dz1, s_h2, s_dz2, s_dh, s_xs, row0, row1, part + (long long)b * Part::kSize);
+}
+
+// ---- kernel C: member blockIdx.y; element t = its partial blocks summed in workgroup order; the last workgroup folds its loss
+static int fold_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
+
+__global__ __launch_bounds__(256) void bank_fold_kernel(const float *__restrict__ part_all, const Tables tb, int n_s, int k2, int n_out,
+                                                        MMMlpParams gr, const double *__restrict__ lossp, const int *__restrict__ count,
+                                                        int loss_mode, float *__restrict__ loss) {
+  const int k = blockIdx.y;
+  if (blockIdx.x == gridDim.x - 1) {
+    __shared__ double ssum[1][256];
+    const int nt = tb.tile_start[k + 1] - tb.tile_start[k];
+    loss_tree<1>(lossp + tb.tile_start[k], nt, ssum);
+    if (threadIdx.x == 0) {
+      const double inv = inv_count(count + k);
+      const float v = (float)(loss_mode == 0 ? ssum[0][0] * inv : (loss_mode == 1 ? -ssum[0][0] * inv : -ssum[0][0] * inv * inv));
+      loss[2 * k] = nt > 0 ? v : 0.0f;
+    }
+    return;
+  }
+  const float *part = part_all + (long long)tb.slice_start[k] * Part::kSize;
+  const int slices = tb.slice_start[k + 1] - tb.slice_start[k];
+  int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < kHidden * n_s) { const int o = t / n_s, c = t % n_s; gr.W1[(long long)k * kHidden * n_s + t] = fold<Part::kSize>(part, slices, Part::kW1 + o * 32 + c); return; }
+  t -= kHidden * n_s;
+  if (t < kHidden) { gr.b1[k * kHidden + t] = fold<Part::kSize>(part, slices, Part::kb1 + t); return; }
+  t -= kHidden;
+  if (t < kHidden * k2) { const int o = t / k2, c = t % k2; gr.W2[(long long)k * kHidden * k2 + t] = fold<Part::kSize>(part, slices, Part::kW2 + o * kCat + c); return; }
+  t -= kHidden * k2;
+  if (t < kHidden) { gr.b2[k * kHidden + t] = fold<Part::kSize>(part, slices, Part::kb2 + t); return; }
+  t -= kHidden;
+  if (t < n_out * kHidden) { gr.W3[k * n_out * kHidden + t] = fold<Part::kSize>(part, slices, Part::kHd + t); return; }
+  t -= n_out * kHidden;
+  if (t < n_out) gr.b3[k * n_out + t] = fold<Part::kSize>(part, slices, Part::kbh + t);
+}
+
+// ---- host side
+struct Plan {
+  Tables tb;
+  long long total_tiles, total_slices, cap_slices;  // cap_slices: the partial blocks the scratch query reserves
+  long long n;
+};
+
+// checks rows / row_len / K / col_start and fills the tables; false: refused
+static bool plan(int64_t rows, int64_t row_len, int32_t K, const int64_t *col_start, bool with_grid, Plan &P) {
+  if (rows < 0 || row_len < 0 || !col_start || K < 1 || K > kG || col_start[0] != 0) return false;
+  for (int k = 0; k < K; k++)
+    if (col_start[k + 1] < col_start[k]) return false;
+  if (col_start[K] != row_len) return false;
+  if (row_len > 0 && rows > 0x7FFFFFFFll / row_len) return false;
+  P.n = rows * row_len;
+  int64_t size_start[kG + 1];
+  Tables &tb = P.tb;
+  tb.rows = (int)rows; tb.row_len = (int)row_len;
+  tb.tile_start[0] = tb.slice_start[0] = 0;
+  size_start[0] = 0;
+  P.cap_slices = 0;
+  for (int k = 0; k < K; k++) {
+    const long long nk = (col_start[k + 1] - col_start[k]) * rows, nt = (nk + 31) / 32;
+    long long per = (nt + kMaxSlices - 1) / kMaxSlices;
+    if (per < 2) per = 2;
+    const long long cap = (nt + 1) / 2 < kMaxSlices ? (nt + 1) / 2 : kMaxSlices;
+    tb.col_start[k] = (int)col_start[k];
+    tb.tile_start[k + 1] = tb.tile_start[k] + (int)nt;
+    tb.slice_start[k + 1] = tb.slice_start[k] + (int)((nt + per - 1) / per);
+    size_start[k + 1] = size_start[k] + nk;
+    P.cap_slices += cap;
+  }
+  for (int k = K; k <= kG; k++) {
+    tb.col_start[k] = (int)row_len;
+    tb.tile_start[k] = tb.tile_start[K];
+    tb.slice_start[k] = tb.slice_start[K];
+  }
+  P.total_tiles = tb.tile_start[K];
+  P.total_slices = tb.slice_start[K];
+  for (int k = 0; k <= kG; k++) tb.block_start[k] = 0;
+  if (with_grid && P.n > 0) {
+    if (mm_policy_bank_grid(K, size_start, tb.block_start) != MM_OK) return false;
+    for (int k = K + 1; k <= kG; k++) tb.block_start[k] = tb.block_start[K];
+  }
+  return true;
+}
+
+// the scratch, offsets in floats
+struct Scratch {
+  long long count, sums, frag, h1, dz1, h2, dz2, dh, xs, lossp, stats, part, total;
+};
+
+static Scratch scratch_of(const Plan &P, int K) {
+  Scratch S;
+  const long long n_pad = 32 * P.total_tiles;
+  S.count = 0;
+  S.sums = kG;
+  S.frag = MM_PBT_HEADER_BYTES / 4;
+  S.h1 = S.frag + (long long)K * 2 * kFrag;
+  S.dz1 = S.h1 + n_pad * kHidden;
+  S.h2 = S.dz1 + n_pad * kHidden;
+  S.dz2 = S.h2 + n_pad * kHidden;
+  S.dh = S.dz2 + n_pad * kHidden;
+  S.xs = S.dh + n_pad * kDh;
+  S.lossp = S.xs + n_pad * kXs;
+  S.stats = S.lossp + 2 * P.total_tiles;
+  S.part = S.stats + 6 * P.total_tiles;
+  S.total = S.part + P.cap_slices * Part::kSize;
+  return S;
+}
+
+static bool shapes_ok(int32_t n_s, int32_t hidden, int32_t n_a) {
+  return n_s >= 25 && n_s <= 32 && hidden == kHidden && n_a >= 1 && n_a <= 8;
+}
+
+}  // namespace bank_train
+}  // namespace mm
+
+extern "C" int32_t mm_policy_bank_eval(const float *obs, int64_t obs_stride, int64_t rows, int64_t row_len, int32_t n_s,
+                                       const int32_t *actions, int64_t act_stride, const uint8_t *valid, const MMMlpParams *actors,
+                                       const MMMlpParams *critics, int32_t K, const int64_t *col_start, int32_t hidden, int32_t n_a,
+                                       float *logp_taken, float *value, MMStream stream) {
+  using namespace mm::bank_train;
+  if (!actors && !critics) return MM_ERR_INVALID_ARG;
+  if ((actors && !complete(actors)) || (critics && !complete(critics))) return MM_ERR_INVALID_ARG;
+  if (!shapes_ok(n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  Plan P;
+  if (!plan(rows, row_len, K, col_start, true, P)) return MM_ERR_INVALID_ARG;
+  if (P.n == 0) return MM_OK;
+  if ((actors != nullptr) != (logp_taken != nullptr) || (critics != nullptr) != (value != nullptr)) return MM_ERR_INVALID_ARG;
+  if (!obs || !actions || obs_stride < n_s) return MM_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  SampleArgs a = {};
+  a.obs = obs; a.obs_stride = obs_stride; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride; a.valid = valid; a.n_a = n_a;
+  const unsigned grid = (unsigned)P.tb.block_start[K];
+  if (actors) {
+    a.w = *actors; a.out0 = logp_taken;
+    hipLaunchKernelGGL((bank_sample_kernel<false, false>), dim3(grid), dim3(kThreadsA), 0, s, a, P.tb);
+  }
+  if (critics) {
+    a.w = *critics; a.out0 = value;
+    hipLaunchKernelGGL((bank_sample_kernel<true, false>), dim3(grid), dim3(kThreadsA), 0, s, a, P.tb);
+  }
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}
+
+extern "C" int32_t mm_policy_bank_train_scratch_bytes(int64_t rows, int64_t row_len, int32_t K, const int64_t *col_start,
+                                                      uint64_t *bytes) {
+  using namespace mm::bank_train;
+  Plan P;
+  if (!bytes || !plan(rows, row_len, K, col_start, false, P)) return MM_ERR_INVALID_ARG;
+  *bytes = (uint64_t)scratch_of(P, K).total * 4u;
+  return MM_OK;
+}
+
+extern "C" int32_t mm_policy_bank_train(const float *obs, int64_t obs_stride, int64_t rows, int64_t row_len, int32_t n_s,
+                                        const int32_t *actions, int64_t act_stride, const float *returns, int64_t ret_stride,
+                                        const float *old_logp, const uint8_t *valid, const MMMlpParams *actors,
+                                        const MMMlpParams *critics, int32_t K, const int64_t *col_start, int32_t hidden, int32_t n_a,
+                                        float clip_param, int32_t critic_loss, int32_t form, const float *advantages,
+                                        const float *target_value, const MMMlpParams *actor_grads, const MMMlpParams *critic_grads,
+                                        float *loss, float *adv_sums, float *logp_taken, float *value, float *ratio, void *scratch,
+                                        uint64_t scratch_bytes, MMStream stream) {
+  using namespace mm::bank_train;
+  if ((!actors && !critics) || !loss) return MM_ERR_INVALID_ARG;
+  if ((actors != nullptr) != (actor_grads != nullptr) || (critics != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
+  if ((actors && (!complete(actors) || !complete(actor_grads))) || (critics && (!complete(critics) || !complete(critic_grads))))
+    return MM_ERR_INVALID_ARG;
+  if (!shapes_ok(n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
+  if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
+  if (form != MM_PT_FORM_REFERENCE && form != MM_PT_FORM_PER_SAMPLE) return MM_ERR_INVALID_ARG;
+  if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
+  if ((!actors && (logp_taken || ratio)) || (!critics && value)) return MM_ERR_INVALID_ARG;
+  Plan P;
+  if (!plan(rows, row_len, K, col_start, true, P)) return MM_ERR_INVALID_ARG;
+  const Scratch S = scratch_of(P, K);
+  if (P.n > 0) {  // (n == 0: the per-sample inputs and the scratch are not looked at and may be NULL, as in mm_policy_train)
+    if (actors && ((advantages != nullptr) == (target_value != nullptr))) return MM_ERR_INVALID_ARG;
+    if (!obs || !actions || obs_stride < n_s || (actors && !old_logp) || ((critics || (actors && target_value)) && !returns))
+      return MM_ERR_INVALID_ARG;
+    if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < (uint64_t)S.total * 4u) return MM_ERR_INVALID_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int k2c = kHidden + n_a;
+  if (hipMemsetAsync(loss, 0, (size_t)K * 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+  if (P.n == 0) {  // nothing to contract: zero gradients (K members of each tensor), zero sums
+    if (adv_sums && hipMemsetAsync(adv_sums, 0, (size_t)K * 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+    for (int net = 0; net < 2; net++) {
+      const MMMlpParams *g = net ? critic_grads : actor_grads;
+      if (!g) continue;
+      const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
+      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
+      const size_t gsz[6] = {(size_t)kHidden * n_s, (size_t)kHidden, (size_t)kHidden * k2, (size_t)kHidden, (size_t)n_out * kHidden, (size_t)n_out};
+      for (int t = 0; t < 6; t++)
+        if (hipMemsetAsync(gp[t], 0, gsz[t] * K * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
+    }
+    return MM_OK;
+  }
+  float *sc = (float *)scratch;
+  int *count = (int *)(sc + S.count);
+  float *sums = sc + S.sums;
+  double *lossp = (double *)(sc + S.lossp), *stats = (double *)(sc + S.stats);
+  const bool ref_form = form == MM_PT_FORM_REFERENCE;
+  hipLaunchKernelGGL(bank_frag_kernel, dim3(2 * 4096 / 256, K), dim3(256), 0, s, actors ? actors->W2 : nullptr,
+                     critics ? critics->W2 : nullptr, k2c, (float4 *)(sc + S.frag));
+  StatArgs st = {};
+  st.valid = valid; st.advantages = advantages; st.target_value = target_value; st.returns = returns; st.ret_stride = ret_stride;
+  st.sums = actors && ref_form; st.stats = stats;
+  const long long stat_blocks = (P.total_tiles + 3) / 4;
+  hipLaunchKernelGGL(bank_stats_kernel, dim3((unsigned)(stat_blocks < 2048 ? stat_blocks : 2048)), dim3(256), 0, s, st, P.tb,
+                     (int)P.total_tiles);
+  hipLaunchKernelGGL(bank_stats_fold_kernel, dim3(K), dim3(256), 0, s, (const double *)stats, P.tb, count, sums, adv_sums);
+  SampleArgs a = {};
+  a.obs = obs; a.obs_stride = obs_stride; a.n_s = n_s; a.actions = actions; a.act_stride = act_stride; a.returns = returns;
+  a.ret_stride = ret_stride; a.old_logp = old_logp; a.valid = valid; a.n_a = n_a; a.clip_param = clip_param;
+  a.huber = critic_loss == MM_PT_CRITIC_HUBER; a.ref_form = ref_form; a.adv_sums = sums; a.advantages = advantages;
+  a.target_value = target_value; a.count = count;
+  a.s_h1 = sc + S.h1; a.s_dz1 = sc + S.dz1; a.s_h2 = sc + S.h2; a.s_dz2 = sc + S.dz2; a.s_dh = sc + S.dh; a.s_xs = sc + S.xs;
+  a.lossp = lossp;
+  const unsigned grid_a = (unsigned)P.tb.block_start[K], grid_b = (unsigned)P.total_slices;
+  for (int net = 0; net < 2; net++) {  // the actors' three kernels, then the critics' over the same scratch
+    const MMMlpParams *w = net ? critics : actors;
+    if (!w) continue;
+    const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
+    a.w = *w; a.frag = (const float4 *)(sc + S.frag + net * kFrag);
+    a.out0 = net ? value : logp_taken; a.out1 = net ? nullptr : ratio;
+    if (net) {
+      hipLaunchKernelGGL((bank_sample_kernel<true, true>), dim3(grid_a), dim3(kThreadsA), 0, s, a, P.tb);
+      hipLaunchKernelGGL((bank_wgrad_kernel<true>), dim3(grid_b), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2, a.s_dh,
+                         a.s_xs, P.tb, sc + S.part);
+    } else {
+      hipLaunchKernelGGL((bank_sample_kernel<false, true>), dim3(grid_a), dim3(kThreadsA), 0, s, a, P.tb);
+      hipLaunchKernelGGL((bank_wgrad_kernel<false>), dim3(grid_b), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2, a.s_dh,
+                         a.s_xs, P.tb, sc + S.part);
+    }
+    hipLaunchKernelGGL(bank_fold_kernel, dim3((fold_elems(n_s, k2, n_out) + 255) / 256 + 1, K), dim3(256), 0, s,
+                       (const float *)(sc + S.part), P.tb, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads,
+                       (const double *)lossp, (const int *)count, net ? 0 : (ref_form ? 2 : 1), loss + net);
+  }
+  return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_DEVICE;
+}

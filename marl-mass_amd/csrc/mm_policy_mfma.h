@@ -244,19 +244,16 @@ struct PartialBlock {
 // owns output rows 32 w .. 32 w + 31 of dW2 = dz2^T [h1 | one_hot] (kL1 column tiles, + 1 with kOneHot: the one-hot row rebuilt
 // from the action in column kActCol of the head row) and columns 32 w .. of the head tile dhead^T h2; wave 4 owns dW1 = dz1^T x.
 // Bias sums on the VALU from the A operands, in fp64: one add per k-step, no rounding of a 10^3-term running sum.
+// wgrad_rows: the contraction over rows [row0, row1) into the partial block `out`; wgrad_slice: workgroup b's slice of a batch.
 template <int kL1, bool kOneHot>
-MM_DEV void wgrad_slice(const float *s_h1, const float *s_dz1, const float *s_h2,
-                        const float *s_dz2, const float *s_dh, const float *s_xs,
-                        long long n_pad, long long slice_rows, float *part) {
+MM_DEV void wgrad_rows(const float *s_h1, const float *s_dz1, const float *s_h2,
+                       const float *s_dz2, const float *s_dh, const float *s_xs,
+                       const long long row0, const long long row1, float *out) {
   typedef PartialBlock<kL1> P;
   constexpr int kPitch1 = 32 * kL1, kTiles2 = kL1 + (kOneHot ? 1 : 0);
   static_assert(32 * kTiles2 <= kW2Pitch, "dW2's column tiles fit a row of the partial");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 31, kh = lane >> 5;
-  const long long row0 = (long long)blockIdx.x * slice_rows;
-  long long row1 = row0 + slice_rows;
-  if (row1 > n_pad) row1 = n_pad;
-  float *out = part + (long long)blockIdx.x * P::kSize;
   if (wave < 4) {
     const int mf = wave;
     f32x16 acc[kTiles2], acch;
@@ -326,6 +323,16 @@ MM_DEV void wgrad_slice(const float *s_h1, const float *s_dz1, const float *s_h2
       if (kh == 0) out[P::kb1 + 32 * c + i] = (float)s;
     }
   }
+}
+
+template <int kL1, bool kOneHot>
+MM_DEV void wgrad_slice(const float *s_h1, const float *s_dz1, const float *s_h2,
+                        const float *s_dz2, const float *s_dh, const float *s_xs,
+                        long long n_pad, long long slice_rows, float *part) {
+  const long long row0 = (long long)blockIdx.x * slice_rows;
+  long long row1 = row0 + slice_rows;
+  if (row1 > n_pad) row1 = n_pad;
+  wgrad_rows<kL1, kOneHot>(s_h1, s_dz1, s_h2, s_dz2, s_dh, s_xs, row0, row1, part + (long long)blockIdx.x * PartialBlock<kL1>::kSize);
 }
 
 // ---- kernel C: element `off` of the partial blocks summed in workgroup order (fp64 running sum)

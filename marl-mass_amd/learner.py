@@ -36,6 +36,10 @@ rollout's envs are: every agent step of train() takes the gradient of ONE loss o
 equal stay bit-equal without a broadcast (`replicas_in_sync()` checks it).  Both phases are public and need no process group.
 At hidden 512 a block is 4.9 MB per rank and agent step, and one pass of a whole shard is 8 384 bytes per sample: a sharded
 learner there wants `scratch_budget_bytes`.  Limit: a sharded train() is not graph-capturable (it runs collectives).
+
+`BankPPOLearner` (at the end) is K `PPOLearner(fused_step=True)`s of one shape as one learner, for the K env groups of a bank-mode
+`DeviceRollout`: stacked storage that the member modules alias, and per agent step one `mm_policy_bank_eval`, one
+`mm_policy_bank_train` (include/mm_policy_bank_train.h) and one `mm_opt_step_bank` whatever K is.
 """
 import copy
 import ctypes as C
@@ -892,4 +896,262 @@ class PPOLearner(_DeviceLearner):
             raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
         if update and not every and not (self.fused_step and losses):
             self.soft_update()
+        return losses
+
+
+class BankPPOLearner(_DeviceLearner):
+    """The training half of bank mode: K `PPOLearner(fused_step=True)`s as ONE learner whose launches do not multiply with K.
+    `actors` / `critics` are K rollout.ActorNetwork / rollout.CriticNetwork of one shape, hidden 128, float32, on the device --
+    typically the members a `DeviceRollout(env, actors, critics, group_envs=...)` acts with; `group_envs` are that rollout's env
+    counts (member k trains on `batch[:, roll.group_slice(k)]`).  The hyperparameters are PPOLearner's and are shared by the
+    members; the optimiser step is always the fused one.
+
+    The learner owns STACKED storage, member k at index k of the leading axis: parameters, gradients, optimiser state, targets
+    (deep copies at construction) and the per-member Adam steps.  At construction every member module's `param.data` and `.grad`
+    are re-pointed at views of the stacks, so the modules -- and a DeviceRollout / PolicyBank built on them -- see every update
+    with no copy back.
+
+    Per agent step (or once, form "flat") train() issues one `mm_policy_bank_eval` on the stacked targets, one
+    `mm_policy_bank_train` (include/mm_policy_bank_train.h) fed the critic targets' values, and one `mm_opt_step_bank`
+    (include/mm_opt_step.h).  Member k's parameters, targets and optimiser state are bit for bit those of a K = 1 learner on its
+    slice.  Against `PPOLearner` the one difference is the reference form's S+ / S-: torch's float32 sums there, one fp64
+    accumulation rounded once here.  Out of scope: hidden 512, ActorCriticNetwork members, scratch budgets and shard groups,
+    per-member hyperparameters."""
+
+    def __init__(self, actors, critics, clib, group_envs, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
+                 critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, soft_update_every="train"):
+        actors, critics = list(actors), list(critics)
+        K = len(actors)
+        if K < 1 or len(critics) != K:
+            raise ValueError("BankPPOLearner needs at least one member and one critic per actor")
+        if K > abi.BANK_MAX_GROUPS:
+            raise ValueError("a policy bank has at most %d members, got %d" % (abi.BANK_MAX_GROUPS, K))
+        if any(isinstance(m, ActorCriticNetwork) for m in actors + critics):
+            raise ValueError("BankPPOLearner does not train ActorCriticNetwork members (MAPPO_GI's shared network): use one "
+                             "SharedPPOLearner per member")
+        if any(type(a) is not ActorNetwork for a in actors) or any(type(c) is not CriticNetwork for c in critics):
+            raise ValueError("BankPPOLearner needs rollout.ActorNetwork and rollout.CriticNetwork members")
+        shapes = [tuple(tuple(p.shape) for p in _mlp_params(a) + _mlp_params(c)) for a, c in zip(actors, critics)]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("the members of a bank learner must have one shape, got %d different ones" % len(set(shapes)))
+        n_s, n_a, hid = actors[0].fc1.weight.shape[1], actors[0].fc3.weight.shape[0], actors[0].fc2.weight.shape[0]
+        if hid != 128:
+            raise ValueError("BankPPOLearner trains hidden-128 members only (hidden %d: one PPOLearner per member)" % hid)
+        if shapes[0] != ((hid, n_s), (hid,), (hid, hid), (hid,), (n_a, hid), (n_a,), (hid, n_s), (hid,), (hid, hid + n_a), (hid,),
+                         (1, hid), (1,)):
+            raise ValueError("BankPPOLearner needs the same state and action sizes in actor and critic and one critic output")
+        if not 1 <= n_a <= 8 or not 25 <= n_s <= 32:
+            raise ValueError("BankPPOLearner supports 25..32 state columns and 1..8 actions, got %d and %d" % (n_s, n_a))
+        for m in actors + critics:
+            for p in m.parameters():
+                if p.dtype != torch.float32 or p.device.type != "cuda":
+                    raise ValueError("BankPPOLearner needs float32 networks on the device")
+        if critic_loss not in abi.PT_CRITIC_LOSS:
+            raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
+        if soft_update_every not in ("train", "agent_step"):
+            raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
+        _optimizer_class(optimizer_type)
+        group_envs = [int(e) for e in group_envs]
+        if len(group_envs) != K or min(group_envs) < 0:
+            raise ValueError("group_envs must hold one non-negative env count per member (%d)" % K)
+        clib.require_policy_bank_train()
+        _DeviceLearner.__init__(self, clib, actors[0].fc1.weight.device, None)
+        self.actors, self.critics, self.K, self.group_envs = actors, critics, K, group_envs
+        self.env_start = [sum(group_envs[:k]) for k in range(K + 1)]
+        self.n_s, self.n_a, self.hidden = n_s, n_a, hid
+        self.optimizer_type, self.lrs = optimizer_type, (float(actor_lr), float(critic_lr))
+        self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
+        self.target_tau, self.target_update_steps = float(target_tau), int(target_update_steps)
+        self.soft_update_every, self.fused_step = soft_update_every, True
+        # the stacks, per network (0 actor, 1 critic) a list of six [K, ...] tensors
+        dev = self.device
+        stack = lambda nets: [torch.stack([_mlp_params(m)[i].detach() for m in nets]).contiguous() for i in range(6)]  # noqa: E731
+        self.params = [stack(actors), stack(critics)]
+        self.grads = [[torch.zeros_like(t) for t in net] for net in self.params]
+        self.targets = [[t.clone() for t in net] for net in self.params]
+        self.state1 = [[torch.zeros_like(t) for t in net] for net in self.params]
+        self.state2 = [[torch.zeros_like(t) for t in net] for net in self.params] if optimizer_type == "adam" else [None, None]
+        self.steps = torch.zeros(2, K, dtype=torch.int32, device=dev)
+        self._grad_norm = torch.zeros(2, K, dtype=torch.float32, device=dev)
+        for net, members in enumerate((actors, critics)):
+            for k, m in enumerate(members):
+                for i, p in enumerate(_mlp_params(m)):
+                    p.data = self.params[net][i][k]
+                    p.grad = self.grads[net][i][k]
+        struct = lambda ts: abi.MMMlpParams(*[t.data_ptr() for t in ts])  # noqa: E731
+        self._W = [struct(net) for net in self.params]
+        self._G = [struct(net) for net in self.grads]
+        self._T = [struct(net) for net in self.targets]
+        self._groups = []
+        for net in range(2):
+            g = abi.MMOptGroup()
+            g.algo, g.n_tensors = OPT_ALGO[optimizer_type], 6
+            for i in range(6):
+                g.count[i] = self.params[net][i][0].numel()
+                g.param[i], g.grad[i] = self.params[net][i].data_ptr(), self.grads[net][i].data_ptr()
+                g.target[i], g.state1[i] = self.targets[net][i].data_ptr(), self.state1[net][i].data_ptr()
+                if self.state2[net] is not None:
+                    g.state2[i] = self.state2[net][i].data_ptr()
+            g.step, g.grad_norm = self.steps[net].data_ptr(), self._grad_norm[net].data_ptr()
+            self._groups.append(g)
+
+    # -- plumbing ----------------------------------------------------------------------------
+    def _torch_optimizer(self, net, k):
+        """A torch optimiser over member k's network: the home of the hyperparameters in torch's format (it never steps)."""
+        members = self.critics if net else self.actors
+        return _optimizer_class(self.optimizer_type)(members[k].parameters(), lr=self.lrs[net])
+
+    def _cols(self, col_start, row_len):
+        cols = [int(c) for c in (self.env_start if col_start is None else col_start)]
+        if len(cols) != self.K + 1 or cols[0] != 0 or cols[-1] != row_len or any(b < a for a, b in zip(cols, cols[1:])):
+            raise ValueError("group_envs %s do not match the batch: the column prefix %s must run from 0 to the row length %d"
+                             % (self.group_envs, cols, row_len))
+        return cols, (C.c_int64 * (self.K + 1))(*cols)
+
+    def _samples(self, obs, actions, rows):
+        n, S = obs.shape
+        if obs.dtype != torch.float32 or (n and obs.stride(1) != 1) or S != self.n_s:
+            raise ValueError("obs must be float32 [n, %d] with contiguous rows" % self.n_s)
+        if actions.dtype != torch.int32 or actions.dim() != 1 or actions.shape[0] != n:
+            raise ValueError("actions must be int32 [n]")
+        rows = int(rows)
+        row_len = n // rows if rows > 0 else self.env_start[-1]
+        if rows < 0 or rows * row_len != n:
+            raise ValueError("%d samples are not %d rows" % (n, rows))
+        return n, S, rows, row_len
+
+    def evaluate(self, obs, actions, rows, col_start=None, valid=None, targets=True, actor=True, critic=True):
+        """The bare mm_policy_bank_eval: (logp_taken, value), float32 [n] each (None for a network that is not asked for), of
+        every sample's own member -- the stacked targets, or with targets=False the stacked networks.  obs [n, S] with any row
+        stride, actions int32 [n] with any stride, n = rows * row_len; col_start: the K + 1 column prefix (None: group_envs')."""
+        n, S, rows, row_len = self._samples(obs, actions, rows)
+        _, cs = self._cols(col_start, row_len)
+        if valid is not None:
+            valid = valid.reshape(-1).to(torch.uint8).contiguous()
+        logp = torch.empty(n, dtype=torch.float32, device=self.device) if actor else None
+        value = torch.empty(n, dtype=torch.float32, device=self.device) if critic else None
+        W = self._T if targets else self._W
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_bank_eval(
+            obs.data_ptr(), obs.stride(0) if n else S, rows, row_len, S, actions.data_ptr(), actions.stride(0) if n else 1, opt(valid),
+            C.byref(W[0]) if actor else None, C.byref(W[1]) if critic else None, self.K, cs, self.hidden, self.n_a, opt(logp),
+            opt(value), self._stream()))
+        return logp, value
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, rows, col_start=None, valid=None, form="reference", advantages=None,
+                      target_value=None, diagnostics=False, networks="both"):
+        """The bare mm_policy_bank_train: writes every member's gradients into the stacked gradients (the modules' .grad) and
+        returns the float32 [K, 2] losses (actor, critic); with diagnostics also the [K, 2] (S+, S-) that were used and
+        (logp_taken, value, ratio) [n].  Inputs as PPOLearner.loss_and_grad's, n = rows * row_len; exactly one of advantages and
+        target_value (float32 [n]) with the actors; form "reference" | "flat".  Only enqueues work."""
+        n, S, rows, row_len = self._samples(obs, actions, rows)
+        cols, cs = self._cols(col_start, row_len)
+        if networks not in ("both", "actor", "critic"):
+            raise ValueError("networks must be 'both', 'actor' or 'critic', got %r" % (networks,))
+        if form not in ("reference", "flat"):
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        if returns.dtype != torch.float32 or returns.dim() != 1 or returns.shape[0] != n or old_logp.shape[0] != n:
+            raise ValueError("returns must be float32 [n] and old_logp [n]")
+        with_a, with_c = networks != "critic", networks != "actor"
+        flat32 = lambda t: None if t is None else t.reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+        old_logp, advantages, target_value = flat32(old_logp), flat32(advantages), flat32(target_value)
+        if valid is not None:
+            valid = valid.reshape(-1).to(torch.uint8).contiguous()
+        loss = torch.empty(self.K, 2, dtype=torch.float32, device=self.device)
+        sums = torch.empty(self.K, 2, dtype=torch.float32, device=self.device) if diagnostics else None
+        new = lambda on: torch.empty(n, dtype=torch.float32, device=self.device) if (diagnostics and on) else None  # noqa: E731
+        diag = [new(with_a), new(with_c), new(with_a)]
+        scratch = self._grow(self.clib.policy_bank_train_scratch_bytes(rows, row_len, cols))
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_bank_train(
+            obs.data_ptr(), obs.stride(0) if n else S, rows, row_len, S, actions.data_ptr(), actions.stride(0) if n else 1,
+            returns.data_ptr(), returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid),
+            C.byref(self._W[0]) if with_a else None, C.byref(self._W[1]) if with_c else None, self.K, cs, self.hidden, self.n_a,
+            self.clip_param, abi.PT_CRITIC_LOSS[self.critic_loss], abi.PT_FORM["reference" if form == "reference" else "per_sample"],
+            opt(advantages) if with_a else None, opt(target_value) if with_a else None, C.byref(self._G[0]) if with_a else None,
+            C.byref(self._G[1]) if with_c else None, loss.data_ptr(), opt(sums), opt(diag[0]), opt(diag[1]), opt(diag[2]),
+            scratch.data_ptr(), scratch.numel(), self._stream()))
+        return (loss, sums, tuple(diag)) if diagnostics else loss
+
+    def _fill(self):
+        for net, g in enumerate(self._groups):
+            g.lr, g.eps = self.lrs[net], 1e-8  # (torch's default eps of both optimisers)
+            g.alpha_or_beta1, g.beta2 = (0.9, 0.999) if self.optimizer_type == "adam" else (0.99, 0.0)
+            g.max_grad_norm = -1.0 if self.max_grad_norm is None else self.max_grad_norm
+            g.tau = self.target_tau
+        return self._groups
+
+    def step(self, soft_mask=0):
+        """clip + optimiser step of all 2 K networks, and the soft update of the members whose bit is set: one launch."""
+        self.clib.opt_step_bank(self._fill(), self.K, int(soft_mask), self._stream())
+
+    def last_grad_norm(self):
+        """The total gradient norms before clipping of the last step, float32 [K, 2] (actor, critic) on the device."""
+        return self._grad_norm.t()
+
+    def optimizer_state_dict(self, k):
+        """Member k's {"actor_optimizer", "critic_optimizer"} in torch.optim's state_dict() format: it loads into a PPOLearner
+        (either path) and into torch.optim.  Reads the member's step counts: synchronises."""
+        out = {}
+        for net, name in enumerate(("actor_optimizer", "critic_optimizer")):
+            s2 = None if self.state2[net] is None else [t[k] for t in self.state2[net]]
+            out[name] = optimizer_state_to_torch(self.optimizer_type, self._torch_optimizer(net, k).state_dict()["param_groups"],
+                                                 int(self.steps[net, k].item()), [t[k] for t in self.state1[net]], s2)
+        return out
+
+    def load_optimizer_state_dict(self, k, state_dict):
+        """The reverse, in place.  The state dict's hyperparameters are not taken: the members share the learner's."""
+        for net, name in enumerate(("actor_optimizer", "critic_optimizer")):
+            step, s1, s2 = optimizer_state_from_torch(state_dict[name], self.optimizer_type, 6)
+            for mine, theirs in ((self.state1[net], s1), (self.state2[net], s2)):
+                if mine is not None:
+                    for m, t in zip(mine, theirs):
+                        m[k].zero_() if t is None else m[k].copy_(t)
+            self.steps[net, k] = step
+
+    def _soft_mask(self, n_episodes):
+        eps = [int(n_episodes)] * self.K if isinstance(n_episodes, int) else [int(e) for e in n_episodes]
+        if len(eps) != self.K:
+            raise ValueError("n_episodes must be an int or one int per member (%d)" % self.K)
+        return sum(1 << k for k, e in enumerate(eps) if e % self.target_update_steps == 0 and e > 0)
+
+    @torch.no_grad()
+    def train(self, states, actions=None, returns=None, n_episodes=0, form="reference", valid=None):
+        """PPOLearner.train() for every member on its env group at once.  states [T, E, N, S] (or [T * E, N, S]),
+        E = sum(group_envs), actions and returns [T, E, N], or `DeviceRollout.interact()`'s dict.  n_episodes: an
+        int or K ints; member k's targets are blended, by PPOLearner's rule (soft_update_every included), when
+        n_episodes[k] % target_update_steps == 0 and n_episodes[k] > 0.  Returns the list of float32 [K, 2] loss tensors, one
+        per agent step (one in all, form "flat"); nothing is synchronised."""
+        if isinstance(states, dict):
+            states, actions, returns = states["states"], states["actions"], states["returns"]
+        if form not in ("reference", "flat"):
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        N, S, E = states.shape[-2], states.shape[-1], self.env_start[-1]
+        if states.dim() == 4 and states.shape[1] == E:
+            rows = states.shape[0]
+        elif states.dim() == 3 and E > 0 and states.shape[0] % E == 0:
+            rows = states.shape[0] // E
+        else:
+            raise ValueError("group_envs %s do not match the batch: states %s must be [T, %d, N, S] or [T * %d, N, S]"
+                             % (self.group_envs, tuple(states.shape), E, E))
+        if actions.numel() != rows * E * N or returns.numel() != rows * E * N:
+            raise ValueError("actions and returns must hold one entry per state row")
+        states = states.reshape(rows, E, N, S).to(torch.float32).contiguous()
+        actions = actions.reshape(rows, E, N).to(torch.int32).contiguous()
+        returns = returns.reshape(rows, E, N).to(torch.float32).contiguous()
+        if valid is not None:
+            valid = valid.reshape(rows, E, N).to(torch.uint8)
+        mask = self._soft_mask(n_episodes)
+        every = self.soft_update_every == "agent_step"
+        losses = []
+        if form == "reference":
+            passes = [(states.view(rows * E, N, S)[:, a, :], actions.view(rows * E, N)[:, a], returns.view(rows * E, N)[:, a],
+                       None if valid is None else valid[:, :, a].reshape(-1).contiguous(), None) for a in range(N)]
+        else:
+            passes = [(states.view(rows * E * N, S), actions.view(-1), returns.view(-1), None if valid is None else valid.reshape(-1),
+                       [e * N for e in self.env_start])]
+        for i, (obs, act, ret, v, cols) in enumerate(passes):
+            old, value = self.evaluate(obs, act, rows, col_start=cols, valid=v)
+            losses.append(self.loss_and_grad(obs, act, ret, old, rows, col_start=cols, valid=v, form=form, target_value=value))
+            self.step(mask if (every or i == len(passes) - 1) else 0)
         return losses
