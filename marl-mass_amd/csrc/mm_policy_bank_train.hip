@@ -2,34 +2,30 @@
 // evaluation (mm_policy_bank_eval) and the loss and full gradient (mm_policy_bank_train) of include/mm_policy_bank_train.h.
 //
 // The arithmetic is mm_policy_train.hip's, from the pieces of mm_policy_mfma.h, and the decomposition of every group is
-// mm_policy_train's on that group's n_k samples; what differs is where a tile's inputs and scratch rows live and whose weights
-// a workgroup stages.  The per-tile body of kernel A is written out here rather than shared with policy_train_sample_kernel:
-// that kernel sits at the register limit with recorded figures (profiles/policy_train), and its body is not moved.  Kernel B is
-// wgrad_rows and kernel C fold / loss_tree of the header, on the group's own rows, partial blocks and tiles.
+// mm_policy_train's on that group's n_k samples; what differs is where a tile's inputs and scratch rows live and whose weights a
+// workgroup stages.  Kernel A is the text mm_policy_train.hip runs, mlp_sample_kernel of mm_policy_sample.h, with that difference as
+// its policy `Group`; kernel B is wgrad_rows and kernel C fold / loss_tree, on the group's own rows, partial blocks and tiles.
 //
 //   frag      W2[:, :128]^T of every member's given networks in MFMA A-fragment order (128 KB per member).
 //   stats     per 32-sample tile of a group, in fp64: the number of valid samples and the sums of the non-negative and of the
 //             negative advantages (a fixed butterfly); stats_fold: one workgroup per group folds its tiles in loss_tree's
 //             fixed tree into B_k and the float S+_k, S-_k.
 //   kernel A  a workgroup belongs to ONE group (the block prefix table of mm_policy_bank_grid on the n_k): it stages that
-//             member's fragments once -- the staging and the LDS layout are policy_train_sample_kernel's, conflict-free
-//             ds_read_b128 per four MFMAs -- and walks the group's tiles, counted from the group's own start.  Member-local
+//             member's fragments once and walks the group's tiles, counted from the group's own start.  Member-local
 //             sample i = 32 tile + lane sits at row i / w_k, column col_start[k] + i % w_k of the batch; its scratch rows at
 //             32 tile_start[k] + i.
 //   kernel B  grid = the sum of the groups' slices; a workgroup finds its group from the slice prefix table.
 //   kernel C  grid (elements, K): member k folds its own partial blocks in workgroup order, the last workgroup its loss tree.
 // The tables ride in the by-value argument blocks (uniform lookups: scalar loads from the kernel-argument segment).
-#include "mm_policy_mfma.h"
+#include "mm_policy_sample.h"  // kernel A; mm_policy_mfma.h
 #include "../../include/mm_policy_bank_train.h"
 
 namespace mm {
 namespace bank_train {
 
 using namespace mfma;
-constexpr int kCat = kW2Pitch;
-constexpr int kOhPitch = 136;
-constexpr int kThreadsA = 64 * MM_BANK_WAVES;  // 8 waves, as policy_train_sample_kernel and policy_bank_kernel
-constexpr int kWavesA = MM_BANK_WAVES;
+constexpr int kWavesA = MM_BANK_WAVES;  // kernel A's 8 waves, as policy_bank_kernel's: mm_policy_bank_grid splits the workgroups
+static_assert(kThreadsA == 64 * kWavesA, "kernel A's workgroup");
 constexpr int kThreadsB = 320;
 constexpr int kG = MM_BANK_MAX_GROUPS;
 constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network, in floats
@@ -52,12 +48,6 @@ MM_DEV int group_of(const int (&start)[kG + 1], int b) {
 #pragma unroll
   for (int k = 1; k < kG; k++) g += start[k] <= b ? 1 : 0;
   return g;
-}
-
-// mm_policy_train's slicing of a group of nt tiles: whole tiles, at least 2 per slice, at most kMaxSlices slices
-MM_DEV int tiles_per_slice(int nt) {
-  const int per = (nt + kMaxSlices - 1) / kMaxSlices;
-  return per < 2 ? 2 : per;
 }
 
 // member-local sample i of a group of width w starting at column c0 -> the batch's sample index
@@ -157,239 +147,38 @@ struct SampleArgs {
   float *out0, *out1;  // actor: logp_taken, ratio; critic: value, unused
 };
 
-// ---- kernel A
+// ---- kernel A: mlp_sample_kernel of mm_policy_sample.h; a workgroup serves the group its index falls in
+struct Group {
+  const SampleArgs &p;
+  int g, lb, nblk;           // the workgroup's group = member, its index among the group's workgroups, and their number
+  unsigned c0, gw, row_len;  // the group's first column and its width
+  long long n_, row_base;    // the group's samples and its first scratch row
+  MM_DEV Group(const SampleArgs &a, const Tables &tb) : p(a) {
+    const int b = (int)blockIdx.x;
+    g = group_of(tb.block_start, b);
+    lb = b - tb.block_start[g]; nblk = tb.block_start[g + 1] - tb.block_start[g];
+    c0 = tb.col_start[g]; gw = tb.col_start[g + 1] - c0; row_len = tb.row_len;
+    n_ = (long long)gw * tb.rows; row_base = 32ll * tb.tile_start[g];
+  }
+  MM_DEV MMMlpParams net(int n_s, int k2, int n_out) const {  // member g of the stacked tensors
+    return {p.w.W1 + (long long)g * kHidden * n_s, p.w.b1 + g * kHidden, p.w.W2 + (long long)g * kHidden * k2, p.w.b2 + g * kHidden,
+            p.w.W3 + g * n_out * kHidden, p.w.b3 + g * n_out};
+  }
+  MM_DEV const float4 *frag() const { return p.frag + (long long)g * 2 * 4096; }
+  MM_DEV double *lossp() const { return p.lossp + (row_base >> 5); }
+  MM_DEV long long n() const { return n_; }
+  MM_DEV long long first_tile(int wave) const { return (long long)lb * kWavesA + wave; }  // tiles are counted from the group's start
+  MM_DEV long long tile_stride() const { return (long long)nblk * kWavesA; }
+  MM_DEV int count() const { return p.count[g]; }
+  MM_DEV const float *adv_sums() const { return p.adv_sums + 2 * g; }
+  MM_DEV bool ref_form() const { return p.ref_form != 0; }
+  MM_DEV long long sample(long long i, bool in_range) const { return in_range ? (long long)sample_of((unsigned)i, gw, c0, row_len) : 0; }
+  MM_DEV long long row(long long i) const { return row_base + i; }
+  MM_DEV float advantage(long long ag) const { return p.advantages ? p.advantages[ag] : p.returns[ag * p.ret_stride] - p.target_value[ag]; }
+};
+
 template <bool kCritic, bool kTrain>
-__global__ __launch_bounds__(kThreadsA) void bank_sample_kernel(const SampleArgs p, const Tables tb) {
-  __shared__ float4 sW1[4][4][64];   // [out tile][k-step / 4][lane]: 16 KB
-  __shared__ float4 sW2[4][16][64];  // [out tile][k-step / 4][lane]: 64 KB
-  __shared__ __attribute__((aligned(16))) float sWh[8][kHidden];
-  __shared__ __attribute__((aligned(16))) float sOh[kCritic ? 8 : 1][kOhPitch];
-  __shared__ __attribute__((aligned(16))) float sB1[kHidden], sB2[kHidden];
-  __shared__ float sBh[8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 31, h = lane >> 5;
-  const int n_s = p.n_s, n_a = p.n_a;
-  const int k2 = kCritic ? kHidden + n_a : kHidden;
-  const int n_out = kCritic ? 1 : n_a;
-  // ---- the workgroup's group and that member's tensors
-  const int b = (int)blockIdx.x;
-  const int g = group_of(tb.block_start, b);
-  const int lb = b - tb.block_start[g], nblk = tb.block_start[g + 1] - tb.block_start[g];
-  const unsigned c0 = tb.col_start[g], gw = tb.col_start[g + 1] - c0, row_len = tb.row_len;
-  const long long n = (long long)gw * tb.rows;
-  const long long row_base = 32ll * tb.tile_start[g];
-  const float *__restrict__ W1 = p.w.W1 + (long long)g * kHidden * n_s;
-  const float *__restrict__ W2 = p.w.W2 + (long long)g * kHidden * k2;
-  const float *__restrict__ W3 = p.w.W3 + g * n_out * kHidden;
-  for (int t = tid; t < 4 * 4 * 64; t += kThreadsA) {
-    const int l = t & 63, q = (t >> 6) & 3, m = t >> 8;
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int k = 2 * (4 * q + u) + (l >> 5);
-      v[u] = k < n_s ? W1[(32 * m + (l & 31)) * n_s + k] : 0.0f;
-    }
-    sW1[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  for (int t = tid; t < 4 * 16 * 64; t += kThreadsA) {
-    const int l = t & 63, q = (t >> 6) & 15, m = t >> 10;
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int s = 4 * q + u;
-      v[u] = W2[(32 * m + (l & 31)) * k2 + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
-    }
-    sW2[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  for (int t = tid; t < 8 * kHidden; t += kThreadsA) {
-    const int o = t / kHidden, c = t % kHidden;
-    sWh[o][c] = o < n_out ? W3[o * kHidden + c] : 0.0f;
-    if constexpr (kCritic) sOh[o][c] = o < n_a ? W2[c * k2 + kHidden + o] : 0.0f;
-  }
-  if (tid < kHidden) {
-    sB1[tid] = p.w.b1[g * kHidden + tid];
-    sB2[tid] = p.w.b2[g * kHidden + tid];
-  }
-  if (tid < 8) sBh[tid] = tid < n_out ? p.w.b3[g * n_out + tid] : 0.0f;
-  __syncthreads();
-  int nb = 0;
-  if (kTrain) nb = p.count[g];
-  const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
-  const bool ref_form = p.ref_form != 0;
-  const double sp_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[2 * g] : 0.0;
-  const double sn_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[2 * g + 1] : 0.0;
-  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
-  const float lo = 1.0f - p.clip_param, hi = 1.0f + p.clip_param;
-  const long long ntiles = (n + 31) / 32;
-  const float4 *const frag = p.frag + (long long)g * 2 * 4096;
-  double *const lossp = p.lossp + tb.tile_start[g];
-  for (long long tile = (long long)lb * kWavesA + wave; tile < ntiles; tile += (long long)nblk * kWavesA) {
-    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
-    const long long local = tile * 32 + j;
-    const bool inr = local < n;
-    const long long ag = inr ? (long long)sample_of((unsigned)local, gw, c0, row_len) : 0;  // the batch's sample index
-    const long long sr = row_base + local;                                                  // the scratch row
-    bool live = inr;
-    if (live && p.valid) live = p.valid[ag] != 0;
-    const float *row = p.obs + (live ? ag : 0) * p.obs_stride;
-    int act = live ? p.actions[ag * p.act_stride] : 0;
-    act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
-    float x[16];
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const int k = 2 * s + h;
-      x[s] = (live && k < n_s) ? row[k] : 0.0f;
-    }
-    if (kTrain) {
-      float4 *dst = reinterpret_cast<float4 *>(p.s_xs + sr * kXs + 16 * h);
-#pragma unroll
-      for (int gq = 0; gq < 4; gq++) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int c = 16 * h + 4 * gq + u;
-          v[u] = (live && c < n_s) ? row[c] : 0.0f;
-        }
-        dst[gq] = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-    f32x16 h1[4], h2[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int gq = 0; gq < 4; gq++) {
-        const float4 bq = *reinterpret_cast<const float4 *>(&sB1[32 * m + 8 * gq + 4 * h]);
-        acc[4 * gq] = bq.x; acc[4 * gq + 1] = bq.y; acc[4 * gq + 2] = bq.z; acc[4 * gq + 3] = bq.w;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; q++) acc = mfma4(sW1[m][q][lane], x[4 * q + 0], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3], acc);
-      h1[m] = relu(acc);
-      if (kTrain) store_tile(p.s_h1 + sr * kHidden + 32 * m + 4 * h, h1[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int gq = 0; gq < 4; gq++) {
-        float4 bq = *reinterpret_cast<const float4 *>(&sB2[32 * m + 8 * gq + 4 * h]);
-        if constexpr (kCritic) {  // the one-hot block of fc2: column 128 + act
-          const float4 o = *reinterpret_cast<const float4 *>(&sOh[act][32 * m + 8 * gq + 4 * h]);
-          bq.x += o.x; bq.y += o.y; bq.z += o.z; bq.w += o.w;
-        }
-        acc[4 * gq] = bq.x; acc[4 * gq + 1] = bq.y; acc[4 * gq + 2] = bq.z; acc[4 * gq + 3] = bq.w;
-      }
-      h2[m] = relu(fc2_tile<4>(sW2[m], h1, lane, acc));
-      if (kTrain) store_tile(p.s_h2 + sr * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- head, the objective's per-sample terms, dhead (both lane halves compute the same numbers)
-    float dhead[8];
-    double t_loss = 0.0;
-    if (kCritic) {
-      float v = 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[0][32 * m + frag_row(r, h)], v);
-      v = v + __shfl_xor(v, 32, 64) + sBh[0];
-      if (h == 0 && inr && p.out0) p.out0[ag] = live ? v : 0.0f;
-      if (!kTrain) continue;
-      const float ret = live ? p.returns[ag * p.ret_stride] : 0.0f;
-      const float d = v - ret;
-      float t_critic, dv;
-      critic_term(d, p.huber, t_critic, dv);
-      t_loss = (double)t_critic;
-      dhead[0] = live ? dv * inv_b : 0.0f;
-#pragma unroll
-      for (int o = 1; o < 8; o++) dhead[o] = 0.0f;
-    } else {
-      float logit[8];
-#pragma unroll
-      for (int o = 0; o < 8; o++) {
-        const float s = head_dot(h2, sWh[o], h, o < n_a);
-        logit[o] = o < n_a ? s + sBh[o] : -INFINITY;
-      }
-      const float mx = max8(logit);
-      float se = 0.0f;
-#pragma unroll
-      for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
-      const float lse = mx + logf(se);
-      const float lp_a = logp_taken(logit, lse, act);
-      if (!kTrain) {
-        if (h == 0 && inr && p.out0) p.out0[ag] = live ? lp_a : 0.0f;
-        continue;
-      }
-      const float olp = live ? p.old_logp[ag] : 0.0f;
-      const float r = expf(lp_a - olp);
-      const float c = fminf(fmaxf(r, lo), hi);
-      float wsel;
-      if (ref_form) {
-        ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_loss, wsel);
-      } else {
-        float adv = 0.0f;
-        if (live) adv = p.advantages ? p.advantages[ag] : p.returns[ag * p.ret_stride] - p.target_value[ag];
-        ppo_clip_flat(adv, lo, hi, r, c, t_loss, wsel);
-      }
-      const float g_lp = live ? -inv_b * wsel * r : 0.0f;  // d loss / d logp_taken
-#pragma unroll
-      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
-      if (h == 0 && inr) {
-        if (p.out0) p.out0[ag] = live ? lp_a : 0.0f;
-        if (p.out1) p.out1[ag] = live ? r : 0.0f;
-      }
-    }
-    {
-      float4 *dst = reinterpret_cast<float4 *>(p.s_dh + sr * kDh + 8 * h);
-      if (h == 0) {
-        dst[0] = make_float4(dhead[0], dhead[1], dhead[2], dhead[3]);
-        dst[1] = make_float4(dhead[4], dhead[5], dhead[6], dhead[7]);
-      } else {
-        dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        dst[1] = make_float4(0.0f, 0.0f, 0.0f, kCritic ? (float)act : 0.0f);  // column kActCol
-      }
-    }
-    {
-      double pl = (live && h == 0) ? t_loss : 0.0;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) pl += __shfl_xor(pl, o, 64);
-      if (lane == 0) lossp[tile] = pl;
-    }
-    // ---- dz2 = (W3^T dhead) . [h2 > 0], in accumulator form (reuses h2's registers)
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-#pragma unroll
-      for (int gq = 0; gq < 4; gq++) {
-        const int f = 32 * m + 8 * gq + 4 * h;
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-#pragma unroll
-        for (int o = 0; o < (kCritic ? 1 : 8); o++) {
-          const float4 wa = *reinterpret_cast<const float4 *>(&sWh[o][f]);
-          s0 = fmaf(dhead[o], wa.x, s0);
-          s1 = fmaf(dhead[o], wa.y, s1);
-          s2 = fmaf(dhead[o], wa.z, s2);
-          s3 = fmaf(dhead[o], wa.w, s3);
-        }
-        h2[m][4 * gq + 0] = h2[m][4 * gq + 0] > 0.0f ? s0 : 0.0f;
-        h2[m][4 * gq + 1] = h2[m][4 * gq + 1] > 0.0f ? s1 : 0.0f;
-        h2[m][4 * gq + 2] = h2[m][4 * gq + 2] > 0.0f ? s2 : 0.0f;
-        h2[m][4 * gq + 3] = h2[m][4 * gq + 3] > 0.0f ? s3 : 0.0f;
-      }
-      store_tile(p.s_dz2 + sr * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- dz1 = (W2[:, :128]^T dz2) . [h1 > 0]: 4 output tiles x 64 k-steps, A fragments from global memory
-    const unsigned vlane = opaque_lane(lane);
-#pragma unroll
-    for (int mt = 0; mt < 4; mt++) {
-      const f32x16 acc = dz1_tile(frag, mt, vlane, h2);
-#pragma unroll
-      for (int gq = 0; gq < 4; gq++) {
-        float4 *dst = reinterpret_cast<float4 *>(p.s_dz1 + sr * kHidden + 32 * mt + 4 * h);
-        dst[2 * gq] = make_float4(h1[mt][4 * gq] > 0.0f ? acc[4 * gq] : 0.0f, h1[mt][4 * gq + 1] > 0.0f ? acc[4 * gq + 1] : 0.0f,
-                                  h1[mt][4 * gq + 2] > 0.0f ? acc[4 * gq + 2] : 0.0f, h1[mt][4 * gq + 3] > 0.0f ? acc[4 * gq + 3] : 0.0f);
-      }
-    }
-  }
-}
+constexpr auto bank_sample_kernel = mlp_sample_kernel<kCritic, kTrain, Group, SampleArgs, Tables>;
 
 // ---- kernel B: workgroup b = slice b - slice_start[g] of group g
 template <bool kCritic>
@@ -408,8 +197,6 @@ __global__ __launch_bounds__(kThreadsB) void bank_wgrad_kernel(const float *__re
 }
 
 // ---- kernel C: member blockIdx.y; element t = its partial blocks summed in workgroup order; the last workgroup folds its loss
-static int fold_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
-
 __global__ __launch_bounds__(256) void bank_fold_kernel(const float *__restrict__ part_all, const Tables tb, int n_s, int k2, int n_out,
                                                         MMMlpParams gr, const double *__restrict__ lossp, const int *__restrict__ count,
                                                         int loss_mode, float *__restrict__ loss) {
@@ -432,7 +219,7 @@ __global__ __launch_bounds__(256) void bank_fold_kernel(const float *__restrict_
   t -= kHidden * n_s;
   if (t < kHidden) { gr.b1[k * kHidden + t] = fold<Part::kSize>(part, slices, Part::kb1 + t); return; }
   t -= kHidden;
-  if (t < kHidden * k2) { const int o = t / k2, c = t % k2; gr.W2[(long long)k * kHidden * k2 + t] = fold<Part::kSize>(part, slices, Part::kW2 + o * kCat + c); return; }
+  if (t < kHidden * k2) { const int o = t / k2, c = t % k2; gr.W2[(long long)k * kHidden * k2 + t] = fold<Part::kSize>(part, slices, Part::kW2 + o * kW2Pitch + c); return; }
   t -= kHidden * k2;
   if (t < kHidden) { gr.b2[k * kHidden + t] = fold<Part::kSize>(part, slices, Part::kb2 + t); return; }
   t -= kHidden;
@@ -464,8 +251,7 @@ static bool plan(int64_t rows, int64_t row_len, int32_t K, const int64_t *col_st
   P.cap_slices = 0;
   for (int k = 0; k < K; k++) {
     const long long nk = (col_start[k + 1] - col_start[k]) * rows, nt = (nk + 31) / 32;
-    long long per = (nt + kMaxSlices - 1) / kMaxSlices;
-    if (per < 2) per = 2;
+    const long long per = tiles_per_slice(nt);
     const long long cap = (nt + 1) / 2 < kMaxSlices ? (nt + 1) / 2 : kMaxSlices;
     tb.col_start[k] = (int)col_start[k];
     tb.tile_start[k + 1] = tb.tile_start[k] + (int)nt;
@@ -512,10 +298,6 @@ static Scratch scratch_of(const Plan &P, int K) {
   return S;
 }
 
-static bool shapes_ok(int32_t n_s, int32_t hidden, int32_t n_a) {
-  return n_s >= 25 && n_s <= 32 && hidden == kHidden && n_a >= 1 && n_a <= 8;
-}
-
 }  // namespace bank_train
 }  // namespace mm
 
@@ -526,9 +308,8 @@ extern "C" int32_t mm_policy_bank_eval(const float *obs, int64_t obs_stride, int
   using namespace mm::bank_train;
   if (!actors && !critics) return MM_ERR_INVALID_ARG;
   if ((actors && !complete(actors)) || (critics && !complete(critics))) return MM_ERR_INVALID_ARG;
-  if (!shapes_ok(n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
   Plan P;
-  if (!plan(rows, row_len, K, col_start, true, P)) return MM_ERR_INVALID_ARG;
+  if (!plan(rows, row_len, K, col_start, true, P) || !shape_ok(P.n, n_s, hidden, n_a, kHidden)) return MM_ERR_INVALID_ARG;
   if (P.n == 0) return MM_OK;
   if ((actors != nullptr) != (logp_taken != nullptr) || (critics != nullptr) != (value != nullptr)) return MM_ERR_INVALID_ARG;
   if (!obs || !actions || obs_stride < n_s) return MM_ERR_INVALID_ARG;
@@ -569,13 +350,12 @@ extern "C" int32_t mm_policy_bank_train(const float *obs, int64_t obs_stride, in
   if ((actors != nullptr) != (actor_grads != nullptr) || (critics != nullptr) != (critic_grads != nullptr)) return MM_ERR_INVALID_ARG;
   if ((actors && (!complete(actors) || !complete(actor_grads))) || (critics && (!complete(critics) || !complete(critic_grads))))
     return MM_ERR_INVALID_ARG;
-  if (!shapes_ok(n_s, hidden, n_a)) return MM_ERR_INVALID_ARG;
   if (critic_loss != MM_PT_CRITIC_MSE && critic_loss != MM_PT_CRITIC_HUBER) return MM_ERR_INVALID_ARG;
   if (form != MM_PT_FORM_REFERENCE && form != MM_PT_FORM_PER_SAMPLE) return MM_ERR_INVALID_ARG;
   if (!(clip_param >= 0.0f)) return MM_ERR_INVALID_ARG;
   if ((!actors && (logp_taken || ratio)) || (!critics && value)) return MM_ERR_INVALID_ARG;
   Plan P;
-  if (!plan(rows, row_len, K, col_start, true, P)) return MM_ERR_INVALID_ARG;
+  if (!plan(rows, row_len, K, col_start, true, P) || !shape_ok(P.n, n_s, hidden, n_a, kHidden)) return MM_ERR_INVALID_ARG;
   const Scratch S = scratch_of(P, K);
   if (P.n > 0) {  // (n == 0: the per-sample inputs and the scratch are not looked at and may be NULL, as in mm_policy_train)
     if (actors && ((advantages != nullptr) == (target_value != nullptr))) return MM_ERR_INVALID_ARG;
@@ -588,15 +368,8 @@ extern "C" int32_t mm_policy_bank_train(const float *obs, int64_t obs_stride, in
   if (hipMemsetAsync(loss, 0, (size_t)K * 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
   if (P.n == 0) {  // nothing to contract: zero gradients (K members of each tensor), zero sums
     if (adv_sums && hipMemsetAsync(adv_sums, 0, (size_t)K * 2 * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    for (int net = 0; net < 2; net++) {
-      const MMMlpParams *g = net ? critic_grads : actor_grads;
-      if (!g) continue;
-      const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
-      float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
-      const size_t gsz[6] = {(size_t)kHidden * n_s, (size_t)kHidden, (size_t)kHidden * k2, (size_t)kHidden, (size_t)n_out * kHidden, (size_t)n_out};
-      for (int t = 0; t < 6; t++)
-        if (hipMemsetAsync(gp[t], 0, gsz[t] * K * sizeof(float), s) != hipSuccess) return MM_ERR_DEVICE;
-    }
+    if (actors && !zero_mlp_grads(s, actor_grads, kHidden, n_s, kHidden, n_a, K)) return MM_ERR_DEVICE;
+    if (critics && !zero_mlp_grads(s, critic_grads, kHidden, n_s, k2c, 1, K)) return MM_ERR_DEVICE;
     return MM_OK;
   }
   float *sc = (float *)scratch;
@@ -627,16 +400,11 @@ extern "C" int32_t mm_policy_bank_train(const float *obs, int64_t obs_stride, in
     const int k2 = net ? k2c : kHidden, n_out = net ? 1 : n_a;
     a.w = *w; a.frag = (const float4 *)(sc + S.frag + net * kFrag);
     a.out0 = net ? value : logp_taken; a.out1 = net ? nullptr : ratio;
-    if (net) {
-      hipLaunchKernelGGL((bank_sample_kernel<true, true>), dim3(grid_a), dim3(kThreadsA), 0, s, a, P.tb);
-      hipLaunchKernelGGL((bank_wgrad_kernel<true>), dim3(grid_b), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2, a.s_dh,
-                         a.s_xs, P.tb, sc + S.part);
-    } else {
-      hipLaunchKernelGGL((bank_sample_kernel<false, true>), dim3(grid_a), dim3(kThreadsA), 0, s, a, P.tb);
-      hipLaunchKernelGGL((bank_wgrad_kernel<false>), dim3(grid_b), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1, a.s_h2, a.s_dz2, a.s_dh,
-                         a.s_xs, P.tb, sc + S.part);
-    }
-    hipLaunchKernelGGL(bank_fold_kernel, dim3((fold_elems(n_s, k2, n_out) + 255) / 256 + 1, K), dim3(256), 0, s,
+    hipLaunchKernelGGL((net ? bank_sample_kernel<true, true> : bank_sample_kernel<false, true>), dim3(grid_a), dim3(kThreadsA), 0, s, a,
+                       P.tb);
+    hipLaunchKernelGGL((net ? bank_wgrad_kernel<true> : bank_wgrad_kernel<false>), dim3(grid_b), dim3(kThreadsB), 0, s, a.s_h1, a.s_dz1,
+                       a.s_h2, a.s_dz2, a.s_dh, a.s_xs, P.tb, sc + S.part);
+    hipLaunchKernelGGL(bank_fold_kernel, dim3((fold_elems(kHidden, n_s, k2, n_out) + 255) / 256 + 1, K), dim3(256), 0, s,
                        (const float *)(sc + S.part), P.tb, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads,
                        (const double *)lossp, (const int *)count, net ? 0 : (ref_form ? 2 : 1), loss + net);
   }

@@ -1,5 +1,5 @@
 // mm_policy_mfma.h -- what the policy kernel files share (mm_policy_gi.hip, mm_policy_gi_train.hip, mm_policy_train.hip, the
-// hidden-512 files), and at its end the small host helpers of the training entries (argument checks, the n == 0 path).
+// hidden-512 files, the bank's), and at its end the small host helpers of the training entries (argument checks, the n == 0 path).
 // The device helpers are force-inlined and parametrised by compile-time sizes alone: the kernels that use them keep their
 // names, their shared memory and their register budget (255 / 256 VGPRs, no spills), and no floating-point operation moves.
 //
@@ -20,7 +20,17 @@
 // machine code as it was.  Hence thread-derived indices are taken from threadIdx inside a helper or as unsigned (a plain int
 // argument loses its range), the per-logit terms (exp_shifted, dlogit) are per-element with the 8-way loop in the kernel, and
 // three pieces stay in the kernels: the value head's dot product (head_dot's FMAs with the row fixed), fc2's staging in
-// mm_policy_train.hip (its row pitch is not a constant there) and the per-tile loss butterfly.
+// mm_policy_sample.h (its row pitch is not a constant there) and the per-tile loss butterfly.
+// A whole kernel body is shared as the kernel template itself, with a policy type for what differs, not as a helper
+// (mm_policy_sample.h, kernel A of mm_policy_train.hip and of the bank).  Measured by cross-compiling for gfx950: with the body in a
+// force-inlined function template that the kernel calls, mm_policy_train.hip's kernel A <actor, train> goes from 255 VGPRs / 71
+// spilled SGPR lanes to 253 / 64 and <critic, train> from 232 / 18 to 233 / 16; as the kernel template, with a policy of trivial
+// members, all eight kernels of that file are instruction for instruction the recorded ones.  The arguments stay the kernels' own
+// by-value blocks (a parameter pack): the bank's two blocks joined into one struct, at the same offsets, move its SGPR figures
+// (<critic, eval> 80 -> 79, <actor, train> 117 -> 89 spilled lanes); as two arguments all its figures are the recorded ones.  What
+// the bank's policy computes once in its constructor matters as well: with its workgroup index and count read from the table per
+// use, VGPRs move (<critic, train> 246 -> 233, measured in the joined-struct form).
+// Kernel C stays written out in both files: as a force-inlined helper its index map changes policy_train_fold_kernel's code.
 //
 // A persistent kernel's tile loop starts with `asm volatile("" ::: "memory")`: the weight fragments are tile-invariant, and
 // without the fence the compiler hoists their LDS reads out of the loop, which costs 320 registers and spills the activations.
@@ -45,6 +55,13 @@ constexpr int kW2Pitch = 160;      // row pitch of the dW2 partial: 5 column til
 constexpr long long kHdr = 64;     // scratch header, in floats: [0] (int) B, the number of valid samples
 
 MM_DEV int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// Kernel B's slicing of ntiles 32-sample tiles (an int or a long long): whole tiles, at least 2 per slice, at most kMaxSlices slices
+template <typename T>
+__host__ __device__ inline T tiles_per_slice(T ntiles) {
+  const T per = (ntiles + kMaxSlices - 1) / kMaxSlices;
+  return per < 2 ? 2 : per;
+}
 
 // GI layer-1 fragment q -> (output tile m, k-step s): tile 0 = fc11 (3 k-steps), tiles 1-2 = fc12, 3-4 = fc13 (5 k-steps each)
 MM_DEV void l1_step(int q, int &m, int &s) {
@@ -398,8 +415,7 @@ static Layout scratch_layout(long long n, long long frag_floats, int pitch1, int
   L.xs = L.dh + L.n_pad * kDh;
   L.lossp = L.xs + L.n_pad * kXs;  // double[ntiles][sums]
   L.part = L.lossp + 2 * sums * L.ntiles;
-  long long tiles_per = (L.ntiles + kMaxSlices - 1) / kMaxSlices;
-  if (tiles_per < 2) tiles_per = 2;
+  const long long tiles_per = tiles_per_slice(L.ntiles);
   L.slices = (int)((L.ntiles + tiles_per - 1) / tiles_per);
   if (L.slices < 1) L.slices = 1;
   L.slice_rows = tiles_per * 32;
@@ -425,12 +441,15 @@ static bool chunk_ok(int64_t chunk) { return chunk > 0 && chunk % 64 == 0 && chu
 template <typename T>
 static T *shifted(T *p, long long by) { return p ? p + by : nullptr; }
 
-// zeroes the six gradient tensors of a network with fc2 rows of k2 floats and n_out outputs; false: an enqueue failed
-static bool zero_mlp_grads(hipStream_t s, const MMMlpParams *g, int hidden, int n_s, int k2, int n_out) {
+// the gradient elements of a network with fc2 rows of k2 floats and n_out outputs: kernel C's threads
+static int fold_elems(int hidden, int n_s, int k2, int n_out) { return hidden * n_s + hidden + hidden * k2 + hidden + n_out * hidden + n_out; }
+
+// zeroes the six gradient tensors of `members` stacked networks of that shape; false: an enqueue failed
+static bool zero_mlp_grads(hipStream_t s, const MMMlpParams *g, int hidden, int n_s, int k2, int n_out, int members = 1) {
   float *const gp[6] = {g->W1, g->b1, g->W2, g->b2, g->W3, g->b3};
   const size_t gsz[6] = {(size_t)hidden * n_s, (size_t)hidden, (size_t)hidden * k2, (size_t)hidden, (size_t)n_out * hidden, (size_t)n_out};
   for (int k = 0; k < 6; k++)
-    if (hipMemsetAsync(gp[k], 0, gsz[k] * sizeof(float), s) != hipSuccess) return false;
+    if (hipMemsetAsync(gp[k], 0, gsz[k] * members * sizeof(float), s) != hipSuccess) return false;
   return true;
 }
 

@@ -1,25 +1,11 @@
 // mm_policy_train.hip -- loss and parameter gradient of MAPPO's separate actor and critic (include/mm_policy_train.h), and the
 // forward-only mm_policy_eval.
 //
-// The shape is mm_policy_gi_train.hip's, in the layout and from the pieces of mm_policy_mfma.h.  Both networks are
-// "n_s -> 128 -> 128 -> head", so ONE kernel template serves them (kCritic) and, without the backward, mm_policy_eval (!kTrain).
+// The shape is mm_policy_gi_train.hip's, in the layout and from the pieces of mm_policy_mfma.h.
 //
 //   prep      W2[:, :128]^T of each given network in MFMA A-fragment order into the scratch (64 KB each), and B = the number
 //             of valid samples.
-//   kernel A  per sample: fc1 (K = n_s padded to 32: 16 k-steps x 4 tiles), fc2 (K = 128: 64 k-steps x 4 tiles), the head on
-//             the VALU (<= 8 rows), then the loss terms and dlogit / dvalue; dz2 = W3^T dhead . [h2 > 0] on the VALU;
-//             dz1 = (W2[:, :128]^T dz2) . [h1 > 0] as a second 128 x 128 MFMA contraction whose A operand comes from the
-//             fragment array `prep` wrote (global, L2 resident: reading transposed fragments out of the one staged LDS copy
-//             would put the 64 lanes of a read on 8 banks -- the trap recorded at dz1_tile in mm_policy_mfma.h).
-//             The critic's fc2 has K = 128 + n_a with a one-hot block: in the forward that block is a column gather,
-//             z2 = b2 + W2[:, 128 + a_j] + W2[:, :128] h1, added where the accumulator is initialised, out of an [8][128]
-//             LDS table (rows padded to 136 floats: lanes with different actions land on different banks); in the backward
-//             dW2[:, 128 + a] = sum_j dz2_j [a_j = a] is a fifth column tile of kernel B whose B operand is the one-hot row
-//             rebuilt from the action kept in the sample's head row.  No gradient flows into the one-hot input.
-//             Stores h1, dz1, h2, dz2 (128 each), dhead (16: the actor's dlogit 0..7 | the critic's dvalue in column 0 and
-//             the clamped action, as a float, in column 15) and x (32: the observation, zeros past n_s) per sample in
-//             [sample][feature] order, gradient rows of masked / out-of-range samples as exact zeros, and one loss partial
-//             per 32 samples in fp64.
+//   kernel A  mlp_sample_kernel of mm_policy_sample.h, on the one network and the contiguous samples of a call (`Flat`).
 //   kernel B  contractions over the sample dimension, the sample index as the MFMA k dimension, both operands coalesced row
 //             reads of the scratch: dW2 = dz2^T [h1 | one_hot] (4 x 4 or 4 x 5 tiles), dW3 = dhead^T h2 (4 tiles), dW1 =
 //             dz1^T x (4 tiles), bias sums on the VALU from the A operands.  5 waves per workgroup: wave w < 4 owns output
@@ -29,14 +15,13 @@
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
 // The actor's three kernels run first, then the critic's over the same scratch (stream order).
 #include "mm_policy_chunked.h"  // PassArgs and the launch helpers' declarations; mm_policy_mfma.h and the public header
+#include "mm_policy_sample.h"   // kernel A
 
 namespace mm {
 namespace pt {
 
 using namespace mfma;
 constexpr int kCat = kW2Pitch;  // row pitch of the dW2 partial: 128 + the one-hot tile
-constexpr int kOhPitch = 136;   // row pitch of the one-hot column table in LDS
-constexpr int kThreadsA = 512;  // 8 waves = 2 per SIMD
 constexpr int kThreadsB = 320;  // 5 waves
 
 constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network, in floats: [out tile 4][k chunk 4][group 4][lane 64] float4
@@ -81,223 +66,26 @@ struct SampleArgs {
   float *out0, *out1;  // actor: logp_taken, ratio; critic: value, unused
 };
 
-// ---- kernel A
+// ---- kernel A: mlp_sample_kernel of mm_policy_sample.h on the one network and the contiguous samples of a SampleArgs
+struct Flat {
+  const SampleArgs &p;
+  MM_DEV explicit Flat(const SampleArgs &a) : p(a) {}
+  MM_DEV long long n() const { return p.n; }
+  MM_DEV MMMlpParams net(int, int, int) const { return p.w; }
+  MM_DEV int count() const { return *p.count; }
+  MM_DEV const float *adv_sums() const { return p.adv_sums; }
+  MM_DEV bool ref_form() const { return p.adv_sums != nullptr; }
+  MM_DEV const float4 *frag() const { return p.frag; }
+  MM_DEV double *lossp() const { return p.lossp; }
+  MM_DEV long long first_tile(int wave) const { return (long long)blockIdx.x * (kThreadsA / 64) + wave; }
+  MM_DEV long long tile_stride() const { return (long long)gridDim.x * (kThreadsA / 64); }
+  MM_DEV long long sample(long long i, bool) const { return i; }
+  MM_DEV long long row(long long i) const { return i; }
+  MM_DEV float advantage(long long ag) const { return p.advantages[ag]; }
+};
+
 template <bool kCritic, bool kTrain>
-__global__ __launch_bounds__(kThreadsA) void policy_train_sample_kernel(const SampleArgs p) {
-  __shared__ float4 sW1[4][4][64];   // [out tile][k-step / 4][lane]: 16 KB
-  __shared__ float4 sW2[4][16][64];  // [out tile][k-step / 4][lane]: 64 KB
-  __shared__ __attribute__((aligned(16))) float sWh[8][kHidden];  // head rows (zero past the head's width): 4 KB
-  __shared__ __attribute__((aligned(16))) float sOh[kCritic ? 8 : 1][kOhPitch];  // critic: fc2's one-hot columns, [action][feature]
-  __shared__ __attribute__((aligned(16))) float sB1[kHidden], sB2[kHidden];
-  __shared__ float sBh[8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 31, h = lane >> 5;
-  const int n_s = p.n_s, n_a = p.n_a;
-  const int k2 = kCritic ? kHidden + n_a : kHidden;  // fc2's row length
-  const int n_out = kCritic ? 1 : n_a;
-  for (int t = tid; t < 4 * 4 * 64; t += kThreadsA) {
-    const int l = t & 63, q = (t >> 6) & 3, m = t >> 8;
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int k = 2 * (4 * q + u) + (l >> 5);
-      v[u] = k < n_s ? p.w.W1[(32 * m + (l & 31)) * n_s + k] : 0.0f;
-    }
-    sW1[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  for (int t = tid; t < 4 * 16 * 64; t += kThreadsA) {
-    const int l = t & 63, q = (t >> 6) & 15, m = t >> 10;
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int s = 4 * q + u;
-      v[u] = p.w.W2[(32 * m + (l & 31)) * k2 + 32 * (s >> 4) + frag_row(s & 15, l >> 5)];
-    }
-    sW2[m][q][l] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  for (int t = tid; t < 8 * kHidden; t += kThreadsA) {
-    const int o = t / kHidden, c = t % kHidden;
-    sWh[o][c] = o < n_out ? p.w.W3[o * kHidden + c] : 0.0f;
-    if constexpr (kCritic) sOh[o][c] = o < n_a ? p.w.W2[c * k2 + kHidden + o] : 0.0f;
-  }
-  if (tid < kHidden) {
-    sB1[tid] = p.w.b1[tid];
-    sB2[tid] = p.w.b2[tid];
-  }
-  if (tid < 8) sBh[tid] = tid < n_out ? p.w.b3[tid] : 0.0f;
-  __syncthreads();
-  int nb = 0;
-  if (kTrain) nb = *p.count;
-  const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
-  const bool ref_form = p.adv_sums != nullptr;
-  const double sp_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[0] : 0.0;
-  const double sn_d = (kTrain && !kCritic && ref_form) ? (double)p.adv_sums[1] : 0.0;
-  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
-  const float lo = 1.0f - p.clip_param, hi = 1.0f + p.clip_param;
-  const long long n = p.n, ntiles = (n + 31) / 32;
-  constexpr int kWaves = kThreadsA / 64;
-  for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
-    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
-    const long long ag = tile * 32 + j;
-    bool live = ag < n;
-    if (live && p.valid) live = p.valid[ag] != 0;
-    const float *row = p.obs + (live ? ag : 0) * p.obs_stride;
-    int act = live ? p.actions[ag * p.act_stride] : 0;
-    act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
-    float x[16];
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      const int k = 2 * s + h;
-      x[s] = (live && k < n_s) ? row[k] : 0.0f;
-    }
-    if (kTrain) {  // x row of the scratch: columns 16 h .. 16 h + 15, zeros past n_s and for a masked sample
-      float4 *dst = reinterpret_cast<float4 *>(p.s_xs + ag * kXs + 16 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int c = 16 * h + 4 * g + u;
-          v[u] = (live && c < n_s) ? row[c] : 0.0f;
-        }
-        dst[g] = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-    f32x16 h1[4], h2[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const float4 b = *reinterpret_cast<const float4 *>(&sB1[32 * m + 8 * g + 4 * h]);
-        acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; q++) acc = mfma4(sW1[m][q][lane], x[4 * q + 0], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3], acc);
-      h1[m] = relu(acc);
-      if (kTrain) store_tile(p.s_h1 + ag * kHidden + 32 * m + 4 * h, h1[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        float4 b = *reinterpret_cast<const float4 *>(&sB2[32 * m + 8 * g + 4 * h]);
-        if constexpr (kCritic) {  // the one-hot block of fc2: column 128 + act
-          const float4 o = *reinterpret_cast<const float4 *>(&sOh[act][32 * m + 8 * g + 4 * h]);
-          b.x += o.x; b.y += o.y; b.z += o.z; b.w += o.w;
-        }
-        acc[4 * g] = b.x; acc[4 * g + 1] = b.y; acc[4 * g + 2] = b.z; acc[4 * g + 3] = b.w;
-      }
-      h2[m] = relu(fc2_tile<4>(sW2[m], h1, lane, acc));
-      if (kTrain) store_tile(p.s_h2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- head, the objective's per-sample terms, dhead (both lane halves compute the same numbers)
-    float dhead[8];
-    double t_loss = 0.0;
-    if (kCritic) {
-      float v = 0.0f;
-#pragma unroll
-      for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[0][32 * m + frag_row(r, h)], v);
-      v = v + __shfl_xor(v, 32, 64) + sBh[0];
-      if (h == 0 && ag < n && p.out0) p.out0[ag] = live ? v : 0.0f;
-      if (!kTrain) continue;
-      const float ret = live ? p.returns[ag * p.ret_stride] : 0.0f;
-      const float d = v - ret;
-      float t_critic, dv;
-      critic_term(d, p.huber, t_critic, dv);
-      t_loss = (double)t_critic;
-      dhead[0] = live ? dv * inv_b : 0.0f;
-#pragma unroll
-      for (int o = 1; o < 8; o++) dhead[o] = 0.0f;
-    } else {
-      float logit[8];
-#pragma unroll
-      for (int o = 0; o < 8; o++) {
-        const float s = head_dot(h2, sWh[o], h, o < n_a);
-        logit[o] = o < n_a ? s + sBh[o] : -INFINITY;
-      }
-      const float mx = max8(logit);
-      float se = 0.0f;
-#pragma unroll
-      for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
-      const float lse = mx + logf(se);
-      const float lp_a = logp_taken(logit, lse, act);
-      if (!kTrain) {
-        if (h == 0 && ag < n && p.out0) p.out0[ag] = live ? lp_a : 0.0f;
-        continue;
-      }
-      const float olp = live ? p.old_logp[ag] : 0.0f;
-      const float r = expf(lp_a - olp);
-      const float c = fminf(fmaxf(r, lo), hi);
-      float wsel;
-      if (ref_form) ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_loss, wsel);
-      else ppo_clip_flat(live ? p.advantages[ag] : 0.0f, lo, hi, r, c, t_loss, wsel);
-      const float g_lp = live ? -inv_b * wsel * r : 0.0f;  // d loss / d logp_taken
-#pragma unroll
-      for (int o = 0; o < 8; o++) dhead[o] = (o < n_a) ? dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
-      if (h == 0 && ag < n) {
-        if (p.out0) p.out0[ag] = live ? lp_a : 0.0f;
-        if (p.out1) p.out1[ag] = live ? r : 0.0f;
-      }
-    }
-    {
-      float4 *dst = reinterpret_cast<float4 *>(p.s_dh + ag * kDh + 8 * h);
-      if (h == 0) {
-        dst[0] = make_float4(dhead[0], dhead[1], dhead[2], dhead[3]);
-        dst[1] = make_float4(dhead[4], dhead[5], dhead[6], dhead[7]);
-      } else {
-        dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        dst[1] = make_float4(0.0f, 0.0f, 0.0f, kCritic ? (float)act : 0.0f);  // column kActCol
-      }
-    }
-    // loss partial of this tile: lanes of half 0, fixed butterfly
-    {
-      double pl = (live && h == 0) ? t_loss : 0.0;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) pl += __shfl_xor(pl, o, 64);
-      if (lane == 0) p.lossp[tile] = pl;
-    }
-    // ---- dz2 = (W3^T dhead) . [h2 > 0], in accumulator form (reuses h2's registers)
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        // the lane's features 32 m + 8 g + 4 h .. + 3 are contiguous in a head row: one ds_read_b128 per row.  Rows past
-        // the head's width are zero in sWh and their dhead is zero, so all rows are summed without a branch.
-        const int f = 32 * m + 8 * g + 4 * h;
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-#pragma unroll
-        for (int o = 0; o < (kCritic ? 1 : 8); o++) {
-          const float4 wa = *reinterpret_cast<const float4 *>(&sWh[o][f]);
-          s0 = fmaf(dhead[o], wa.x, s0);
-          s1 = fmaf(dhead[o], wa.y, s1);
-          s2 = fmaf(dhead[o], wa.z, s2);
-          s3 = fmaf(dhead[o], wa.w, s3);
-        }
-        h2[m][4 * g + 0] = h2[m][4 * g + 0] > 0.0f ? s0 : 0.0f;
-        h2[m][4 * g + 1] = h2[m][4 * g + 1] > 0.0f ? s1 : 0.0f;
-        h2[m][4 * g + 2] = h2[m][4 * g + 2] > 0.0f ? s2 : 0.0f;
-        h2[m][4 * g + 3] = h2[m][4 * g + 3] > 0.0f ? s3 : 0.0f;
-      }
-      store_tile(p.s_dz2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- dz1 = (W2[:, :128]^T dz2) . [h1 > 0]: 4 output tiles x 64 k-steps, A fragments from global memory
-    const unsigned vlane = opaque_lane(lane);
-#pragma unroll
-    for (int mt = 0; mt < 4; mt++) {
-      const f32x16 acc = dz1_tile(p.frag, mt, vlane, h2);
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        float4 *dst = reinterpret_cast<float4 *>(p.s_dz1 + ag * kHidden + 32 * mt + 4 * h);
-        dst[2 * g] = make_float4(h1[mt][4 * g] > 0.0f ? acc[4 * g] : 0.0f, h1[mt][4 * g + 1] > 0.0f ? acc[4 * g + 1] : 0.0f,
-                                 h1[mt][4 * g + 2] > 0.0f ? acc[4 * g + 2] : 0.0f, h1[mt][4 * g + 3] > 0.0f ? acc[4 * g + 3] : 0.0f);
-      }
-    }
-  }
-}
+constexpr auto policy_train_sample_kernel = mlp_sample_kernel<kCritic, kTrain, Flat, SampleArgs>;
 
 // ---- kernel B: one workgroup = one slice of samples [row0, row1), rows are whole 32-sample tiles inside n_pad
 template <bool kCritic>
@@ -309,8 +97,6 @@ __global__ __launch_bounds__(kThreadsB) void policy_train_wgrad_kernel(
 
 // ---- kernel C: gradient element t = sum over the partial blocks in workgroup order; the last workgroup folds the loss
 MM_DEV float fold(const float *__restrict__ part, int slices, int off) { return mfma::fold<Part::kSize>(part, slices, off); }
-
-static int fold_elems(int n_s, int k2, int n_out) { return kHidden * n_s + kHidden + kHidden * k2 + kHidden + n_out * kHidden + n_out; }
 
 // loss_mode 0: sum / B (critic); 1: -sum / B (actor, per-sample form); 2: -sum / B^2 (actor, reference form)
 __global__ __launch_bounds__(256) void policy_train_fold_kernel(const float *__restrict__ part, int slices, int n_s, int k2, int n_out,
@@ -368,17 +154,13 @@ void launch_sample(hipStream_t s, bool critic, const PassArgs &p) {
   a.s_h1 = p.rows.h1; a.s_dz1 = p.rows.dz1; a.s_h2 = p.rows.h2; a.s_dz2 = p.rows.dz2; a.s_dh = p.rows.dh; a.s_xs = p.rows.xs;
   a.lossp = p.lossp; a.out0 = p.out0; a.out1 = p.out1;
   const unsigned grid = grid_a((p.n + 31) / 32);
-  if (critic) hipLaunchKernelGGL((policy_train_sample_kernel<true, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
-  else hipLaunchKernelGGL((policy_train_sample_kernel<false, true>), dim3(grid), dim3(kThreadsA), 0, s, a);
+  hipLaunchKernelGGL((critic ? policy_train_sample_kernel<true, true> : policy_train_sample_kernel<false, true>), dim3(grid),
+                     dim3(kThreadsA), 0, s, a);
 }
 
 void launch_wgrad(hipStream_t s, bool critic, const SampleRows &r, long long n_pad, long long slice_rows, int slices, float *part) {
-  if (critic)
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<true>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
-                       n_pad, slice_rows, part);
-  else
-    hipLaunchKernelGGL((policy_train_wgrad_kernel<false>), dim3(slices), dim3(kThreadsB), 0, s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs,
-                       n_pad, slice_rows, part);
+  hipLaunchKernelGGL((critic ? policy_train_wgrad_kernel<true> : policy_train_wgrad_kernel<false>), dim3(slices), dim3(kThreadsB), 0,
+                     s, r.h1, r.dz1, r.h2, r.dz2, r.dh, r.xs, n_pad, slice_rows, part);
 }
 
 }  // namespace pt
@@ -462,7 +244,7 @@ extern "C" int32_t mm_policy_train(const float *obs, int64_t obs_stride, int64_t
     p.out0 = net ? value : logp_taken; p.out1 = net ? nullptr : ratio;
     launch_sample(s, net != 0, p);
     launch_wgrad(s, net != 0, p.rows, L.n_pad, L.slice_rows, L.slices, sc + L.part);
-    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(n_s, k2, n_out) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
+    hipLaunchKernelGGL(policy_train_fold_kernel, dim3((fold_elems(kHidden, n_s, k2, n_out) + 255) / 256 + 1), dim3(256), 0, s, sc + L.part,
                        L.slices, (int)n_s, k2, n_out, net ? *critic_grads : *actor_grads, (const double *)p.lossp, L.ntiles,
                        (const int *)count, net ? 0 : (adv_sums ? 2 : 1), loss + net);
   }

@@ -154,10 +154,10 @@ def test_kernel_resources(tmp_path):
                            os.path.join(csrc, "mm_policy_bank_train.o"), os.path.join(csrc, "mm_opt_step_bank.o")],
                           stdout=subprocess.DEVNULL)
     now = {r["kernel"]: r for r in json.load(open(path))}
+    sample = "mm::mfma::mlp_sample_kernel<%s, mm::bank_train::Group, mm::bank_train::SampleArgs, mm::bank_train::Tables>"  # kernel A
     assert set(now) == {"mm::bank_train::bank_frag_kernel", "mm::bank_train::bank_stats_kernel", "mm::bank_train::bank_stats_fold_kernel",
-                        "mm::bank_train::bank_fold_kernel", "mm::bank_train::bank_sample_kernel<false, false>",
-                        "mm::bank_train::bank_sample_kernel<true, false>", "mm::bank_train::bank_sample_kernel<false, true>",
-                        "mm::bank_train::bank_sample_kernel<true, true>", "mm::bank_train::bank_wgrad_kernel<false>",
+                        "mm::bank_train::bank_fold_kernel", sample % "false, false", sample % "true, false", sample % "false, true",
+                        sample % "true, true", "mm::bank_train::bank_wgrad_kernel<false>",
                         "mm::bank_train::bank_wgrad_kernel<true>", "mm::opt::opt_step_bank_kernel"}
     for r in now.values():
         assert r["vgpr_spill"] == 0 and r["scratch_B"] == 0 and r["lds_B"] <= 160 * 1024, r

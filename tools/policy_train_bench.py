@@ -60,15 +60,15 @@ def kernel_model(n, slices=512):
     a_eval = 64 + 256
     slices = min(slices, max(1, (tiles + 1) // 2))
     out = {}
-    for crit, tag in ((0, "<false, true>"), (1, "<true, true>")):
-        out["policy_train_sample_kernel" + tag] = {"flop": tiles * a_train * MFMA_FLOP, "hbm_bytes": n * (30 * 4 + ROW_BYTES),
-                                                   "cache_bytes": tiles * 64 * 1024}
+    for crit, tag in ((0, "<false, true, mm::pt::Flat"), (1, "<true, true, mm::pt::Flat")):
+        out["mlp_sample_kernel" + tag] = {"flop": tiles * a_train * MFMA_FLOP, "hbm_bytes": n * (30 * 4 + ROW_BYTES),
+                                          "cache_bytes": tiles * 64 * 1024}
     for crit, tag in ((0, "<false>"), (1, "<true>")):
         b_mfma = (16 + 4 * crit) + 4 + 4  # per 2 samples: dW2 (+ the one-hot tile), the head tile, dz1^T x
         out["policy_train_wgrad_kernel" + tag] = {"flop": (tiles * 16) * b_mfma * MFMA_FLOP,
                                                   "hbm_bytes": n * ROW_BYTES + slices * PARTIAL * 4, "cache_bytes": n * 3 * 128 * 4}
-    for tag in ("<false, false>", "<true, false>"):
-        out["policy_train_sample_kernel" + tag] = {"flop": tiles * a_eval * MFMA_FLOP, "hbm_bytes": n * (30 * 4 + 8), "cache_bytes": 0}
+    for tag in ("<false, false, mm::pt::Flat", "<true, false, mm::pt::Flat"):
+        out["mlp_sample_kernel" + tag] = {"flop": tiles * a_eval * MFMA_FLOP, "hbm_bytes": n * (30 * 4 + 8), "cache_bytes": 0}
     out["policy_train_fold_kernel"] = {"flop": 0, "hbm_bytes": slices * PARTIAL * 4, "cache_bytes": 0}
     out["policy_train_prep_kernel"] = {"flop": 0, "hbm_bytes": 4 * 64 * 1024, "cache_bytes": 0}
     return out
@@ -79,7 +79,7 @@ def trim_stats(src, dst, width=100):
     several KB each) and without the rows below 0.1 % of the time, which is the form that is committed under profiles/."""
     with open(src) as f, open(dst, "w", newline="") as g:
         rows = list(csv.reader(f))
-        keep = [r for r in rows[1:] if r and (float(r[4]) >= 0.1 or "policy_train" in r[0])]  # >= 0.1 % of the time, or ours
+        keep = [r for r in rows[1:] if r and (float(r[4]) >= 0.1 or "policy_train" in r[0] or "mm::pt::" in r[0])]  # >= 0.1 % of the time, or ours
         csv.writer(g, quoting=csv.QUOTE_MINIMAL).writerows([[r[0][:width]] + r[1:] for r in rows[:1] + keep])
 
 
