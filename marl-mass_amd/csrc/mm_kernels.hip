@@ -1764,6 +1764,22 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // to 36 B of scratch with this, the act selects and the wide copy-out, so the trace kernels keep all three of the earlier forms.
   constexpr bool kHBits = kSine && !TRACE && kPoseHBits;
   constexpr bool kWideObs = kSine && !TRACE && kObsWide;  // observe<WIDE>'s 16-byte copy-out of the float32 rows
+  // kPBits: what a lane sees of partner m in the classification pass -- its committed image, its pre-step image, nothing --
+  // comes from the rank scan at the top of the sub-step instead of from the partner's rank word: the scan's own term
+  // ("m steps before me") and the exchanged `live` ride in one int (`pbits`, bit m / bit 8 + m) and rank is the population count of
+  // the first.  Every lane keeps (x, y, pose code) of the candidate it currently commits in a fixed "post" image four slots
+  // behind the pre-step image, so a partner's address is pre + bit * 4 slots with no read in front of it; there is no rank word.
+  // In the kPrimary kernels, whose main-pass candidate is the one a lane commits in pass 0, without the per-env parameter planes
+  // (those keep the rank words).  (-DMM_PARTNER_BITS=0: rank words everywhere)
+#ifndef MM_PARTNER_BITS
+#define MM_PARTNER_BITS 1
+#endif
+  constexpr bool kPBits = kPrimary && kHBits && kEarly && !PENV && MM_PARTNER_BITS != 0;
+  // ... and the collision pre-check takes the partner's `live` from the same int (-DMM_PARTNER_LIVE=0: exchanged again)
+#ifndef MM_PARTNER_LIVE
+#define MM_PARTNER_LIVE 1
+#endif
+  constexpr bool kPLive = kPBits && MM_PARTNER_LIVE != 0;
   double car_sn = __builtin_nan("");
   (void)car_sn;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
@@ -1852,13 +1868,16 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   // (C_GU0 / C_GU1: parallel form only -- the g*u product of my pre- / post-step record for the askers' gather)
   // (C_PRE, C_MSGW: parallel form only -- my pre-step pose (x, y, h, pose code) and my rank word, the mailbox the
   // partners' classification reads instead of a DPP exchange per field)
-  enum { C_B = 0, C_H1X = 8, C_H1VX, C_H2X, C_H2VX, C_SSTEER, C_SACC, C_TSPEED, C_A = 15, C_GU0 = 23, C_GU1 = 24, C_PRE = 25, C_MSGW = 29 };
+  // (kPBits: pre-step image (x, y, pose code) in slots 24 .. 26, the post image in 28 .. 30, C_GU1 in the gap: no heading slot --
+  // the predicates are in the code word -- and no rank word, 38 slots at G = 8 instead of 37)
+  enum { C_B = 0, C_H1X = 8, C_H1VX, C_H2X, C_H2VX, C_SSTEER, C_SACC, C_TSPEED, C_A = 15, C_GU0 = 23, C_GU1 = kPBits ? 27 : 24,
+         C_PRE = kPBits ? 24 : 25, C_PREPK = C_PRE + (kPBits ? 2 : 3), C_POST = C_PRE + 4, C_MSGW = 29 };
   // (16-lane groups keep the DPP exchange: 5 more slots would cost them a wave per CU -- measured 0.456 -> 0.504 ms at N = 12)
   constexpr bool kMailbox = G <= 8 || !kPow2<G>;  // (the DPP form below exchanges reader-specific messages: power-of-two groups only)
   // (rotation layouts: the rank word rides in the unused high half of the pose-code slot -- 40 slots = 20 KB at G = 12, the
   // eighth wave of a CU)
   constexpr bool kPackMsg = !kPow2<G>;
-  constexpr int kColdB = kMailbox ? (kPackMsg ? 29 : 30) : 25;
+  constexpr int kColdB = kPBits ? 31 : (kMailbox ? (kPackMsg ? 29 : 30) : 25);
   // candidates occupy 8 slots each (x, y, h, pose code [int], cos h, steering, g.vx, sin h); unshielded kernels use only slots
   // 8..14 (+ the obs staging: 15 slots); the sort keys are a parallel-form temporary
   constexpr bool kRoomy = false;  // (round 1 parked cos(heading) / g.vx in LDS as well: no longer measurable, 0.332 ms either way)
@@ -1875,7 +1894,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
   s_cold[C_TSPEED][tid] = v.tspeed;
   if constexpr (kEarly) {
     static_assert(kMailbox && !kPackMsg, "the high words of the pose-code and rank-word slots must be free");
-    ((int *)&s_cold[C_PRE + 3][tid])[1] = n_merge; ((int *)&s_cold[C_MSGW][tid])[1] = episode;
+    ((int *)&s_cold[C_PREPK][tid])[1] = n_merge; ((int *)&s_cold[kPBits ? C_POST + 2 : C_MSGW][tid])[1] = episode;
   }
   // (form / slot selection is `if constexpr` throughout: an instantiation contains no code for slots it does not own)
   if constexpr (kRoomy) { s_cold[C_CPSI][tid] = cpsi; s_cold[C_GVX][tid] = v.gvx; }
@@ -1895,14 +1914,22 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
                   __builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
     // Road.act / Road.step order: sorted by x descending, stable (road.py:277,286) -> rank
     int rank = 0;
+    int pbits = 0;  // kPBits: bit m -- I see partner m's committed image, bit 8 + m -- partner m is live
+    (void)pbits;
     if ((SHIELDED || MIXED) && head) {
       for_partners<G>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         double px = px_d<m, G>(v.x, a);
         bool pp = px_i<m, G>((int)live, a) != 0;
-        if constexpr (kScan) rank += (pp & ((px > v.x) | ((px == v.x) & (pidx<m, G>(a) < a)))) ? 1 : 0;
+        if constexpr (kPBits) pbits |= ((pp & ((px > v.x) | ((px == v.x) & (pidx<m, G>(a) < a)))) ? 1 << m : 0) | (pp ? 256 << m : 0);
+        else if constexpr (kScan) rank += (pp & ((px > v.x) | ((px == v.x) & (pidx<m, G>(a) < a)))) ? 1 : 0;
         else rank += (pp && (px > v.x || (px == v.x && pidx<m, G>(a) < a))) ? 1 : 0;
       });
+    }
+    if constexpr (kPBits) {
+      rank = __popc(pbits & 255);  // (the bits are the scan's terms)
+      // (a lane that is not live sees the committed image of every live partner: the rank words' `!i_first && p_rank < 99`)
+      pbits = live ? pbits : ((pbits >> 8) * 257);
     }
     if (head) v.tspeed = s_cold[C_TSPEED][tid];
     if constexpr (kActSel) {
@@ -2068,6 +2095,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     };
     if constexpr (kPrimary) park_at(first_B ? (int)C_B : (int)C_A, cA, v.act_steer);
     else if (head) park(std::integral_constant<int, C_A>{}, cA, v.act_steer);
+    // (kPBits: the main pass's candidate is the one this lane commits in pass 0 -- use_B = first_B below: its post image)
+    if constexpr (kPBits) { s_cold[C_POST + 0][tid] = cA.x; s_cold[C_POST + 1][tid] = cA.y; cold_i(C_POST + 2, tid) = cA.pk; }
     STAMP(2);  // predict A
     // LC veto re-steers to the CURRENT lane (decentral_layer.py:501-506,739-744); identical to the
     // nominal command unless a lane change / lane hand-over is under way or the car crashed.
@@ -2225,7 +2254,8 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         // can a vehicle have more than 5 others around it at all?  (compile-time only: making the 8-lane kernels
         // test st.N > 6 as well cost them 3 % through 20 B/lane more scratch)
         constexpr bool count5 = G > 4;
-        if constexpr (kMailbox) { s_cold[C_PRE + 0][tid] = v.x; s_cold[C_PRE + 1][tid] = v.y; s_cold[C_PRE + 2][tid] = v.h; cold_i(C_PRE + 3, tid) = pk_self; }
+        if constexpr (kPBits) { s_cold[C_PRE + 0][tid] = v.x; s_cold[C_PRE + 1][tid] = v.y; cold_i(C_PREPK, tid) = pk_self; }
+        else if constexpr (kMailbox) { s_cold[C_PRE + 0][tid] = v.x; s_cold[C_PRE + 1][tid] = v.y; s_cold[C_PRE + 2][tid] = v.h; cold_i(C_PRE + 3, tid) = pk_self; }
         // (interior-point mode) the QP this lane solved in the previous veto pass of this sub-step: rows that did not change
         // need no second solve.  a, h1, h2 depend on the lane's own pre-step state only, so (rows, h0, h3) identify the QP.
         double qc_h0 = 0.0, qc_h3 = 0.0, qc_d = 0.0;
@@ -2247,9 +2277,11 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           // both candidate images in LDS, a partner picks what it sees of me by address -- my committed post-state if I step
           // before it, else my pre-step pose -- instead of receiving 3 doubles + 2 ints through DPP and select chains
           if constexpr (kMailbox) {
-            const int my_word = (live ? rank : 99) | (use_B ? 256 : 0);
-            if constexpr (kPackMsg) ((int *)&s_cold[C_PRE + 3][tid])[1] = my_word;
-            else cold_i(C_MSGW, tid) = my_word;
+            if constexpr (!kPBits) {
+              const int my_word = (live ? rank : 99) | (use_B ? 256 : 0);
+              if constexpr (kPackMsg) ((int *)&s_cold[C_PRE + 3][tid])[1] = my_word;
+              else cold_i(C_MSGW, tid) = my_word;
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2264,6 +2296,16 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
             int p_rank, opk;
             double ox, oy, oh;
             bool i_first;
+            (void)p_rank; (void)i_first;
+            bool o_first, other;  // partner steps before me (ranks are distinct); partner is there at all
+            if constexpr (kPBits) {
+              // its pose as I see it: the committed image if it steps before me, else the pre-step one -- by address, from the scan's bit
+              const int pl = plane<m, G>(tid, a);
+              const int pb = C_PRE + ((pbits >> m) & 1) * 4;
+              ox = s_cold[pb + 0][pl]; oy = s_cold[pb + 1][pl]; oh = 0.0;  // (its predicates are in the code word)
+              opk = cold_i(pb + 2, pl);
+              o_first = ((pbits >> m) & 1) != 0; other = ((pbits >> (8 + m)) & 1) != 0;
+            } else {
             if constexpr (kMailbox) {
               const int pl = plane<m, G>(tid, a);
               int pw;
@@ -2286,8 +2328,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
               ox = dppx_d<m>(sx_); oy = dppx_d<m>(sy_); oh = dppx_d<m>(sh_);
               opk = dppx_i<m>(spk | (int)live << 8);
             }
-            const bool o_first = !i_first && p_rank < 99;  // partner steps before me (ranks are distinct)
-            const Rel r = relate<kHBits && kMailbox>(v.x, v.y, pk_self, ((opk >> 8) & 1) != 0, ox, oy, oh, opk);
+            o_first = !i_first && p_rank < 99;
+            other = ((opk >> 8) & 1) != 0;
+            }
+            const Rel r = relate<kHBits && kMailbox>(v.x, v.y, pk_self, other, ox, oy, oh, opk);
             if constexpr (count5) s_cold[kColdB + m - 1][tid] = r.key;
             // running "first in sorted order" per class: smaller key, ties by creation index (selects, no branches)
             // (the slot's flags ride in the index word -- bit 4: that partner steps before me, bit 5: its corner
@@ -2516,6 +2560,13 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           const bool flip = want_B != use_B;
           use_B = want_B;
           if (!__any(flip)) break;
+          if constexpr (kPBits) {  // a lane that now commits its other candidate re-publishes its post image for the next pass
+            if (flip) {
+              const int cb = use_B ? (int)C_B : (int)C_A;
+              s_cold[C_POST + 0][tid] = s_cold[cb + 0][tid]; s_cold[C_POST + 1][tid] = s_cold[cb + 1][tid];
+              cold_i(C_POST + 2, tid) = cold_i(cb + 3, tid);
+            }
+          }
         }
         serial = __any(irregular);
         if (!serial && shield_on) {
@@ -2725,7 +2776,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     for_partners<G>([&](auto mc) {
       constexpr int m = decltype(mc)::value;
       double px = px_d<m, G>(v.x, a), py = px_d<m, G>(v.y, a), ph = px_d<m, G>(v.h, a);
-      bool pp = px_i<m, G>((int)live, a) != 0;
+      bool pp;
+      if constexpr (kPLive) pp = ((pbits >> (8 + m)) & 1) != 0;  // (`live` as the rank scan exchanged it: env_active changes after this)
+      else pp = px_i<m, G>((int)live, a) != 0;
       double dx = px - v.x, dy = py - v.y;
       const bool near = live & pp & !((dx * dx + dy * dy) > kU5);  // norm > LENGTH pre-check, sqrt-free
       CAND_COUNT(MM_CS_NEAR, near);
@@ -2935,7 +2988,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     th = h2d / (vx > 1 ? vx : 1);
   }
   const double min_headway = group_min_d<G>(th, a);
-  if constexpr (kEarly) { n_merge = ((const int *)&s_cold[C_PRE + 3][tid])[1]; episode = ((const int *)&s_cold[C_MSGW][tid])[1]; }
+  if constexpr (kEarly) { n_merge = ((const int *)&s_cold[C_PREPK][tid])[1]; episode = ((const int *)&s_cold[kPBits ? C_POST + 2 : C_MSGW][tid])[1]; }
   else if (e < st.E) { n_merge = st.I[MM_E_N_MERGE * st.E + e]; episode = st.I[MM_E_EPISODE * st.E + e]; }
   double merge_pct = __builtin_nan("");
   if (done) {
