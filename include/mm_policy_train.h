@@ -138,6 +138,8 @@ int32_t mm_policy_train_chunked(const float *obs, int64_t obs_stride, int64_t n,
  *       block (PartialBlock<4>, mm_policy_mfma.h): dW2 [128][160] at 0 (row pitch 160, k2 columns used); dW3 rows [16][128] at
  *       20 480; dW1 [128][32] at 22 528; db2 [128] at 26 624; db3 [16] at 26 752; db1 [128] at 26 768.  Zeros for a network
  *       that was not given.
+ * Every double of the block is a function of the inputs: a slot that finish does not read (a dW2 column from k2 on, a dW3 row
+ * or db3 element from the network's outputs on, a dW1 column from n_s on) is 0.0, whatever the scratch held.
  *
  * mm_policy_train_partial: mm_policy_train_chunked's arguments without actor_grads, critic_grads and loss, and with count (DEV
  * int32[1], 4-byte aligned: B of the whole batch over all ranks) and shard (DEV double[MM_PT_SHARD_DOUBLES], 16-byte aligned,

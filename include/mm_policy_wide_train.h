@@ -23,7 +23,7 @@
  * mm_policy_wide_train_chunked (below) is the same gradient in passes under a fixed scratch budget, and
  * mm_policy_wide_train_partial / mm_policy_wide_train_finish (at the end) over a batch that is sharded over ranks.
  *
- * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip, mm_policy_wide_chunked.hip, mm_policy_wide_sharded.hip): no oracle twin, not part of
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_wide_train.hip, mm_policy_chunked.hip, mm_policy_sharded.hip): no oracle twin, not part of
  * include/mm_abi.h's symbol list or version.  torch.autograd on the two rollout modules is the CPU form.
  */
 #ifndef MM_POLICY_WIDE_TRAIN_H
@@ -105,7 +105,7 @@ int32_t mm_policy_wide_train(const float *obs, int64_t obs_stride, int64_t n, in
                              float *value, float *ratio, void *scratch, uint64_t scratch_bytes, MMStream stream);
 
 /*
- * The same call under a fixed scratch budget (marl-mass_amd/csrc/mm_policy_wide_chunked.hip): mm_policy_train_chunked's
+ * The same call under a fixed scratch budget (marl-mass_amd/csrc/mm_policy_chunked.hip): mm_policy_train_chunked's
  * contract (include/mm_policy_train.h) at hidden == 512.  Kernels A and B run over the batch in passes of `chunk` samples, the
  * actor's pass and the critic's alternating over the same rows; each pass's partial blocks are added, in slice order and in
  * fp64, to the network's own accumulator block, and gradients and losses are written once at the end: the gradient of ONE
@@ -154,7 +154,7 @@ int32_t mm_policy_wide_train_chunked(const float *obs, int64_t obs_stride, int64
                                      uint64_t scratch_bytes, MMStream stream, int64_t chunk);
 
 /*
- * The same gradients over a batch that is SHARDED over ranks, in two phases (marl-mass_amd/csrc/mm_policy_wide_sharded.hip):
+ * The same gradients over a batch that is SHARDED over ranks, in two phases (marl-mass_amd/csrc/mm_policy_sharded.hip):
  * mm_policy_train_partial / mm_policy_train_finish's protocol (include/mm_policy_train.h; the header's check and the order of
  * every sum: include/mm_policy_gi_train.h) at hidden == 512, as those are to mm_policy_train_chunked.  Every rank runs `partial`
  * on its own samples, the R blocks are gathered in rank order, and every rank runs `finish` on the same R blocks: the same bits

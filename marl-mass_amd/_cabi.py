@@ -412,7 +412,7 @@ class CLib(object):
             lib.mm_policy_wide_train_chunked_scratch_bytes.restype = i32
             lib.mm_policy_wide_train_chunked.argtypes = list(lib.mm_policy_wide_train.argtypes) + [i64]
             lib.mm_policy_wide_train_chunked.restype = i32
-        # and over a batch sharded over ranks (mm_policy_wide_sharded.hip): the argument lists of mm_policy_train_partial /
+        # and over a batch sharded over ranks (mm_policy_sharded.hip): the argument lists of mm_policy_train_partial /
         # mm_policy_train_finish, hidden 512
         self.has_policy_wide_train_sharded = self.has_policy_wide_train_chunked and sharded("wide_train")
         if self.has_policy_wide_train_sharded:

@@ -604,6 +604,11 @@ def _mlp_struct(net, grads=False):
     return st
 
 
+# hidden size -> the name stem of the library's entries, size queries and require functions for it (mm_<stem>, mm_<stem>_chunked,
+# <stem>_chunked_scratch_bytes, require_<stem>_sharded, ...); hidden 128 is "policy_train"
+_PT_STEM = {128: "policy_train", 512: "policy_wide_train"}
+
+
 class PPOLearner(_DeviceLearner):
     """`MAPPO`'s actor / critic / actor_target / critic_target / two optimisers and its train() (marl/mappo.py:70-95, :161-206);
     defaults are MAPPO.__init__'s.  `actor` is a rollout.ActorNetwork and `critic` a rollout.CriticNetwork, both of hidden size 128
@@ -622,14 +627,9 @@ class PPOLearner(_DeviceLearner):
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, fused_step=False,
                  soft_update_every="train", scratch_budget_bytes=None, shard_group=None):
         # (first: a budget no call can meet is refused whatever else is passed; the smallest pass is that of the hidden size)
-        if _hidden_of(actor) == 512:
-            self._init_budget(scratch_budget_bytes, clib.require_policy_wide_train_chunked, clib.policy_wide_train_chunked_scratch_bytes)
-        else:
-            self._init_budget(scratch_budget_bytes, clib.require_policy_train_chunked, clib.policy_train_chunked_scratch_bytes)
-        if _hidden_of(actor) == 512:
-            self._init_shards(shard_group, clib.require_policy_wide_train_sharded, clib.policy_wide_train_shard_doubles)
-        else:
-            self._init_shards(shard_group, clib.require_policy_train_sharded, clib.policy_train_shard_doubles)
+        stem = _PT_STEM.get(_hidden_of(actor), "policy_train")  # (a size that is neither is refused below)
+        self._init_budget(scratch_budget_bytes, getattr(clib, "require_%s_chunked" % stem), getattr(clib, "%s_chunked_scratch_bytes" % stem))
+        self._init_shards(shard_group, getattr(clib, "require_%s_sharded" % stem), getattr(clib, "%s_shard_doubles" % stem))
         if soft_update_every not in ("train", "agent_step"):
             raise ValueError("soft_update_every must be 'train' or 'agent_step', got %r" % (soft_update_every,))
         if type(actor) is not ActorNetwork or type(critic) is not CriticNetwork:
@@ -653,18 +653,12 @@ class PPOLearner(_DeviceLearner):
         # the library's entries for this hidden size: (gradient, evaluation, scratch query, the gradient in passes, and the two
         # phases over rank-sharded batches where the library has them: without a shard group nothing requires them)
         chunked = scratch_budget_bytes is not None  # (_init_budget required the entry)
-        if hid == 512:
-            clib.require_policy_wide_train()
-            self._entries = (clib.lib.mm_policy_wide_train, clib.lib.mm_policy_wide_eval, clib.policy_wide_train_scratch_bytes,
-                             clib.lib.mm_policy_wide_train_chunked if chunked else None,
-                             clib.lib.mm_policy_wide_train_partial if clib.has_policy_wide_train_sharded else None,
-                             clib.lib.mm_policy_wide_train_finish if clib.has_policy_wide_train_sharded else None)
-        else:
-            clib.require_policy_train()
-            self._entries = (clib.lib.mm_policy_train, clib.lib.mm_policy_eval, clib.policy_train_scratch_bytes,
-                             clib.lib.mm_policy_train_chunked if chunked else None,
-                             clib.lib.mm_policy_train_partial if clib.has_policy_train_sharded else None,
-                             clib.lib.mm_policy_train_finish if clib.has_policy_train_sharded else None)
+        getattr(clib, "require_" + stem)()
+        sharded = getattr(clib, "has_%s_sharded" % stem)
+        entry = lambda suffix: getattr(clib.lib, "mm_" + stem + suffix)  # noqa: E731
+        self._entries = (entry(""), getattr(clib.lib, "mm_" + stem.replace("train", "eval")), getattr(clib, stem + "_scratch_bytes"),
+                         entry("_chunked") if chunked else None, entry("_partial") if sharded else None,
+                         entry("_finish") if sharded else None)
         _DeviceLearner.__init__(self, clib, actor.fc1.weight.device, self._entries[2])
         self.actor, self.critic = actor, critic
         self.actor_target, self.critic_target = copy.deepcopy(actor), copy.deepcopy(critic)

@@ -81,20 +81,26 @@ def test_scratch_query(which):
 
 
 def test_kernel_resources(tmp_path):
-    """mm_policy_chunked.o holds the accumulate kernel and one finish kernel per entry, none spills or uses scratch memory,
-    and profiles/train_chunked/kernel_resources.json records what the build gives.  (That the two training objects still hold
-    exactly their recorded kernels is tests/test_policy_train_host.py::test_kernel_resources.)"""
+    """mm_policy_chunked.o holds the one accumulate kernel and one finish kernel per entry (the separate networks' as one
+    template, instantiated for hidden 128 and 512), none spills or uses scratch memory, and
+    profiles/train_chunked/kernel_resources.json records what the build gives.  (That the training objects still hold exactly
+    their recorded kernels is test_kernel_resources of tests/test_policy_train_host.py and tests/test_policy_wide_train_host.py.)"""
     csrc = os.path.join(REPO, "marl-mass_amd", "csrc")
     subprocess.check_call(["make", "-C", csrc, "mm_policy_chunked.o"], stdout=subprocess.DEVNULL)
     path = str(tmp_path / "resources.json")
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"), "--match", "_kernel", "--json", path,
                            os.path.join(csrc, "mm_policy_chunked.o")], stdout=subprocess.DEVNULL)
     now = {r["kernel"]: r for r in json.load(open(path))}
-    assert sorted(now) == ["mm::chunked::policy_gi_train_chunked_finish_kernel", "mm::chunked::policy_train_chunked_finish_kernel",
+    assert sorted(now) == ["mm::chunked::policy_gi_train_chunked_finish_kernel",
+                           "mm::chunked::policy_train_chunked_finish_kernel<mm::chunked::Pt128>",
+                           "mm::chunked::policy_train_chunked_finish_kernel<mm::chunked::Pt512>",
                            "mm::chunked::train_chunked_accumulate_kernel"]
     for r in now.values():
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch_B"] == 0 and r["vgpr"] <= 64, r
         assert r["lds_B"] <= 2 * 256 * 8  # the loss tree of the finish kernels
+    for name in now:
+        if "policy_train_chunked_finish_kernel" in name:
+            assert now[name]["lds_B"] <= 256 * 8  # one network's loss tree
     rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "train_chunked", "kernel_resources.json")))}
     assert set(rec) == set(now)
     for name in now:

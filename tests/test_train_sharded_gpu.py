@@ -377,6 +377,49 @@ def test_refusals_leave_everything_alone(kind):
     ch._bit_equal(runs[2], runs[1], "two calls")
 
 
+# ---- 6b. every double of the separate networks' block is a function of the inputs (tests/test_wide_sharded_gpu.py's, at 128)
+# the offsets of a PartialBlock<4> accumulator block: dW2 [128][160], head rows [16][128], dW1 [128][32], db2, head bias [16], db1
+O_W2, O_HD, O_W1, O_B2, O_BH, O_B1 = 0, 20480, 22528, 26624, 26752, 26768
+
+
+def _unread(n_s, n_a):
+    """bool [K["pt"]]: the accumulator slots the finish index map does not read (the header and the loss sums are read)."""
+    assert O_B1 + 128 == PART_PT
+    mask = np.zeros(K["pt"], dtype=bool)
+    for i, (k2, n_out) in enumerate(((128, n_a), (128 + n_a, 1))):
+        m = np.zeros(PART_PT, dtype=bool)
+        m[O_W2:O_HD].reshape(128, 160)[:, k2:] = True
+        m[O_HD:O_W1].reshape(16, 128)[n_out:] = True
+        m[O_W1:O_B2].reshape(128, 32)[:, n_s:] = True
+        m[O_BH + n_out:O_B1] = True
+        mask[ACC + i * PART_PT:ACC + (i + 1) * PART_PT] = m
+    return mask
+
+
+@pytest.mark.parametrize("networks", ["both", "actor"])
+def test_the_block_is_a_function_of_the_inputs(networks):
+    case = ch._base("pt", 1000)
+    chunk = 64
+    scratch = torch.empty(case.chunked_bytes(chunk), dtype=torch.uint8, device="cuda")
+    unread = torch.from_numpy(_unread(case.obs.shape[1], case.n_a)).cuda()
+    assert bool(unread.any())
+    for form in ("reference", "flat"):
+        runs = []
+        for fill in (0xFF, 0x00, None):
+            if fill is not None:
+                scratch.fill_(fill)
+            rc, block, _ = partial_rc(case, form, chunk, _count(case), sums=case.sums(form), scratch=scratch, networks=networks)
+            assert rc == abi.MM_OK
+            runs.append(block)
+        assert bool(torch.isfinite(runs[0]).all())
+        bits = [r.view(torch.int64) for r in runs]
+        assert torch.equal(bits[0], bits[1]) and torch.equal(bits[1], bits[2]), (form, networks)
+        assert bool((bits[0][unread] == 0).all()), (form, networks)  # exactly 0.0
+        if networks == "actor":
+            assert bool((bits[0][ACC + PART_PT:] == 0).all()) and float(runs[0][5]) == 0.0
+        assert float(runs[0][ACC:ACC + PART_PT].abs().max()) > 0.0
+
+
 # ---- 7. the learner's two phases composed by hand, on one device
 B_ALL, N_AGENTS, S_COLS, N_ACT, HALF = 600, 4, 30, 5, 300
 

@@ -1,5 +1,5 @@
 """The rank-sharded gradient entries without a GPU: the exported symbols and the binding, the shard block's size against the
-public headers, the resources of the two new kernels, the rank-ordered gather over two gloo ranks, and the learners' refusals."""
+public headers, the resources of the kernels of mm_policy_sharded.o, the rank-ordered gather over two gloo ranks, and the learners' refusals."""
 import ctypes
 import datetime
 import json
@@ -69,18 +69,27 @@ def test_block_sizes_are_the_headers():
 
 
 def test_kernel_resources(tmp_path):
-    """mm_policy_sharded.o holds the two new kernels, neither spills or uses scratch memory, both are built for 256-thread
-    workgroups, and profiles/train_sharded/kernel_resources.json records what the build gives."""
+    """mm_policy_sharded.o holds the shared network's header kernel, the separate networks' tail kernel at both hidden sizes and
+    the finish kernel of the three families, none spills or uses scratch memory, all fit 64 VGPRs and are built for 256-thread
+    workgroups, the only LDS is the loss trees of the header and tail kernels, and
+    profiles/train_sharded/kernel_resources.json records what the build gives."""
     csrc = os.path.join(REPO, "marl-mass_amd", "csrc")
     subprocess.check_call(["make", "-C", csrc, "mm_policy_sharded.o"], stdout=subprocess.DEVNULL)
     path = str(tmp_path / "resources.json")
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"), "--match", "_kernel", "--json", path,
                            os.path.join(csrc, "mm_policy_sharded.o")], stdout=subprocess.DEVNULL)
     now = {r["kernel"]: r for r in json.load(open(path))}
-    assert sorted(now) == ["mm::sharded::train_shard_finish_kernel", "mm::sharded::train_shard_header_kernel"]
+    finish = ["mm::sharded::train_shard_finish_kernel<mm::%s>" % f for f in ("chunked::Pt128", "chunked::Pt512", "sharded::Gi")]
+    assert sorted(now) == finish + ["mm::sharded::train_shard_header_kernel", "mm::sharded::train_shard_tail_kernel<mm::chunked::Pt128>",
+                                    "mm::sharded::train_shard_tail_kernel<mm::chunked::Pt512>"]
     for r in now.values():
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch_B"] == 0 and r["vgpr"] <= 64, r
         assert r["lds_B"] <= 2 * 256 * 8  # the loss tree of the header kernel
+    for name in now:
+        if "tail_kernel" in name:
+            assert now[name]["lds_B"] <= 256 * 8  # one network per workgroup
+    for name in finish:
+        assert now[name]["lds_B"] == 0
     rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "train_sharded", "kernel_resources.json")))}
     assert set(rec) == set(now)
     for name in now:
@@ -88,7 +97,7 @@ def test_kernel_resources(tmp_path):
         for k in ("vgpr", "agpr", "sgpr", "vgpr_spill", "sgpr_spill", "scratch_B", "lds_B"):
             assert now[name][k] == rec[name][k], (name, k)
     source = open(os.path.join(csrc, "mm_policy_sharded.hip")).read()
-    assert source.count("__global__ __launch_bounds__(256)") == 2 and "atomicAdd" not in source
+    assert source.count("__global__ __launch_bounds__(256)") == 3 and "atomicAdd" not in source  # header, tail<F>, finish<F>
 
 
 def _gather_worker(rank, world, port, out_dir):

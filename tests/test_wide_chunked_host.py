@@ -1,5 +1,5 @@
 """mm_policy_wide_train_chunked (include/mm_policy_wide_train.h) without a GPU: the exported symbols and the binding, the size
-query against a restatement of the header's sum, the header as C, the resources of the two new kernels, the learner's budget
+query against a restatement of the header's sum, the header as C, the resources of the entry's two kernels, the learner's budget
 floor at hidden 512, and the input conditions of the 6 208-sample batches of the GPU module (host generators: they are
 properties of the seeds)."""
 import ctypes
@@ -115,25 +115,26 @@ def test_header_compiles_as_c_and_states_the_sum(tmp_path):
 
 
 def test_kernel_resources(tmp_path):
-    """mm_policy_wide_chunked.o holds the accumulate kernel and the finish kernel, neither spills or uses scratch memory, and
-    profiles/wide_chunked/kernel_resources.json records what the build gives.  (That mm_policy_wide_train.o still holds exactly
-    its recorded kernels is tests/test_policy_wide_train_host.py::test_kernel_resources.)"""
-    subprocess.check_call(["make", "-C", CSRC, "mm_policy_wide_chunked.o"], stdout=subprocess.DEVNULL)
+    """The hidden-512 entry's kernels in mm_policy_chunked.o -- the accumulate kernel it shares with the hidden-128 entries and
+    the Pt512 instantiation of the separate networks' finish kernel -- neither spills or uses scratch memory, and
+    profiles/train_chunked/kernel_resources.json records what the build gives.  (The object's whole kernel list:
+    tests/test_train_chunked_host.py::test_kernel_resources; that mm_policy_wide_train.o still holds exactly its recorded
+    kernels: tests/test_policy_wide_train_host.py::test_kernel_resources.)"""
+    subprocess.check_call(["make", "-C", CSRC, "mm_policy_chunked.o"], stdout=subprocess.DEVNULL)
     path = str(tmp_path / "resources.json")
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"), "--match", "_kernel", "--json", path,
-                           os.path.join(CSRC, "mm_policy_wide_chunked.o")], stdout=subprocess.DEVNULL)
+                           os.path.join(CSRC, "mm_policy_chunked.o")], stdout=subprocess.DEVNULL)
+    mine = ["mm::chunked::policy_train_chunked_finish_kernel<mm::chunked::Pt512>", "mm::chunked::train_chunked_accumulate_kernel"]
     now = {r["kernel"]: r for r in json.load(open(path))}
-    assert sorted(now) == ["mm::wide_chunked::policy_wide_chunked_accumulate_kernel",
-                           "mm::wide_chunked::policy_wide_chunked_finish_kernel"]
-    for r in now.values():
+    assert sorted(k for k in now if "Pt512" in k or "accumulate" in k) == mine
+    rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "train_chunked", "kernel_resources.json")))}
+    for name in mine:
+        r = now[name]
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch_B"] == 0 and r["vgpr"] <= 64, r
         assert r["lds_B"] <= 256 * 8  # the loss tree of the finish kernel
-    rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "wide_chunked", "kernel_resources.json")))}
-    assert set(rec) == set(now)
-    for name in now:
-        assert rec[name]["object"] == "mm_policy_wide_chunked.o"
+        assert rec[name]["object"] == "mm_policy_chunked.o"
         for k in ("vgpr", "agpr", "sgpr", "vgpr_spill", "sgpr_spill", "scratch_B", "lds_B"):
-            assert now[name][k] == rec[name][k], (name, k)
+            assert r[k] == rec[name][k], (name, k)
 
 
 def test_learner_budget_floor_at_512():

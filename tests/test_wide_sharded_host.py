@@ -1,6 +1,6 @@
 """mm_policy_wide_train_partial / mm_policy_wide_train_finish (include/mm_policy_wide_train.h) without a GPU: the exported
-symbols and the binding, the shard block's size against the public header as C, the resources of the two new kernels, and what a
-hidden-512 learner with a shard group refuses."""
+symbols and the binding, the shard block's size against the public header as C, the resources of the entries' two kernels, and
+what a hidden-512 learner with a shard group refuses."""
 import ctypes
 import json
 import os
@@ -72,27 +72,28 @@ def test_block_size_is_the_headers(tmp_path):
 
 
 def test_kernel_resources(tmp_path):
-    """mm_policy_wide_sharded.o holds the tail kernel of `partial` and the finish kernel, neither spills or uses scratch memory,
-    both fit 64 VGPRs, the only LDS is the tail's loss tree (one network per workgroup), and
-    profiles/wide_sharded/kernel_resources.json records what the build gives."""
-    subprocess.check_call(["make", "-C", CSRC, "mm_policy_wide_sharded.o"], stdout=subprocess.DEVNULL)
+    """The hidden-512 entries' kernels in mm_policy_sharded.o -- the Pt512 instantiations of the tail kernel of `partial` and of
+    the finish kernel -- neither spills or uses scratch memory, both fit 64 VGPRs, the only LDS is the tail's loss tree (one
+    network per workgroup), and profiles/train_sharded/kernel_resources.json records what the build gives.  (The object's whole
+    kernel list and its source: tests/test_train_sharded_host.py::test_kernel_resources.)"""
+    subprocess.check_call(["make", "-C", CSRC, "mm_policy_sharded.o"], stdout=subprocess.DEVNULL)
     path = str(tmp_path / "resources.json")
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"), "--match", "_kernel", "--json", path,
-                           os.path.join(CSRC, "mm_policy_wide_sharded.o")], stdout=subprocess.DEVNULL)
+                           os.path.join(CSRC, "mm_policy_sharded.o")], stdout=subprocess.DEVNULL)
+    finish, tail = ("mm::sharded::train_shard_%s_kernel<mm::chunked::Pt512>" % k for k in ("finish", "tail"))
     now = {r["kernel"]: r for r in json.load(open(path))}
-    assert sorted(now) == ["mm::wide_sharded::wide_shard_finish_kernel", "mm::wide_sharded::wide_shard_tail_kernel"]
-    for r in now.values():
+    assert sorted(k for k in now if "Pt512" in k) == [finish, tail]
+    rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "train_sharded", "kernel_resources.json")))}
+    for name in (finish, tail):
+        r = now[name]
         assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch_B"] == 0 and r["vgpr"] <= 64, r
         assert r["lds_B"] <= 2 * 256 * 8  # the loss trees, 256 x 8 B per network
-    assert now["mm::wide_sharded::wide_shard_finish_kernel"]["lds_B"] == 0
-    rec = {r["kernel"]: r for r in json.load(open(os.path.join(REPO, "profiles", "wide_sharded", "kernel_resources.json")))}
-    assert set(rec) == set(now)
-    for name in now:
-        assert rec[name]["object"] == "mm_policy_wide_sharded.o"
+        assert rec[name]["object"] == "mm_policy_sharded.o"
         for k in ("vgpr", "agpr", "sgpr", "vgpr_spill", "sgpr_spill", "scratch_B", "lds_B"):
-            assert now[name][k] == rec[name][k], (name, k)
-    source = open(os.path.join(CSRC, "mm_policy_wide_sharded.hip")).read()
-    assert source.count("__global__ __launch_bounds__(256)") == 2 and "atomicAdd" not in source
+            assert r[k] == rec[name][k], (name, k)
+    assert now[finish]["lds_B"] == 0
+    source = open(os.path.join(CSRC, "mm_policy_sharded.hip")).read()
+    assert "atomicAdd" not in source
 
 
 def test_learner_construction():
