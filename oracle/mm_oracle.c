@@ -133,6 +133,82 @@ static unsigned g_qplog_stepped;
 void orc_qplog_open(const char *path) { if (g_qplog) fclose(g_qplog); g_qplog = path ? fopen(path, "w") : NULL; }
 #endif
 
+/*
+ * Census of the step (oracle-only, like the supervisors' g_sup_census): which decision outcomes and which data states the
+ * step path went through since the last orc_step_census_reset.  tests/test_tape_census_host.py replays every reference tape
+ * and demands that each name is either counted or listed, with the reason, in tests/golden/cv_unreached.json: a branch no
+ * tape reaches is a branch on which this restatement is not pinned to the reference.  Off by default (one predictable
+ * branch per site); counts are atomic adds, so they are exact under the OpenMP loops over envs.
+ */
+#define STEP_CENSUS(X) \
+  X(NEXT_LANE_KNOWN, "next_lane_known") X(NEXT_LANE_DEFAULT, "next_lane_default") \
+  X(IDM_EGO_ABSENT, "idm_ego_absent") X(IDM_EGO_OBJECT, "idm_ego_object") X(IDM_EGO_VEHICLE, "idm_ego_vehicle") \
+  X(QP_FIRST_FACTOR_OK, "qp_first_factor_ok") X(QP_FIRST_FACTOR_FAILED, "qp_first_factor_failed") \
+  X(QP_LATER_FACTOR_OK, "qp_later_factor_ok") X(QP_LATER_FACTOR_FAILED, "qp_later_factor_failed") \
+  X(QP_START_S_SHIFTED, "qp_start_s_shifted") X(QP_START_S_KEPT, "qp_start_s_kept") \
+  X(QP_START_Z_SHIFTED, "qp_start_z_shifted") X(QP_START_Z_KEPT, "qp_start_z_kept") \
+  X(QP_PCOST_NEGATIVE, "qp_pcost_negative") X(QP_PCOST_NOT_NEGATIVE, "qp_pcost_not_negative") \
+  X(QP_CONVERGED, "qp_converged") X(QP_ITERATION_CAP, "qp_iteration_cap") X(QP_LOOP_RAN_OUT, "qp_loop_ran_out") \
+  X(NEG_SPEED_SUBSTEP, "negative_speed_at_substep") X(NEG_SPEED_STEP_END, "negative_speed_at_step_end") \
+  X(G_VX_ZERO, "g_vx_zero") X(G_VX_NONZERO, "g_vx_nonzero") \
+  X(HSS_NO_RELATION, "hss_no_relation") X(HSS_LEADER, "hss_leader") X(HSS_FRONT_ADJACENT, "hss_front_adjacent") \
+  X(HSS_REAR_ADJACENT, "hss_rear_adjacent") X(HSS_RAMP_HDV_TWIN, "hss_ramp_hdv_twin") \
+  X(MASS_NO_RELATION, "mass_no_relation") X(MASS_LEADER, "mass_leader") X(MASS_FRONT_ADJACENT, "mass_front_adjacent") \
+  X(MASS_REAR_ADJACENT, "mass_rear_adjacent") X(MASS_RAMP_HDV_TWIN, "mass_ramp_hdv_twin") \
+  X(CORNER_LEFT_BY_EGO_SIDE, "adj_corner_left_by_ego_side") X(CORNER_LEFT_BY_OTHER_SIDE, "adj_corner_left_by_other_side") \
+  X(CORNER_RIGHT, "adj_corner_right") \
+  X(OBST_LEADER, "obstacle_leader") X(OBST_LEADER_NOT_TAKEN, "obstacle_leader_not_taken") \
+  X(OBST_ADJ_NO_VEHICLE, "obstacle_adjacent_no_vehicle") X(OBST_ADJ_VEHICLE_FARTHER, "obstacle_adjacent_vehicle_farther") \
+  X(OBST_ADJ_VEHICLE_NEARER, "obstacle_adjacent_vehicle_nearer") X(OBST_ADJ_LATERAL_LE2, "obstacle_adjacent_lateral_le2") \
+  X(OBST_ADJ_LATERAL_GT4, "obstacle_adjacent_lateral_gt4") X(OBST_ADJ, "obstacle_adjacent") \
+  X(QP_EXACT_A_POS, "qp_exact_a_positive") X(QP_EXACT_A_NEG, "qp_exact_a_negative") X(QP_EXACT_A_ZERO, "qp_exact_a_zero") \
+  X(BOUNDS_OK, "check_bounds_ok") X(BOUNDS_FIRED, "check_bounds_fired") \
+  X(STEP_RC_OK, "substep_return_ok") X(STEP_RC_ERROR, "substep_return_error") \
+  X(STATUS_BOUNDS_CLEAR, "status_bounds_bit_clear") X(STATUS_BOUNDS_SET, "status_bounds_bit_set") \
+  X(ABORT_BOTH_ON, "abort_both_corners_on_lane") X(ABORT_LEFT_OFF, "abort_left_corner_off_lane") \
+  X(ABORT_RIGHT_OFF, "abort_right_corner_off_lane") \
+  X(VETO_HSS, "veto_hss") X(VETO_MASS, "veto_mass_can_abort") X(NO_VETO_MASS_CANNOT_ABORT, "no_veto_mass_cannot_abort") \
+  X(LC_ALLOWED, "lc_allowed") X(MASS_STOPPING_OVERRIDE, "mass_stopping_speed_override") \
+  X(CLIP_SPEED_ABOVE, "clip_speed_above_max") X(CLIP_SPEED_BELOW, "clip_speed_below_minus_max") \
+  X(CLIP_SPEED_INSIDE, "clip_speed_inside") \
+  X(CRASH_OBST_SPEED_ZERO, "obstacle_crash_speed_zero") X(CRASH_OBST_SPEED_NONZERO, "obstacle_crash_speed_nonzero") \
+  X(ACTION_IN_RANGE, "action_in_range") X(ACTION_OUT_OF_RANGE, "action_out_of_range") \
+  X(MASK_LEFT_NOT_BC1, "mask_left_not_on_bc1") X(MASK_LEFT_UNREACHABLE, "mask_left_bc0_unreachable") X(MASK_LEFT, "mask_left") \
+  X(MASK_RIGHT_NOT_BC0, "mask_right_not_on_bc0") X(MASK_RIGHT_UNREACHABLE, "mask_right_bc1_unreachable") X(MASK_RIGHT, "mask_right") \
+  X(REWARD_NOT_COLLAB, "reward_not_collaborating") X(REWARD_COLLAB_SREW, "reward_collaborating_srew") \
+  X(REWARD_COLLAB_MREW, "reward_collaborating_mrew") \
+  X(REWARD_SPEED_POS, "reward_headway_speed_positive") X(REWARD_SPEED_ZERO, "reward_headway_speed_zero") \
+  X(NOT_ZERO_NEG_SPEED, "not_zero_of_negative_speed") \
+  X(STEER_CACHE_HIT, "mm_math_steer_cache_hit") X(STEER_CACHE_STEER_VEL, "mm_math_steer_cache_miss_steer_vel") \
+  X(STEER_CACHE_NO_RESULT, "mm_math_steer_cache_miss_no_result") X(STEER_CACHE_CHANGED, "mm_math_steer_cache_miss_steer_changed") \
+  X(MTH_OBST_LATERAL_FAR, "headway_obstacle_lateral_far") X(MTH_OBST_BEHIND, "headway_obstacle_behind") \
+  X(MTH_OBST_AHEAD, "headway_obstacle_ahead") X(MTH_OBST_NEAREST, "headway_obstacle_nearest")
+#define X(id, name) CEN_##id,
+enum { STEP_CENSUS(X) CEN_COUNT };
+#undef X
+#define X(id, name) name,
+static const char *const step_census_names[CEN_COUNT] = {STEP_CENSUS(X)};
+#undef X
+static int64_t g_step_census[CEN_COUNT];
+static int g_step_census_on;
+static inline void cen_add(int k) {
+  if (!g_step_census_on) return;
+#pragma omp atomic
+  g_step_census[k]++;
+}
+#define CEN(id) cen_add(CEN_##id)
+/* Oracle-only: zero the counters; `enable` != 0 counts from now on, 0 stops counting. */
+void orc_step_census_reset(int32_t enable) {
+  memset(g_step_census, 0, sizeof g_step_census);
+  g_step_census_on = enable != 0;
+}
+/* Oracle-only: the counters since the last reset, summed over every call and env; returns how many there are. */
+int32_t orc_step_census(int64_t *out, int32_t n) {
+  for (int k = 0; k < n && k < CEN_COUNT; k++) out[k] = g_step_census[k];
+  return CEN_COUNT;
+}
+const char *orc_step_census_name(int32_t k) { return k >= 0 && k < CEN_COUNT ? step_census_names[k] : NULL; }
+
 /* ------------------------------------------------------------------ utils.py */
 
 /* utils.py:40-41 wrap_to_pi with Python float % semantics (sign of the divisor) */
@@ -249,16 +325,18 @@ static int closest_lane(double x, double y, double heading) {
 }
 /* road.py:67-109 next_lane on the merge graph a->b->c->d, j->k->b (no route, one successor each) */
 static int next_lane(int lane, double x, double y) {
-  switch (lane) {
+  switch (lane) { /* census: next_lane_default */
     case MM_LANE_AB0: /* 1 lane -> 2 lanes: closest by lane.distance, first min wins */
     case MM_LANE_KB0:
+      CEN(NEXT_LANE_KNOWN);
       return lane_distance(MM_LANE_BC0, x, y) <= lane_distance(MM_LANE_BC1, x, y) ? MM_LANE_BC0
                                                                                   : MM_LANE_BC1;
     case MM_LANE_BC0:
-    case MM_LANE_BC1: return MM_LANE_CD0; /* 2 lanes -> 1 lane */
-    case MM_LANE_CD0: return MM_LANE_CD0; /* KeyError branch: end of network */
-    case MM_LANE_JK0: return MM_LANE_KB0; /* same lane count: keep id 0 */
+    case MM_LANE_BC1: CEN(NEXT_LANE_KNOWN); return MM_LANE_CD0; /* 2 lanes -> 1 lane */
+    case MM_LANE_CD0: CEN(NEXT_LANE_KNOWN); return MM_LANE_CD0; /* KeyError branch: end of network */
+    case MM_LANE_JK0: CEN(NEXT_LANE_KNOWN); return MM_LANE_KB0; /* same lane count: keep id 0 */
   }
+  CEN(NEXT_LANE_DEFAULT);
   return lane;
 }
 static int lane_road(int lane) { /* (from,to) pair id */
@@ -291,6 +369,7 @@ static double steering_control(Veh *v, int target_lane) {
   double lane_next = s + v->speed * PURSUIT_TAU;
   double lane_future_heading = lane_heading_at(target_lane, lane_next);
   double lateral_speed_command = -KP_LATERAL * r;
+  if (v->speed < 0) CEN(NOT_ZERO_NEG_SPEED);
   double heading_command = m_asin(clipd(lateral_speed_command / not_zero(v->speed), -1, 1));
   double heading_ref = lane_future_heading + clipd(heading_command, -PI / 4, PI / 4);
   double heading_rate_command = KP_HEADING * wrap_to_pi(heading_ref - v->heading);
@@ -415,7 +494,9 @@ static double desired_gap(const Body *ego, const Body *front) {
 }
 /* behavior.py:111-139 acceleration (IDM); ego / front may be absent, ego may be an object */
 static double idm_acceleration(const Body *ego, const Body *front) {
-  if (!ego->present || ego->is_object) return 0;
+  if (!ego->present) { CEN(IDM_EGO_ABSENT); return 0; }
+  if (ego->is_object) { CEN(IDM_EGO_OBJECT); return 0; }
+  CEN(IDM_EGO_VEHICLE);
   double ego_target_speed = not_zero(ego->target_speed);
   double acceleration = IDM_COMFORT_ACC_MAX * (1 - m_p4(fmax(ego->speed, 0) / ego_target_speed));
   if (front->present) {
@@ -577,7 +658,7 @@ static int qp_factor(QpKkt *f, const double *Pd, const double G[4][QP_N], int m,
   for (int j = 0; j < QP_N; j++) {
     double t = S[j][j];
     for (int k = 0; k < j; k++) t -= f->L[j][k] * f->L[j][k];
-    if (!(t > 0.0)) return 0; /* potrf: ArithmeticError */
+    if (!(t > 0.0)) return 0; /* potrf: ArithmeticError; census: qp_first_factor_failed qp_later_factor_failed */
     f->L[j][j] = sqrt(t);
     for (int i = j + 1; i < QP_N; i++) {
       t = S[i][j];
@@ -621,20 +702,23 @@ static int qp_ipm(const double *Pd, const double *q, const double G[4][QP_N], co
   double s[4], z[4], d[4], di[4], lmbda[4], lmbdasq[4], rx[QP_N], rz[4], dx[QP_N], dz[4], ds[4], ws3[4];
   const double resx0 = fmax(1.0, sqrt(qp_dot(q, q, QP_N))), resz0 = fmax(1.0, sqrt(qp_dot(h, h, m)));
   for (int k = 0; k < m; k++) di[k] = 1.0;
-  if (!qp_factor(&kkt, Pd, G, m, di)) { x[0] = x[1] = x[2] = NAN; *iters_out = 0; return 0; } /* ValueError("Rank...") */
+  if (!qp_factor(&kkt, Pd, G, m, di)) { CEN(QP_FIRST_FACTOR_FAILED); x[0] = x[1] = x[2] = NAN; *iters_out = 0; return 0; } /* ValueError("Rank...") */
+  CEN(QP_FIRST_FACTOR_OK);
   for (int j = 0; j < QP_N; j++) x[j] = -q[j];
   for (int k = 0; k < m; k++) z[k] = h[k];
   qp_solve(&kkt, x, z);
   for (int k = 0; k < m; k++) s[k] = -z[k];
   {
     double nrm = sqrt(qp_dot(s, s, m)), ts = qp_maxneg(s, m);
-    if (ts >= -1e-8 * fmax(nrm, 1.0)) { const double a = 1.0 + ts; for (int k = 0; k < m; k++) s[k] = s[k] + a; }
+    if (ts >= -1e-8 * fmax(nrm, 1.0)) { CEN(QP_START_S_SHIFTED); const double a = 1.0 + ts; for (int k = 0; k < m; k++) s[k] = s[k] + a; }
+    else CEN(QP_START_S_KEPT);
     nrm = sqrt(qp_dot(z, z, m));
     double tz = qp_maxneg(z, m);
-    if (tz >= -1e-8 * fmax(nrm, 1.0)) { const double a = 1.0 + tz; for (int k = 0; k < m; k++) z[k] = z[k] + a; }
+    if (tz >= -1e-8 * fmax(nrm, 1.0)) { CEN(QP_START_Z_SHIFTED); const double a = 1.0 + tz; for (int k = 0; k < m; k++) z[k] = z[k] + a; }
+    else CEN(QP_START_Z_KEPT);
   }
   double gap = qp_dot(s, z, m);
-  for (int iters = 0; iters <= 100; iters++) {
+  for (int iters = 0; iters <= 100; iters++) { /* census: qp_loop_ran_out */
     for (int j = 0; j < QP_N; j++) rx[j] = q[j] + Pd[j] * x[j];
     const double f0 = 0.5 * (qp_dot(x, rx, QP_N) + qp_dot(x, q, QP_N));
     for (int j = 0; j < QP_N; j++) {
@@ -652,17 +736,22 @@ static int qp_ipm(const double *Pd, const double *q, const double G[4][QP_N], co
     const double pcost = f0, dcost = f0 + qp_dot(z, rz, m) - gap;
     int have_rel = 0;
     double relgap = 0;
-    if (pcost < 0.0) { relgap = gap / -pcost; have_rel = 1; }
-    else if (dcost > 0.0) { relgap = gap / dcost; have_rel = 1; }
+    if (pcost < 0.0) { CEN(QP_PCOST_NEGATIVE); relgap = gap / -pcost; have_rel = 1; }
+    else {
+      CEN(QP_PCOST_NOT_NEGATIVE);
+      if (dcost > 0.0) { relgap = gap / dcost; have_rel = 1; }
+    }
     const double pres = resz / resz0, dres = resx / resx0;
     if ((pres <= 1e-7 && dres <= 1e-7 && (gap <= 1e-7 || (have_rel && relgap <= 1e-6))) || iters == 100) {
       *iters_out = iters;
+      if (iters == 100) CEN(QP_ITERATION_CAP); else CEN(QP_CONVERGED);
       return iters == 100 ? 0 : 1;
     }
     if (iters == 0)
       for (int k = 0; k < m; k++) { d[k] = sqrt(s[k] / z[k]); di[k] = 1.0 / d[k]; lmbda[k] = sqrt(s[k] * z[k]); }
     for (int k = 0; k < m; k++) lmbdasq[k] = lmbda[k] * lmbda[k];
-    if (!qp_factor(&kkt, Pd, G, m, di)) { *iters_out = iters; return 0; } /* "Terminated (singular KKT matrix)" */
+    if (!qp_factor(&kkt, Pd, G, m, di)) { CEN(QP_LATER_FACTOR_FAILED); *iters_out = iters; return 0; } /* "Terminated (singular KKT matrix)" */
+    CEN(QP_LATER_FACTOR_OK);
     const double mu = gap / m;
     double sigma = 0.0, eta = 0.0, step = 1.0;
     for (int i = 0; i < 2; i++) {
@@ -705,6 +794,7 @@ static int qp_ipm(const double *Pd, const double *q, const double G[4][QP_N], co
     }
     gap = qp_dot(lmbda, lmbda, m);
   }
+  CEN(QP_LOOP_RAN_OUT);
   return 0; /* not reached */
 }
 /* the shield's QP through the IPM: P = diag(1, 1, 1e18), q = 0, rows [a 0 -1; 1 0 0; -1 0 0; (a 0 -1)] (cbf.py:288-322,386-403) */
@@ -746,6 +836,8 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
   int constrain_adj = 0;
   int near[MM_MAX_AGENTS];
   int m = close_vehicles_to(e, i, PERCEPTION_DIST, 5, near);
+  int n_rel = 0; /* census: relations this ego took from its neighbours */
+  if (veh->g_vx == 0) CEN(G_VX_ZERO); else CEN(G_VX_NONZERO);
 #ifdef ORC_QP_LOG
   g_qplog_dep_ol = g_qplog_dep_oa = -1;
 #endif
@@ -757,10 +849,12 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
     double ld = lane_distance_to(veh, o);
     if (!appr && (v_a || a_v)) {
       if (!s_oar.present && ld < 0) {
+        n_rel++; cen_add(mass ? CEN_MASS_REAR_ADJACENT : CEN_HSS_REAR_ADJACENT);
         s_oar.present = 1; /* veh.to_dict(): current state */
         s_oar.x = o->x; s_oar.heading = o->heading;
         s_oar.vx = o->speed * m_cos(o->heading); s_oar.speed = o->speed;
       } else if (!s_oa.present && ld >= 0) {
+        n_rel++; cen_add(mass ? CEN_MASS_FRONT_ADJACENT : CEN_HSS_FRONT_ADJACENT);
         s_oa.present = 1; /* veh.state_hist[-2] */
         s_oa.x = o->h2[0]; s_oa.vx = o->h2[1]; /* heading / speed only feed the unused dpsi term */
 #ifdef ORC_QP_LOG
@@ -771,8 +865,9 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
           else { a_oa_acc = CBF_ACC_LO; a_oa_steer = 0; gp_oa = 1; } /* HDV: no safe_action / fg_params (:129-135) */
           /* :138-160: the corner test always overrides the collaborate_adj expression */
           double cx, cy;
-          if (v_a == -1 || a_v == 1) get_corner(o, 0, &cx, &cy);
-          else get_corner(o, 1, &cx, &cy);
+          if (v_a == -1) { CEN(CORNER_LEFT_BY_EGO_SIDE); get_corner(o, 0, &cx, &cy); }
+          else if (a_v == 1) { CEN(CORNER_LEFT_BY_OTHER_SIDE); get_corner(o, 0, &cx, &cy); }
+          else { CEN(CORNER_RIGHT); get_corner(o, 1, &cx, &cy); }
           constrain_adj = !lane_on_lane(o->lane, cx, cy);
         }
       }
@@ -780,11 +875,13 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
       /* :162-184 adjacent HDV on the merging lane: constrain against its "digital twin" half a second
        * of ego travel ahead.  The reference edits the HDV's history record IN PLACE, so later egos of
        * the same sub-step read the shifted x as well -- reproduced by writing o->h2[0]. */
+      n_rel++; cen_add(mass ? CEN_MASS_RAMP_HDV_TWIN : CEN_HSS_RAMP_HDV_TWIN);
       o->h2[0] = o->h2[0] + 0.5 * (veh->speed * m_cos(veh->heading));
       s_oa.present = 1; s_oa.x = o->h2[0]; s_oa.vx = o->h2[1];
       constrain_adj = 1;
       a_oa_acc = CBF_ACC_LO; a_oa_steer = 0; gp_oa = 1;
     } else if (!s_ol.present && (is_same_lane(veh, o->lane) || appr) && ld > 0) {
+      n_rel++; cen_add(mass ? CEN_MASS_LEADER : CEN_HSS_LEADER);
       s_ol.present = 1;
       s_ol.x = o->h2[0]; s_ol.vx = o->h2[1];
 #ifdef ORC_QP_LOG
@@ -796,8 +893,20 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
       }
     }
   }
+  if (!n_rel) cen_add(mass ? CEN_MASS_NO_RELATION : CEN_HSS_NO_RELATION);
   /* obstacles (:213-246): one Obstacle at (420, 4) */
   if (!(veh->x > OBST_X)) {
+    if (g_step_census_on) { /* which way the two obstacle tests below go */
+      const double ady_ = fabs(OBST_Y - veh->y);
+      if ((!s_ol.present || OBST_X <= s_ol.x) && ady_ <= 2) CEN(OBST_LEADER); else CEN(OBST_LEADER_NOT_TAKEN);
+      if (s_oa.present && !(OBST_X <= s_oa.x)) CEN(OBST_ADJ_VEHICLE_NEARER);
+      else {
+        if (!s_oa.present) CEN(OBST_ADJ_NO_VEHICLE); else CEN(OBST_ADJ_VEHICLE_FARTHER);
+        if (!(2 < ady_)) CEN(OBST_ADJ_LATERAL_LE2);
+        else if (!(ady_ <= 4)) CEN(OBST_ADJ_LATERAL_GT4);
+        else CEN(OBST_ADJ);
+      }
+    }
     if ((!s_ol.present || OBST_X <= s_ol.x) && fabs(OBST_Y - veh->y) <= 2) {
       s_ol.present = 1; s_ol.x = OBST_X; s_ol.heading = 0; s_ol.vx = 0.0;
       s_ol.speed = 0.0 / m_cos(0.0); /* "cos_h" branch of simplified_control */
@@ -879,9 +988,9 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
               g_qplog_dep_ol, rows == 4 ? g_qplog_dep_oa : -1);
 #endif
   } else { /* exact KKT solution of min 1/2(d^2 + e^2 + 1e18 s^2): see tools/refshim/cvxopt */
-    if (a > 0) d = fmin(0.0, hc / a);
-    else if (a < 0) d = fmax(0.0, hc / a);
-    else d = 0.0;
+    if (a > 0) { CEN(QP_EXACT_A_POS); d = fmin(0.0, hc / a); }
+    else if (a < 0) { CEN(QP_EXACT_A_NEG); d = fmax(0.0, hc / a); }
+    else { CEN(QP_EXACT_A_ZERO); d = 0.0; }
     d = fmin(fmax(d, lo), hi);
   }
   double u_safe0 = u[0] + d, u_safe1;
@@ -889,7 +998,8 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
   veh->qp_h[3] = h3; veh->qp_d = d;
   int rc = 0;
   veh->qp_bounds = (u_safe0 - 0.001 > v_max || u_safe0 + 0.001 < v_min); /* cbf.py:87-96 */
-  if (veh->qp_bounds) rc = MM_ERR_QP_BOUNDS;
+  if (veh->qp_bounds) { CEN(BOUNDS_FIRED); rc = MM_ERR_QP_BOUNDS; }
+  else CEN(BOUNDS_OK);
 
   { /* update_status (cbf.py:341-351) with u_status = [u_safe (QP), u_ll[2:]] */
     double hls_lon = px_lon + q_lon;
@@ -912,24 +1022,33 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
                    ((hls_lonr >= 0) && (hlds_lonr + (eta - 1) * hls_lonr) >= 0);
   veh->lc_margin = fmin(fmin(hls_lona, hlds_lona + (eta - 1) * hls_lona),
                         fmin(hls_lonr, hlds_lonr + (eta - 1) * hls_lonr));
+  if (lc_allowed) CEN(LC_ALLOWED);
   if (!mass) {
     if (!lc_allowed) { /* :501-506 */
+      CEN(VETO_HSS);
       veh->target_lane = veh->lane;
       u_safe1 = lc_steering_control(veh, veh->target_lane);
       flags &= ~MM_FLAG_IS_LC_SAFE;
     }
   } else {
     double cx, cy;
-    int can_abort_lc = 1; /* :728-736: both front corners still on the current lane */
+    int can_abort_lc; /* :728-736: both front corners still on the current lane */
     get_corner(veh, 0, &cx, &cy);
-    can_abort_lc = can_abort_lc && lane_on_lane(veh->lane, cx, cy);
+    can_abort_lc = lane_on_lane(veh->lane, cx, cy);
+    if (!can_abort_lc) CEN(ABORT_LEFT_OFF);
     get_corner(veh, 1, &cx, &cy);
-    can_abort_lc = can_abort_lc && lane_on_lane(veh->lane, cx, cy);
+    if (can_abort_lc) {
+      can_abort_lc = lane_on_lane(veh->lane, cx, cy);
+      if (can_abort_lc) CEN(ABORT_BOTH_ON); else CEN(ABORT_RIGHT_OFF);
+    }
+    if (!can_abort_lc && !lc_allowed) CEN(NO_VETO_MASS_CANNOT_ABORT);
     if (can_abort_lc && !lc_allowed) { /* :739-744 */
+      CEN(VETO_MASS);
       veh->target_lane = veh->lane;
       u_safe1 = lc_steering_control(veh, veh->target_lane);
       flags &= ~MM_FLAG_IS_LC_SAFE;
     } else if ((veh->hl_action == 2 || veh->hl_action == 0) && veh->speed < STOPPING_SPEED) {
+      CEN(MASS_STOPPING_OVERRIDE);
       u_safe0 = u[0]; /* :746-750 */
     }
     /* can_collaborate_adj (cbf.py:424-430) on u_safe_ma (copied before the edits above) */
@@ -947,8 +1066,9 @@ static int safety_layer(const MMConfig *cfg, Env *e, int i, double dt, double *s
 /* kinematics.py:143-152 (+ safe_controller.py:100-104 for MDPLCVehicle) */
 static void clip_actions(Veh *v, int is_lc) {
   if (v->crashed) { v->act_steer = 0; v->act_acc = -1.0 * v->speed; }
-  if (v->speed > MAX_SPEED) v->act_acc = fmin(v->act_acc, 1.0 * (MAX_SPEED - v->speed));
-  else if (v->speed < -MAX_SPEED) v->act_acc = fmax(v->act_acc, 1.0 * (MAX_SPEED - v->speed));
+  if (v->speed > MAX_SPEED) { CEN(CLIP_SPEED_ABOVE); v->act_acc = fmin(v->act_acc, 1.0 * (MAX_SPEED - v->speed)); }
+  else if (v->speed < -MAX_SPEED) { CEN(CLIP_SPEED_BELOW); v->act_acc = fmax(v->act_acc, 1.0 * (MAX_SPEED - v->speed)); }
+  else CEN(CLIP_SPEED_INSIDE);
   if (is_lc) v->act_acc = clipd(v->act_acc, LC_MIN_ACC, LC_MAX_ACC);
 }
 
@@ -959,6 +1079,7 @@ static int vehicle_step(const MMConfig *cfg, Env *e, int i, double dt) {
   const int is_lc = cfg->env_kind == MM_ENV_V1 && !hdv; /* MDPLCVehicle; HDVs use Vehicle.step */
   int rc = 0;
   if (hdv) v->timer += dt; /* IDMVehicle.step behavior.py:102-109 */
+  if (v->speed < 0) CEN(NEG_SPEED_SUBSTEP);
   clip_actions(v, is_lc);
   double steer = v->act_steer, acc = v->act_acc;
   v->qp_rows = 0; v->qp_a = NAN; v->qp_d = NAN; v->lc_margin = NAN;
@@ -972,6 +1093,11 @@ static int vehicle_step(const MMConfig *cfg, Env *e, int i, double dt) {
      * of the steering angle and one of the new heading (include/mm_math.h, "angle-sum forms"); beta itself is never formed */
     const int sv = is_lc && v->steer_vel;
     double ss, cs, sb, cb, sh, ch;
+    /* census (math mode 1 only): which way the test below goes */
+    if (sv) CEN(STEER_CACHE_STEER_VEL);
+    else if (!v->sc_valid) CEN(STEER_CACHE_NO_RESULT);
+    else if (steer == v->sc_steer) CEN(STEER_CACHE_HIT);
+    else CEN(STEER_CACHE_CHANGED);
     if (!sv && v->sc_valid && steer == v->sc_steer) { ss = v->sc_sin; cs = v->sc_cos; } /* steer IS the last steering_control result */
     else mmm_sincos(sv ? v->steer_angle : steer, &ss, &cs); /* crashed (0 -> (0, 1)), a persisting IDM action, steer_vel */
     mmm_slip_sincos(1.0 / 2 * (ss / cs), &sb, &cb);
@@ -1057,8 +1183,11 @@ static int simulate(const MMConfig *cfg, Env *e, const int32_t *actions, double 
   int rc = 0, order[MM_MAX_AGENTS];
   for (int k = 0; k < nsub; k++) {
     if (e->time % nsub == 0) /* action_type.act(action): action.py:226-231 */
-      for (int i = 0; i < e->n_ctrl; i++) /* an action outside 0..4 (KeyError in the reference, latched by mm_step) acts as IDLE */
-        mdp_act(&e->v[i], (actions[i] < 0 || actions[i] >= MM_N_ACTIONS) ? 1 : actions[i], is_lc);
+      for (int i = 0; i < e->n_ctrl; i++) { /* an action outside 0..4 (KeyError in the reference, latched by mm_step) acts as IDLE */
+        const int bad = actions[i] < 0 || actions[i] >= MM_N_ACTIONS;
+        if (bad) CEN(ACTION_OUT_OF_RANGE); else CEN(ACTION_IN_RANGE);
+        mdp_act(&e->v[i], bad ? 1 : actions[i], is_lc); /* census: action_out_of_range */
+      }
     sort_by_x_desc(e, order); /* road.act: front to back; HDVs read what earlier vehicles already decided */
     for (int r = 0; r < e->n; r++) {
       if (e->v[order[r]].kind == 2) idm_act(e, order[r]);
@@ -1073,7 +1202,8 @@ static int simulate(const MMConfig *cfg, Env *e, const int32_t *actions, double 
       g_qplog_rank = r;
 #endif
       int rr = vehicle_step(cfg, e, order[r], dt);
-      if (rr) rc = rr;
+      if (rr) { CEN(STEP_RC_ERROR); rc = rr; }
+      else CEN(STEP_RC_OK);
 #ifdef ORC_QP_LOG
       g_qplog_stepped |= 1u << order[r];
 #endif
@@ -1090,6 +1220,7 @@ static int simulate(const MMConfig *cfg, Env *e, const int32_t *actions, double 
         }
       }
       if (!v->crashed && is_colliding(v, OBST_X, OBST_Y, OBST_LENGTH, OBST_WIDTH, 0.0)) {
+        if (fabs(v->speed) <= 0) CEN(CRASH_OBST_SPEED_ZERO); else CEN(CRASH_OBST_SPEED_NONZERO);
         v->speed = fabs(v->speed) <= 0 ? v->speed : 0.0;
         v->crashed = 1;
       }
@@ -1111,12 +1242,15 @@ static int simulate(const MMConfig *cfg, Env *e, const int32_t *actions, double 
         t[MM_T_QP_H2 * A] = v->qp_h[2]; t[MM_T_QP_H3 * A] = v->qp_h[3];
         t[MM_T_QP_D * A] = v->qp_d; t[MM_T_LC_MARGIN * A] = v->lc_margin;
         if (v->qp_rows > 0) {
+          if (v->qp_bounds) CEN(STATUS_BOUNDS_SET); else CEN(STATUS_BOUNDS_CLEAR);
           t[MM_T_STATUS * A] = (double)(MM_ST_RAN | (v->qp_optimal ? MM_ST_IS_OPTIMAL : 0) | (v->lon_safe ? MM_ST_IS_SAFE : 0) |
-                                        (v->lon_invariant ? MM_ST_IS_INVARIANT : 0) | (v->qp_bounds ? MM_ST_QP_BOUNDS : 0));
+                                        (v->lon_invariant ? MM_ST_IS_INVARIANT : 0) | (v->qp_bounds ? MM_ST_QP_BOUNDS : 0)); /* census: status_bounds_bit_set */
           t[MM_T_HEADWAY * A] = v->shield_headway;
         }
       }
     }
+    if (g_step_census_on)
+      for (int i = 0; i < e->n; i++) if (e->v[i].speed < 0) CEN(NEG_SPEED_STEP_END);
     if (is_terminal(cfg, e)) break;
   }
   return rc;
@@ -1164,8 +1298,12 @@ static void action_mask(const MMConfig *cfg, const Env *e, uint8_t *out /* [n][5
     for (int i = 0; i < e->n_ctrl; i++) {
       const Veh *v = &e->v[i];
       m[1] = 1;
-      if (v->lane == MM_LANE_BC1 && lane_is_reachable_from(MM_LANE_BC0, v->x, v->y)) m[0] = 1;
-      if (v->lane == MM_LANE_BC0 && lane_is_reachable_from(MM_LANE_BC1, v->x, v->y)) m[2] = 1;
+      if (v->lane != MM_LANE_BC1) CEN(MASK_LEFT_NOT_BC1);
+      else if (lane_is_reachable_from(MM_LANE_BC0, v->x, v->y)) { CEN(MASK_LEFT); m[0] = 1; }
+      else CEN(MASK_LEFT_UNREACHABLE);
+      if (v->lane != MM_LANE_BC0) CEN(MASK_RIGHT_NOT_BC0);
+      else if (lane_is_reachable_from(MM_LANE_BC1, v->x, v->y)) { CEN(MASK_RIGHT); m[2] = 1; }
+      else CEN(MASK_RIGHT_UNREACHABLE);
       if (v->speed_index < 5 - 1) m[3] = 1;
       if (v->speed_index > 0) m[4] = 1;
     }
@@ -1196,10 +1334,14 @@ static double compute_headway_distance(const Env *e, int i) {
 /* merge_env_v1.py:64-89 (v1 "default" agent_reward delegates here, :446-447) */
 static double agent_reward(const MMConfig *cfg, const Env *e, int i) {
   const Veh *v = &e->v[i];
+  if (v->speed > 0) CEN(REWARD_SPEED_POS); else CEN(REWARD_SPEED_ZERO);
   if (cfg->env_kind == MM_ENV_V1 && cfg->agent_reward != 0) {
     /* MergeEnvLCMARL._agent_reward, "srew" / "mrew" (merge_env_v1.py:439-474) */
     const int is_mrew = cfg->agent_reward == 2;
     double lo = cfg->reward_speed_lo, hi = cfg->reward_speed_hi;
+    if (!(v->flags & MM_FLAG_IS_COLLABORATING)) CEN(REWARD_NOT_COLLAB);
+    else if (is_mrew) CEN(REWARD_COLLAB_MREW);
+    else CEN(REWARD_COLLAB_SREW);
     if ((v->flags & MM_FLAG_IS_COLLABORATING) && is_mrew) hi = lo + (hi - lo) / 2;
     double scaled = 0 + (v->speed - lo) * (1 - 0) / (hi - lo);
     double merging2 = 0;
@@ -1265,9 +1407,12 @@ static double min_time_headway(const Env *e) {
   for (int i = 0; i < e->n_ctrl; i++) {
     const Veh *v = &e->v[i];
     double hd = compute_headway_distance(e, i);
+    if (!(fabs(OBST_Y - v->y) <= 2)) CEN(MTH_OBST_LATERAL_FAR);
+    else if (!(OBST_X > v->x)) CEN(MTH_OBST_BEHIND);
+    else CEN(MTH_OBST_AHEAD);
     if (fabs(OBST_Y - v->y) <= 2 && OBST_X > v->x) {
       double d = OBST_X - v->x;
-      if (d < hd) hd = d;
+      if (d < hd) { CEN(MTH_OBST_NEAREST); hd = d; }
     }
     hd = hd - VEH_LENGTH;
     double vx = v->speed * m_cos(v->heading);

@@ -67,7 +67,27 @@ def library():
         lib.orc_supervise_census.argtypes = [vp, i32]
         lib.orc_supervise_census_name.argtypes = [i32]
         lib.orc_supervise_census_name.restype = C.c_char_p
+        # the step's census (mm_oracle.c, "Census of the step")
+        lib.orc_step_census_reset.argtypes = [i32]
+        lib.orc_step_census_reset.restype = None
+        lib.orc_step_census.argtypes = [vp, i32]
+        lib.orc_step_census_name.argtypes = [i32]
+        lib.orc_step_census_name.restype = C.c_char_p
     return _LIB
+
+
+def step_census_reset(enable=True):
+    """Zero the step's branch / state counters; count from now on (enable) or stop counting."""
+    library().lib.orc_step_census_reset(int(bool(enable)))
+
+
+def step_census():
+    """{name: count} since the last step_census_reset, summed over every call and env."""
+    lib = library().lib
+    n = lib.orc_step_census(None, 0)
+    out = (C.c_int64 * n)()
+    lib.orc_step_census(C.cast(out, C.c_void_p), n)
+    return {lib.orc_step_census_name(k).decode(): int(out[k]) for k in range(n)}
 
 
 def set_math_mode(mode):

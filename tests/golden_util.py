@@ -29,9 +29,10 @@ def episode_files(pattern="*_*.npz"):
     """ep_*: random / idle tapes from reference spawns; sc_*: scripted crash scenarios (test/cbf);
     mx_*: mixed traffic (CAVs + IDM/MOBIL HDVs); rw_*: srew / mrew agent rewards; sl_*: with stand-alone
     safety_layer probes; sv_*: lateral_control = "steer_vel"; ipm_*: `solvers.qp` answered by the coneqp
-    restatement (MM_QP_IPM mode); am_*: action masking on; ed_*: placed edge cases."""
+    restatement (MM_QP_IPM mode); am_*: action masking on; ed_*: placed edge cases; cv_* (and ipm_cv_*): placed for the
+    branches and states of the step that the oracle's census found no other tape to reach (cv_index.json)."""
     return sorted(f for f in glob.glob(os.path.join(GOLDEN, pattern))
-                  if os.path.basename(f).split("_")[0] in ("ep", "sc", "mx", "rw", "sl", "sv", "ipm", "am", "ed"))
+                  if os.path.basename(f).split("_")[0] in ("ep", "sc", "mx", "rw", "sl", "sv", "ipm", "am", "ed", "cv"))
 
 
 def is_ipm(meta):

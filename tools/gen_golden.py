@@ -18,6 +18,8 @@ Fixture families
   ipm_*.npz        the same with `solvers.qp` answered by the coneqp restatement (MM_QP_IPM mode)
   am_*.npz         action_masking = True (abstract.py:219-240,474-481, incl. the row aliasing)
   ed_*.npz         placed edge cases: x < 0 terminal, |v| > 40 clamp, a <= 0 and lo > hi QPs
+  cv_*.npz         placed for the branches / states of the step no other tape reaches (+ ipm_cv_* twins), listed with the
+                   census names they are there for in cv_index.json; cvqp.npz: QPs whose KKT factorisation fails
 """
 import os
 import sys
@@ -429,6 +431,89 @@ def gen_reset():
     print("reset.json: %d fixed-count resets, %d drawn-count resets" % (len(rows), len(counts)))
 
 
+def _cv_tapes():
+    """cv_* / ipm_cv_*: name -> (env id, shield, placement, one action row, steps, run_episode keywords), and
+    name -> the census names the tape is there to reach."""
+    v0, v1 = "merge-multi-agent-v0", "merge-multi-agent-v1"
+    hss, mass, I = "cbf-avs_cint", "cbf-cav", 1
+    tapes, index = {}, {}
+
+    def add(name, reach, env_id, shield, placement, steps, ipm_twin=False, **kw):
+        script = (I,) * sum(1 for row in placement if len(row) < 5)  # (HDVs, the rows that end in "h", take no action)
+        tapes[name] = (env_id, shield, placement, script, steps, kw)
+        index[name] = list(reach)
+        if ipm_twin:  # the branch sits in or behind the QP: once more with the interior-point iterate
+            tapes["ipm_" + name] = (env_id, shield, placement, script, steps, dict(kw, qp="coneqp"))
+            index["ipm_" + name] = list(reach)
+
+    # reversing vehicles beyond -MAX_SPEED (kinematics.py:151-152) and a slow one (utils.not_zero of a negative speed in
+    # steering_control); the speed is floored at 0 by the end of the first sub-step (kinematics.py:140, safe_controller.py:160).
+    # A controlled vehicle's own command is above the bound 40 - speed there (speed control asks for (10 - speed) / 0.6), so the
+    # clip takes the branch without binding; the HDV's IDM command is at most 3, so its recorded acceleration IS the bound, 85
+    rev = [(100.0, 0.0, -45.0), (60.0, 0.0, -3.0), (160.0, 0.0, 20.0), (220.0, 0.0, -45.0, None, "h")]
+    names = ("clip_speed_below_minus_max",)  # (the ed_* tapes already hold slow reversing vehicles)
+    add("cv_v0_reverse", names, v0, "none", rev, 6)
+    for tag, shield in (("none", "none"), ("hss", hss), ("mass", mass)):
+        add("cv_v1_reverse_%s" % tag, names, v1, shield, rev, 6)
+    # the obstacle taken as the adjacent vehicle although a real adjacent vehicle is there, farther away (decentral_layer.py:230-246):
+    # an HDV at rest on (b, c, 1) just past the obstacle (an HDV: a CAV starting from rest solves QPs of its own whose bound
+    # d <= v_max - u passes through 0, a case that belongs to the QP tests, not to this branch)
+    for tag, shield in (("hss", hss), ("mass", mass)):
+        add("cv_v1_obstacle_adj_%s" % tag, ("obstacle_adjacent_vehicle_farther",), v1, shield,
+            [(384.0, 0.5, 10.0), (423.4, 4.0, 0.0, None, "h")], 4, ipm_twin=True)
+    # a vehicle that hits the obstacle at speed exactly 0 (kinematics.py:185-200: min by abs of the two speeds)
+    rest = [(417.5, 4.0, -2.0), (100.0, 0.0, 20.0)]
+    add("cv_v0_crash_at_rest", ("obstacle_crash_speed_zero",), v0, "none", rest, 2)
+    add("cv_v1_crash_at_rest_mass", ("obstacle_crash_speed_zero",), v1, mass, rest, 2)
+    # action masking with a vehicle on (b, c, 1) more than two lane widths from (b, c, 0) (abstract.py:219-240, lane.py:78-90)
+    # -- slow, so that it is still out of reach when each of the three steps ends and the recorded masks have LANE_LEFT off
+    add("cv_v0_mask_far", ("mask_left_bc0_unreachable",), v0, "none", [(350.0, 11.0, 2.0), (340.0, 0.0, 15.0)], 3, action_masking=True)
+    # "srew" with a collaborating ego (merge_env_v1.py:439-474): the adjacent vehicle's front corner is off its lane
+    add("cv_v1_srew_collab_mass", ("reward_collaborating_srew",), v1, mass, [(330.0, 0.0, 20.0), (370.0, 2.6, 20.0)], 4,
+        ipm_twin=True, agent_reward="srew")
+    # min_time_headway's obstacle term for a vehicle in the obstacle's lane band that is already past it (merge_env_v1.py:373-386)
+    past = [(430.0, 3.0, 15.0), (380.0, 0.0, 20.0)]
+    add("cv_v0_past_obstacle", ("headway_obstacle_behind",), v0, "none", past, 4)
+    add("cv_v1_past_obstacle_mass", ("headway_obstacle_behind",), v1, mass, past, 4)
+    # two HDVs that collide off the lane centre in the first sub-step of a step: for the rest of that step they stop acting
+    # (behavior.py:83-84) and steer 0 (kinematics.py:144-146) although their last steering_control result was not 0 -- the
+    # one case in which the device arithmetic of the bicycle step (include/mm_math.h) cannot reuse that result's sine and cosine
+    crash = [(60.0, 0.0, 25.0), (20.0, 10.5, 24.0), (150.0, 0.6, 22.0, None, "h"), (153.0, 0.6, 18.0, None, "h")]
+    for tag, shield in (("none", "none"), ("mass", mass)):
+        add("cv_v1_hdv_crash_offcentre_%s" % tag, ("mm_math_steer_cache_miss_steer_changed",), v1, shield, crash, 3)
+    return tapes, index
+
+
+CV_TAPES, CV_INDEX = _cv_tapes()
+
+
+def gen_cv_qp_table():
+    """QPs of get_G's form whose KKT factorisation fails in the reference-side coneqp (tools/refshim/cvxopt/coneqp.py): the
+    first one (ValueError "Rank...": no iterate) and a later one ("Terminated (singular KKT matrix)").  No state of the env
+    gets there (|a| = |g.vx dt| <= 1/15 and h is a few hundred at most), so they are rows of a table for the stand-alone QP
+    entry, not tapes."""
+    rows_ = [(np.inf, [1.0, 2.0, 2.0, 0.0], 3), (np.inf, [-50.0, 0.4, 0.8, -60.0], 4),
+             (1e300, [-50.0, 0.4, 0.8, -60.0], 3), (1e300, [1.0, 2.0, 2.0, 0.0], 4),
+             (-1e200, [-50.0, 0.4, 0.8, -60.0], 3), (-1e200, [-50.0, 0.4, 0.8, -60.0], 4)]
+    n = len(rows_)
+    G, h, rows = np.zeros((n, 4, 3)), np.zeros((n, 4)), np.zeros(n, dtype=np.int32)
+    x, status, iters = np.zeros((n, 3)), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
+    P = np.diag([1.0, 1.0, 1e18])
+    for k, (a, hk, m) in enumerate(rows_):
+        G[k, 0] = (a, 0.0, -1.0); G[k, 1] = (1.0, 0.0, 0.0); G[k, 2] = (-1.0, 0.0, 0.0)
+        if m == 4:
+            G[k, 3] = (a, 0.0, -1.0)
+        h[k, :m], rows[k] = hk[:m], m
+        try:
+            xk, st, it = cvxopt.ipm(P, np.zeros(3), G[k, :m], h[k, :m])
+        except (ValueError, ArithmeticError) as exc:  # coneqp raises where the first factorisation fails
+            xk, st, it = np.full(3, np.nan), "unknown", 0
+            print("cvqp row %d: %s" % (k, exc))
+        x[k], status[k], iters[k] = xk, st == "optimal", it
+        print("cvqp row %d: a=%g rows=%d -> x=%s status=%s iterations=%d" % (k, a, m, xk, st, it))
+    np.savez_compressed(os.path.join(OUT, "cvqp.npz"), G=G, h=h, rows=rows, x=x, status=status, iters=iters)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if not ONLY:
@@ -555,10 +640,24 @@ def main():
         metas.append(run_episode("ed_v1_wreck_%s" % tag, v1, shield, 2, 0, 0, 0.5, 0.03125, max_steps=40,
                                  scripted=[(I, I)], placement=wreck, n_hdv=3))
     metas.append(run_episode("ed_v0_wreck", v0, "none", 2, 0, 0, 1.2, 0.0, max_steps=40, scripted=[(I, A["FASTER"])], placement=wreck, n_hdv=3))
+    # (11) coverage tapes: placed so that the step reaches what the census of the oracle (orc_step_census, tests/
+    # test_tape_census_host.py) found no other tape to reach; CV_TAPES / CV_INDEX below say which name each one is there for
+    for name, (env_id, shield, placement, script, steps, kw) in CV_TAPES.items():
+        ht, eta = (1.2, 0.0) if env_id == v0 else (0.5, 0.03125)
+        n_hdv = sum(1 for row in placement if len(row) > 4)
+        metas.append(run_episode(name, env_id, shield, len(placement) - n_hdv, 0, 0, ht, eta, max_steps=steps, scripted=[script],
+                                 placement=placement, n_hdv=n_hdv, **kw))
+    if not ONLY or any(o.startswith("cv") for o in ONLY):
+        with open(os.path.join(OUT, "cv_index.json"), "w") as fh:
+            json.dump({k: CV_INDEX[k] for k in sorted(CV_INDEX)}, fh, indent=1)
+        gen_cv_qp_table()
     # the index is rebuilt from the tapes on disk, so a partial regeneration (`only <prefix> ...`) keeps the rest
     import glob
     metas = []
+    families = ("am_", "cv_", "ed_", "ep_", "ipm_", "mappo_dropin_", "mx_", "rw_", "sc_", "sl_", "sv_")  # (the others keep their own index)
     for f in sorted(glob.glob(os.path.join(OUT, "*_*.npz"))):
+        if not os.path.basename(f).startswith(families):
+            continue
         m = json.loads(str(np.load(f)["meta"]))
         m["name"] = os.path.basename(f)[:-4]
         metas.append(m)
