@@ -369,7 +369,7 @@ int32_t mm_sample_actions(const float *logp, int64_t n, int32_t n_a, uint64_t se
  * The same with the actor network in front (marl/single_agent/Model_common.py:5-22: n_s -> hidden -> hidden
  * -> n_a, ReLU, log-softmax; weights in torch nn.Linear layout [out][in], float32): one launch from the
  * observation rows mm_step wrote to the next actions.  HIP build: f32-input MFMA, activations kept in
- * registers (marl-mass_amd/csrc/mm_kernels.hip policy_kernel).  hidden must be one of the reference's two values:
+ * registers (marl-mass_amd/csrc/mm_main.hip policy_kernel).  hidden must be one of the reference's two values:
  * 128 or 512 in the HIP library (512, the lateral_control = steer_vel configurations, is forwarded to
  * mm_policy_wide_act, include/mm_policy_wide.h, which also needs W2 16-byte aligned), 128 only in the CPU oracle;
  * n_s <= 32, n_a <= 8.  obs: DEV float[n][n_s]; logp: optional DEV float[n][n_a] (the log-softmax

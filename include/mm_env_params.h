@@ -7,7 +7,7 @@
  * batch's envs, read by the step kernel where it would read the MMConfig values, so one launch steps a whole
  * eta x tau x HEADWAY_TIME grid (x seeds) and a training batch can randomise the safety margin per env.
  *
- * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_kernels.hip); the CPU oracle has no counterpart, its envs are
+ * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_main.hip); the CPU oracle has no counterpart, its envs are
  * uniform.  Optional symbol, like mm_supervise_dmc: MM_ABI_VERSION does not change and a caller looks it up before use.
  *
  * Scope: merge-multi-agent-v1 with the HSS or MASS shield (cbf-avs_cint / cbf-cav), both QP modes, CAV-only and mixed

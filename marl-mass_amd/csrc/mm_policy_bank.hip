@@ -1,7 +1,7 @@
 // mm_policy_bank.hip -- K actors of one shape on the K contiguous groups of one batch, forward fused with the action sample
 // (include/mm_policy_bank.h).
 //
-// Every member is marl/single_agent/Model_common.py:5-22 ActorNetwork at hidden 128, computed as policy_kernel (mm_kernels.hip)
+// Every member is marl/single_agent/Model_common.py:5-22 ActorNetwork at hidden 128, computed as policy_kernel (mm_main.hip)
 // computes it: on f32-input MFMA in the transposed, one-wave-per-32-agents layout that mm_policy_mfma.h describes, activations in
 // registers, layer 3 as 64 FMAs per row per lane plus one cross-half add, log-softmax in fp32 in torch's order, the inverse-CDF
 // sample of mm_sample_actions in fp64, written by h = 0.  The sequence of floating-point operations of a row is policy_kernel's,

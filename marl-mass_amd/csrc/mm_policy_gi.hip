@@ -1,7 +1,7 @@
 // mm_policy_gi.hip -- MAPPO_GI's shared actor-critic fused with the action sample (include/mm_policy_gi.h).
 //
 // marl/single_agent/Model_gi.py:137-216 ActorCriticNetwork(state_split=True), hidden 128, on f32-input MFMA in the transposed,
-// one-wave-per-32-agents layout that mm_policy_mfma.h describes (it is policy_kernel's in mm_kernels.hip): an accumulator tile
+// one-wave-per-32-agents layout that mm_policy_mfma.h describes (it is policy_kernel's in mm_main.hip): an accumulator tile
 // is directly the B operand of the next layer and activations never leave the register file.
 //
 //   layer 1  the three split linears as 5 block-diagonal output tiles: tile 0 = fc11 (32 outputs, K = 5 -> 3 k-steps of

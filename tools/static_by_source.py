@@ -3,9 +3,9 @@
 
     python tools/static_by_source.py [--root CHECKOUT] [--label NAME] [--json OUT] [--top 40] [--exec-regions]
 
-Compiles the single-instantiation form of marl-mass_amd/csrc/mm_kernels.hip for gfx950 to assembly with line tables
+Compiles the single-object, single-instantiation form of the step library (marl-mass_amd/csrc/mm_step_all.hip) for gfx950 to assembly with line tables
 (-gline-tables-only: code generation is the release build's), walks the body of step_kernel<8, MM_ENV_V1, MM_SHIELD_MASS, false,
-false, false, false> and books every instruction on the `.loc` in force, i.e. on the innermost inlined source line.  Output:
+false, false, false, false> and books every instruction on the `.loc` in force, i.e. on the innermost inlined source line.  Output:
 totals per file, per function of include/mm_math.h and marl-mass_amd/csrc/mm_device.h (by the line ranges of their
 definitions), literal s_mov_b32, fp64 divisions (v_div_fmas_f64) per function, and the heaviest lines.
 
@@ -21,7 +21,7 @@ import re
 import subprocess
 import tempfile
 
-KERNEL = "step_kernel<8, 1, 2, false, false, false, false>"
+KERNEL = "step_kernel<8, 1, 2, false, false, false, false, false>"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-DMM_ONLY_G=8", "-DMM_ONLY_MIXED=false",
          "-DMM_ONLY_SHIELD=2", "-gline-tables-only", "--cuda-device-only", "-S"]
 
@@ -57,7 +57,7 @@ def main():
     csrc = os.path.join(args.root, "marl-mass_amd", "csrc")
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, "k.s")
-        subprocess.check_call([args.hipcc] + FLAGS + ["-o", asm, "mm_kernels.hip"], cwd=csrc)
+        subprocess.check_call([args.hipcc] + FLAGS + ["-o", asm, "mm_step_all.hip"], cwd=csrc)
         text = open(asm).read().splitlines()
     syms = [m.group(1) for ln in text for m in [re.match(r"(_Z\w*step_kernel\w*):", ln)] if m]
     dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.splitlines()
