@@ -337,6 +337,12 @@ class CLib(object):
             lib.mm_policy_bank_act.restype = i32
             lib.mm_policy_bank_grid.argtypes = [i32, C.POINTER(i64), C.POINTER(i32)]
             lib.mm_policy_bank_grid.restype = i32
+        # K hidden-128 shared actor-critics on the K contiguous groups of one batch + sample + value in one launch
+        # (include/mm_policy_gi_bank.h), also libmm_hip.so only; its grid split is mm_policy_bank_grid
+        self.has_policy_gi_bank = hasattr(lib, "mm_policy_gi_bank_act")
+        if self.has_policy_gi_bank:
+            lib.mm_policy_gi_bank_act.argtypes = [vp, i64, i32, C.POINTER(MMGiParams), i32, C.POINTER(i64), i32, i32, u64, vp, vp, vp, vp, vp]
+            lib.mm_policy_gi_bank_act.restype = i32
         # the shared actor-critic's loss + parameter gradient (include/mm_policy_gi_train.h), also libmm_hip.so only
         self.has_policy_gi_train = hasattr(lib, "mm_policy_gi_train")
         if self.has_policy_gi_train:
@@ -504,6 +510,11 @@ class CLib(object):
         if not self.has_policy_bank:
             raise NotImplementedError("%s does not export mm_policy_bank_act: the one-launch policy bank needs the HIP library"
                                       % os.path.basename(self.path))
+
+    def require_policy_gi_bank(self):
+        if not self.has_policy_gi_bank:
+            raise NotImplementedError("%s does not export mm_policy_gi_bank_act: the one-launch bank of shared actor-critics "
+                                      "needs the HIP library" % os.path.basename(self.path))
 
     def require_policy_gi_train(self):
         if not self.has_policy_gi_train:

@@ -24,7 +24,8 @@ critic heads; fused on the device as `mm_policy_gi_act`, include/mm_policy_gi.h)
 
 Bank mode: the reference trains one model per configuration and seed; a list of K actors with `group_envs` drives the K
 contiguous env groups of one batch, hidden-128 ActorNetworks in ONE launch (`mm_policy_bank_act`, include/mm_policy_bank.h,
-on the stacked copies a `PolicyBank` keeps).
+on the stacked copies a `PolicyBank` keeps), hidden-128 state-split ActorCriticNetworks likewise (`mm_policy_gi_bank_act`,
+include/mm_policy_gi_bank.h, on a `SharedPolicyBank`; the bootstrap value comes from the same launch).
 """
 import torch
 from torch import nn
@@ -170,6 +171,45 @@ class PolicyBank(object):
             torch.stack([self._params(a)[j].detach().to(t.dtype) for a in self.actors], out=t)
 
 
+class SharedPolicyBank(object):
+    """K state-split hidden-128 ActorCriticNetworks of one shape as twelve stacked float32 tensors in MMGiParams order, the
+    operand of mm_policy_gi_bank_act (include/mm_policy_gi_bank.h): W11 [K, 32, 5], b11 [K, 32], W12 [K, 64, 10], b12 [K, 64],
+    W13, b13 likewise, W2 [K, 128, 160], b2 [K, 128], Wa [K, n_a, 128], ba [K, n_a], Wc [K, 1, 128], bc [K, 1], on the members'
+    device.  A COPY of the members' parameters, as PolicyBank: refresh() brings it up to date in place."""
+
+    NAMES = abi.GI_PARAMS
+
+    def __init__(self, members):
+        self.members = list(members)
+        if not self.members:
+            raise ValueError("a shared policy bank needs at least one member")
+        if len(self.members) > abi.BANK_MAX_GROUPS:
+            raise ValueError("a shared policy bank has at most %d members, got %d" % (abi.BANK_MAX_GROUPS, len(self.members)))
+        if not all(type(m) is ActorCriticNetwork and m.state_split and m.fc2.weight.shape[0] == 128 for m in self.members):
+            raise ValueError("the members of a shared policy bank must be state_split ActorCriticNetworks of hidden 128")
+        shapes = [tuple(tuple(p.shape) for p in self._params(m)) for m in self.members]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("the members of a shared policy bank must have one shape, got %s" % sorted(set(shapes)))
+        first = self._params(self.members[0])
+        self.K, self.hidden, self.n_a = len(self.members), first[6].shape[0], first[8].shape[0]
+        dev = first[0].device
+        self.tensors = [torch.empty((self.K,) + tuple(p.shape), dtype=torch.float32, device=dev) for p in first]
+        for name, t in zip(self.NAMES, self.tensors):
+            setattr(self, name, t)
+        self.params = abi.MMGiParams(*[t.data_ptr() for t in self.tensors])
+        self.refresh()
+
+    @staticmethod
+    def _params(m):
+        return tuple(p for l in (m.fc11, m.fc12, m.fc13, m.fc2, m.actor_linear, m.critic_linear) for p in (l.weight, l.bias))
+
+    @torch.no_grad()
+    def refresh(self):
+        """Copies every member's current parameters into the stack, in place: one launch per stacked tensor."""
+        for j, t in enumerate(self.tensors):
+            torch.stack([self._params(m)[j].detach().to(t.dtype) for m in self.members], out=t)
+
+
 class DeviceRollout(object):
     """MAPPO.interact for a whole env batch; see the module docstring.
 
@@ -177,15 +217,17 @@ class DeviceRollout(object):
     contiguous blocks of envs, in env order, that each member drives (they sum to env.E; zeros are allowed) -- the layout of a
     group-major env_params grid, or of K independent training runs stepped as one batch.  act() is then ONE
     mm_policy_bank_act launch when every member is an ActorNetwork of hidden 128 in float32 on the device, `generator` is
-    None, `fused_policy` is on and the library has the entry; otherwise each member's forward writes its slice of one
-    log-probability buffer and ONE mm_sample_actions draws for the whole batch (given the same rows, the same draws).
+    None, `fused_policy` is on and the library has the entry; with ActorCriticNetwork members (state_split, hidden 128) under
+    the same conditions it is ONE mm_policy_gi_bank_act launch on `shared_bank`, and the bootstrap's draw + value one more;
+    otherwise each member's forward writes its slice of one log-probability buffer and ONE mm_sample_actions draws for the whole
+    batch (given the same rows, the same draws).
     `group_index` ([E], for group_ext_info) and group_slice(k) (of the E axis: batch["states"][:, roll.group_slice(k)]) say
     which env belongs to whom."""
 
     def __init__(self, env, actor, critic=None, roll_out_n_steps=100, reward_gamma=0.99, reward_scale=20.0,
                  reward_type="regionalR", generator=None, use_graph=False, sample_seed=0, fused_policy=True, group_envs=None):
         assert reward_type in ("regionalR", "global_R")  # marl/mappo.py:39
-        self.bank_mode, self.bank = isinstance(actor, (list, tuple)), None
+        self.bank_mode, self.bank, self.shared_bank = isinstance(actor, (list, tuple)), None, None
         if self.bank_mode:
             actor, critic = self._init_bank(env, list(actor), critic, group_envs)
         elif group_envs is not None:
@@ -207,9 +249,17 @@ class DeviceRollout(object):
         # fused actor + sampling launch for the reference's ActorNetwork (hidden 128 or 512), and for its state-split
         # ActorCriticNetwork (hidden 128) on the device; anything else goes through the module's own forward
         f32 = all(next(a.parameters()).dtype == torch.float32 for a in (actor if self.bank_mode else [actor]))
-        if self.bank_mode:
-            # mm_policy_bank_act is a HIP-library entry at hidden 128; hidden 512, shared members and the CPU oracle take
-            # the members' own forwards
+        if self.bank_mode and self.shared:
+            # mm_policy_gi_bank_act is a HIP-library entry for state-split hidden-128 members; anything else and the CPU oracle
+            # take the members' own forwards (self.bank stays None: it is the ActorNetwork stack)
+            self.fused_policy = bool(fused_policy) and generator is None and f32 and self.obs.device.type == "cuda" \
+                and env.clib.has_policy_gi_bank and len(actor) <= abi.BANK_MAX_GROUPS \
+                and all(type(a) is ActorCriticNetwork and a.state_split and a.fc2.weight.shape[0] == 128
+                        and a.actor_linear.weight.shape[0] == self.n_a and a.fc2.weight.device == self.obs.device for a in actor)
+            if self.fused_policy:
+                self.shared_bank = SharedPolicyBank(actor)
+        elif self.bank_mode:
+            # mm_policy_bank_act is a HIP-library entry at hidden 128; hidden 512 and the CPU oracle take the members' own forwards
             b = self.bank
             self.fused_policy = bool(fused_policy) and b is not None and f32 and b.hidden == 128 and b.W1.device == self.obs.device \
                 and self.obs.device.type == "cuda" and env.clib.has_policy_bank
@@ -307,6 +357,16 @@ class DeviceRollout(object):
                                              self._sample_counter.data_ptr() if actions is not None else None, opt(actions),
                                              None, opt(value), self.env._stream()))
 
+    def _policy_gi_bank(self, obs, actions, value):
+        """One mm_policy_gi_bank_act launch on the env's stream (include/mm_policy_gi_bank.h), on the stack
+        shared_bank.refresh() keeps.  actions: int32 [E*N]; value: float32 [E*N] or None."""
+        b, clib = self.shared_bank, self.env.clib
+        E, N, S = obs.shape
+        clib.check(clib.lib.mm_policy_gi_bank_act(obs.contiguous().data_ptr(), E * N, S, abi.C.byref(b.params), b.K,
+                                                  self._group_start, b.hidden, self.n_a, self.sample_seed,
+                                                  self._sample_counter.data_ptr(), actions.data_ptr(),
+                                                  None, None if value is None else value.data_ptr(), self.env._stream()))
+
     def _bank_logp(self, obs):
         """Bank mode without the fused launch: each member's forward on its slice, into one [E*N, n_a] buffer."""
         E, N, S = obs.shape
@@ -318,7 +378,12 @@ class DeviceRollout(object):
 
     def _act(self, obs, dst):
         E, N, S = obs.shape
-        if self.bank_mode and self.generator is None and self.fused_policy and obs.dtype == torch.float32:
+        if self.shared_bank is not None and self.generator is None and self.fused_policy and obs.dtype == torch.float32:
+            # every group's shared actor-critic forward + sampling in ONE launch (mm_policy_gi_bank_act)
+            actions = dst if dst is not None else torch.empty(E * N, dtype=torch.int32, device=obs.device)
+            self._policy_gi_bank(obs, actions, None)
+            return actions.view(E, N)
+        if self.bank is not None and self.generator is None and self.fused_policy and obs.dtype == torch.float32:
             # every group's actor forward + sampling in ONE launch (mm_policy_bank_act on the stack bank.refresh() keeps)
             b, clib = self.bank, self.env.clib
             actions = dst if dst is not None else torch.empty(E * N, dtype=torch.int32, device=obs.device)
@@ -369,8 +434,9 @@ class DeviceRollout(object):
         Returns states [T,E,N,S], actions [T,E,N], discounted returns [T,E,N], dones [T,E] and the
         per-step info means the reference logs (average speed, min headway).  With `use_graph` the
         returned tensors are the graph's static buffers: consume them before the next call."""
-        if self.bank is not None:
-            self.bank.refresh()  # outside the capture: a replayed graph reads the stack this call has just updated
+        for b in (self.bank, self.shared_bank):
+            if b is not None:
+                b.refresh()  # outside the capture: a replayed graph reads the stack this call has just updated
         if not self.use_graph:
             return self._interact()
         if self._graph is None:
@@ -424,8 +490,15 @@ class DeviceRollout(object):
         self.obs = obs.clone()
         # bootstrap value for envs still mid-episode (marl/mappo.py:147-150); 0 where the last step ended one
         final_value = torch.zeros(E, N, dtype=torch.float64, device=dev)
-        if self.bank_mode:
-            # each group's own critic on its slice (the value path stays torch); the final actions are drawn as in act()
+        if self.shared_bank is not None and self.generator is None and self.fused_policy and obs.dtype == torch.float32:
+            # every group's draw + value in one launch, as the single shared network's branch below
+            fa = torch.empty(E * N, dtype=torch.int32, device=dev)
+            val = torch.empty(E * N, dtype=torch.float32, device=dev)
+            self._policy_gi_bank(obs, fa, val)
+            final_value = torch.where(dones[-1].bool().unsqueeze(-1), final_value, val.view(E, N).double())
+        elif self.bank_mode:
+            # each group's own critic on its slice (torch: ActorNetwork members' critics, and shared members without the fused
+            # launch); the final actions are drawn as in act()
             if self.shared or self.critic is not None:
                 fa = self.act(obs)
                 flat = obs.reshape(E * N, S).float()
@@ -478,8 +551,9 @@ class DeviceRollout(object):
         if missing:  # MAPPO.evaluation reads info["vehicle_speed"/"vehicle_position"] and env.is_crashed() (:300-330)
             raise ValueError("evaluate() needs the step outputs %s: this env was built with skip_outputs" % ", ".join(missing))
         was_auto = env.auto_reset
-        if self.bank is not None:
-            self.bank.refresh()
+        for b in (self.bank, self.shared_bank):
+            if b is not None:
+                b.refresh()
         # The reference evaluates on a SEPARATE env (env_eval, run_mappo.py:146-171,300-306) and its training env keeps
         # its own seed sequence and in-progress episode.  Here the batch is borrowed: snapshot everything an evaluation
         # touches (state planes, episode counters, per-env RNG seeds, carried observation) and put it back afterwards,
