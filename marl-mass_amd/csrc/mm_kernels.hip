@@ -33,6 +33,7 @@
 #include "mm_device.h"
 #include "mm_div.h"  // tested division forms behind MM_GEOM_DIV; no step kernel uses them
 #include "mm_handle.h"
+#include "mm_relation.h"  // adj_pair / adj_lane / adj_row / adj_col and the relation word (host-compilable: the table's test)
 #define MM_COUNTS_FN __host__ __device__ inline
 #include "../../include/mm_counts.h"
 #include "../../include/mm_policy_wide.h"  // mm_policy_act forwards hidden = 512 to it
@@ -499,6 +500,19 @@ MM_DEV int pose_code(int lane, int nl, int off) { return lane | nl << 3 | off <<
 constexpr bool kPoseHBits = MM_POSE_HBITS != 0;
 constexpr int kPoseHPos = 0x200, kPoseHNeg = 0x400;
 MM_DEV int pose_hbits(double h) { return ((h > 0.037) ? kPoseHPos : 0) | ((h < -0.037) ? kPoseHNeg : 0); }
+// ... and the lane-pair relation (kPoseRelW, in the kernels that step_kernel's kRelW names): what relate() derives from the lanes of the reader
+// and of the partner's pose -- "adjacent either way" and which front corner counts -- depends on the reader's and the owner's
+// (lane, next lane) pair alone, and every value of the owner's side is fixed when it forms its pose code.  So the owner puts, for
+// each of the eight pairs a reader can hold, those two bits into bits 11 .. 26 of the code (pose_relw, mm_relation.h: a table
+// generated from adj_row / adj_col at compile time), once per pose, and relate_word extracts the two at its own pair's position
+// instead of building rowEN / colE and shifting them for every partner and pass.  The bits are a pure function of bits 0 .. 5 of
+// the same word, so they are correct wherever the word goes.  (-DMM_RELATION_WORD=0: A-B timing)
+#ifndef MM_RELATION_WORD
+#define MM_RELATION_WORD 1
+#endif
+constexpr bool kPoseRelW = kPoseHBits && MM_RELATION_WORD != 0;
+// the reader's side: the position of its own pair's two bits in a partner's code (it changes only when the reader commits a pose)
+MM_DEV int pose_rel_shift(int pk) { return kRelShift + 2 * (pair_index(pk & 7, (pk >> 3) & 7) & 7); }
 
 // Predicted post-state of Vehicle.step for a given steering (kinematics.py:122-141,
 // safe_controller.py:151-172): everything that does not depend on the acceleration.
@@ -513,7 +527,7 @@ struct Cand {
 // sin(beta), cos(psi' + beta), cos(psi') and the three corner angles -- become ONE sincos of the steering angle and ONE of
 // the new heading plus angle sums; beta itself is never formed (include/mm_math.h, "angle-sum forms").
 // GENERAL: the instantiation can meet a steering angle that did not come out of steering_control (kernels with HDVs / steer_vel)
-template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false, bool HB = false>
+template <int KIND, bool SHIELDED, bool CORNERS = SHIELDED, bool GENERAL = true, bool SINE = false, int HB = 0>
 MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double ch, double dt, bool sv = false, double *sine_out = nullptr) {
   Cand c;
   // "steer_vel" (safe_controller.py:124-150): the slip angle comes from the steering-angle STATE and the
@@ -538,26 +552,17 @@ MM_DEV Cand predict(const Veh &v, double steer, double st_t, double sh, double c
   c.gvx = (KIND == MM_ENV_V1) ? mmm_cos_sum(c.spsi, c.cpsi, sb, cb) : 0.0;
   c.lane = closest_lane<SINE>(c.x, c.y, c.h, sine_out);  // on_state_update kinematics.py:154-159 (sine_out: see closest_lane)
   c.pk = c.lane;
-  if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags<SINE>(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
-  if constexpr (HB) c.pk |= pose_hbits(c.h);
+  if constexpr (HB == 2) {  // heading bits and the relation word
+    const int nl = next_lane(c.lane, c.x, c.y);
+    c.pk = pose_code(c.lane, nl, CORNERS ? corner_flags<SINE>(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0) | pose_hbits(c.h) | pose_relw(c.lane, nl);
+  } else {
+    if (SHIELDED) c.pk = pose_code(c.lane, next_lane(c.lane, c.x, c.y), CORNERS ? corner_flags<SINE>(c.x, c.y, c.spsi, c.cpsi, c.lane) : 0);
+    if constexpr (HB != 0) c.pk |= pose_hbits(c.h);
+  }
   return c;
 }
 
-// decentral_layer.py:23-39 is_adj_lane(vehicle, lane2) given vehicle.lane and its next_lane.  Only road
-// (b,c) has two lanes, so "same road and ids differ by one" means the pair {bc0, bc1}: bc0 sees bc1
-// at -1 (to its right), bc1 sees bc0 at +1.
-MM_DEV int adj_pair(int l1, int l2) {
-  return (l1 == MM_LANE_BC0 && l2 == MM_LANE_BC1) ? -1 : ((l1 == MM_LANE_BC1 && l2 == MM_LANE_BC0) ? 1 : 0);
-}
-MM_DEV int adj_lane(int l1, int nl1, int l2) {
-  const int f = adj_pair(l1, l2);
-  return f != 0 ? f : adj_pair(nl1, l2);
-}
-// The same relation as 2-bit codes (0: none, 1: +1, 3: -1) in packed 6-entry tables, for the classification
-// loops (one table build per ego instead of four compare chains per pair):
-//   adj_row(l1) >> 2*l2 & 3 = code of adj_pair(l1, l2);   adj_col(l2) >> 2*l1 & 3 = code of adj_pair(l1, l2)
-MM_DEV unsigned adj_row(int l1) { return l1 == MM_LANE_BC0 ? (3u << (2 * MM_LANE_BC1)) : (l1 == MM_LANE_BC1 ? (1u << (2 * MM_LANE_BC0)) : 0u); }
-MM_DEV unsigned adj_col(int l2) { return l2 == MM_LANE_BC1 ? (3u << (2 * MM_LANE_BC0)) : (l2 == MM_LANE_BC0 ? (1u << (2 * MM_LANE_BC1)) : 0u); }
+// (decentral_layer.py:23-39 is_adj_lane -- adj_pair, adj_lane and the packed tables adj_row / adj_col -- lives in mm_relation.h)
 
 struct QpTrace {
   double rows, a, h0, h1, h2, h3, d, margin;
@@ -1123,6 +1128,37 @@ struct Rel {
   int cls;
   bool cflag;
 };
+// The HB form with the lane-pair relation taken from the partner's code too (kPoseRelW): bits 11 .. 26 of `opk` hold, for every
+// pair a reader can have, "adjacent either way" and "the left front corner counts"; the reader's two sit at `esh`
+// (pose_rel_shift of the reader's own code).  rowE / rowN / rowEN / colE, v_a and a_v are not formed; everything else is
+// relate()'s expression for expression, statement order and the folded `twin` term included: a condensed body gave the same
+// results with one spilled VGPR (8 B of scratch) in the headline kernel, which sits at 256 VGPRs.
+MM_DEV Rel relate_word(double ex, double ey, int epk, bool other, double ox, double oy, int opk, int esh) {
+  const bool o_hdv = false;
+  const int elane = epk & 7, enl = (epk >> 3) & 7, olane = opk & 7;
+  Rel r;
+  const double dx = ox - ex, dy = oy - ey;
+  const bool close = other & ((dx * dx + dy * dy) < kT180);  // road.py:259-262 (norm < 180, sqrt-free)
+  const double esx = lane_sx(elane);
+  const double ld = (ox - esx) - (ex - esx);  // kinematics.py:161-173
+  r.key = close ? fabs(ld) : INFINITY;
+  bool adj_any, csel;  // (v_a | a_v) != 0; v_a == -1 or a_v == 1
+  {
+    const unsigned rel = (unsigned)opk >> esh;
+    adj_any = (rel & 1u) != 0; csel = (rel & 2u) != 0;
+  }
+  bool head;
+  head = (opk & ((dy < 0) ? kPoseHPos : kPoseHNeg)) != 0;
+  const bool appr = (!(ld < 0)) & (fabs(dy) <= 3.5) & head;  // :46-57
+  const bool adj = (!appr) & adj_any;
+  const bool same = (elane == olane) | (olane == enl);  // is_same_lane :15-20
+  const bool twin = o_hdv & (!adj) & (elane == MM_LANE_AB0) & (olane == MM_LANE_KB0) & (ld >= 0);
+  const bool lead = (!adj) & (!twin) & (same | appr) & (ld > 0);
+  const int cls = adj ? ((ld < 0) ? 3 : 2) : (twin ? 4 : (lead ? 1 : 0));
+  r.cls = close ? cls : 0;
+  r.cflag = ((opk >> (csel ? 6 : 7)) & 1) != 0;
+  return r;
+}
 // HB: the partner's two heading predicates come in bits 9 / 10 of `opk` (pose_hbits) and `oh` is not read
 template <bool HB = false>
 MM_DEV Rel relate(double ex, double ey, int epk, bool other, double ox, double oy, double oh, int opk, bool o_hdv = false) {
@@ -1772,6 +1808,12 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
 #define MM_PARTNER_LIVE 1
 #endif
   constexpr bool kPLive = kPBits && MM_PARTNER_LIVE != 0;
+  // kRelW: the pose codes of this kernel carry their owner's relation word as well (pose_relw) and the classification pass reads it
+  // (relate_word).  In the 8-lane kPBits kernels: an owner pays about 16 instructions per pose it forms, a reader saves about 9 per
+  // partner and pass, which pays with seven partners and not with three or one; the per-env 8-lane MASS kernel went from 0 to
+  // 12 B of scratch with it.  (-DMM_RELATION_WORD=0: the parent's form)
+  constexpr bool kRelW = kPBits && G == 8 && kPoseRelW;
+  constexpr int kOwnerBits = kHBits ? (kRelW ? 2 : 1) : 0;  // predict<..., HB>
   double car_sn = __builtin_nan("");
   (void)car_sn;
   static_assert(kPow2<G> || MM_STEP_BLOCK == 64, "rotation layouts: one wave per workgroup");
@@ -1845,12 +1887,20 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     const bool hit = car_kx == __double_as_longlong(v.x) && car_ky == __double_as_longlong(v.y) && car_kh == __double_as_longlong(v.h) &&
                      (car_code >> 8) == ((kPoseWritten >> 8) | (MASS ? 1 : 0)) && (car_code & 7) == v.lane;
     carried = !__any(v.present && !hit);
-    if (carried && v.present) { spsi = car_s; cpsi = car_c; pk_self = (car_code & 0xFF) | (kHBits ? pose_hbits(v.h) : 0); }
+    // (the planes hold bits 0 .. 7 of the code: the owner's bits are formed again, from the heading and from the carried lanes)
+    if (carried && v.present) { spsi = car_s; cpsi = car_c; pk_self = (car_code & 0xFF) | (kHBits ? pose_hbits(v.h) : 0) | (kRelW ? pose_relw(car_code & 7, (car_code >> 3) & 7) : 0); }
   }
   if (!carried) {
     if (v.present) mmm_sincos(v.h, &spsi, &cpsi);
-    if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, spsi, cpsi, v.lane) : 0);
-    if constexpr (kHBits) { if (v.present) pk_self |= pose_hbits(v.h); }
+    if constexpr (kRelW) {
+      if (v.present) {
+        const int nl = next_lane(v.lane, v.x, v.y);
+        pk_self = pose_code(v.lane, nl, MASS ? corner_flags<kSine>(v.x, v.y, spsi, cpsi, v.lane) : 0) | pose_hbits(v.h) | pose_relw(v.lane, nl);
+      }
+    } else {
+      if (SHIELDED && v.present) pk_self = pose_code(v.lane, next_lane(v.lane, v.x, v.y), MASS ? corner_flags<kSine>(v.x, v.y, spsi, cpsi, v.lane) : 0);
+      if constexpr (kHBits) { if (v.present) pk_self |= pose_hbits(v.h); }
+    }
   }
 
   // Register relief: lane-private values that are written once and read rarely live in LDS ("cold"
@@ -2071,7 +2121,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
     memset(&cA, 0, sizeof cA);
     const bool shield_on = SHIELDED && live && !hdv && v.hist_len >= 2;  // gate safe_controller.py:232-239
     if constexpr (kSineCarry) car_sn = __builtin_nan("");
-    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine, kHBits>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv, kSineCarry ? &car_sn : nullptr);
+    if (live && head) cA = predict<KIND, SHIELDED, MASS, MIXED, kSine, kOwnerBits>(v, v.act_steer, st_t, spsi, cpsi, dt, sv && !hdv, kSineCarry ? &car_sn : nullptr);
     auto park = [&](auto base_c, const Cand &cc, double steer) {  // a candidate's LDS image (shielded kernels only)
       constexpr int base = decltype(base_c)::value;
       if constexpr (SHIELDED) {
@@ -2111,7 +2161,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
             steer_o = clipd(steer_o, -kPi / 3, kPi / 3);
             if (v.crashed) { steer_o = 0; t_o = 0; }
           }
-          park_at(mk_A ? (int)C_A : (int)C_B, predict<KIND, true, MASS, MIXED, kSine, kHBits>(v, steer_o, t_o, spsi, cpsi, dt, false), steer_o);
+          park_at(mk_A ? (int)C_A : (int)C_B, predict<KIND, true, MASS, MIXED, kSine, kOwnerBits>(v, steer_o, t_o, spsi, cpsi, dt, false), steer_o);
           haveA = true; haveB = haveB || !mk_A;
         }
       }
@@ -2122,7 +2172,7 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
           double tB;
           double steerB = steering_control<kSine>(v.x, v.y, v.h, v.v, v.lane, tB);
           if (sv) steerB = steer_vel_command(steerB, v.sang);
-          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED, kSine, kHBits>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
+          park(std::integral_constant<int, C_B>{}, predict<KIND, true, MASS, MIXED, kSine, kOwnerBits>(v, steerB, tB, spsi, CPSI(), dt, sv), steerB);
           haveB = true;
         }
       }
@@ -2248,6 +2298,10 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
         constexpr bool count5 = G > 4;
         if constexpr (kPBits) { s_cold[C_PRE + 0][tid] = v.x; s_cold[C_PRE + 1][tid] = v.y; cold_i(C_PREPK, tid) = pk_self; }
         else if constexpr (kMailbox) { s_cold[C_PRE + 0][tid] = v.x; s_cold[C_PRE + 1][tid] = v.y; s_cold[C_PRE + 2][tid] = v.h; cold_i(C_PRE + 3, tid) = pk_self; }
+        // kRelW: where my own pair's two bits sit in a partner's relation word, once per sub-step (my pose code changes at the
+        // commit).  (The partner loop names it in a discarded branch elsewhere, so the other kernels' closure does not hold it.)
+        [[maybe_unused]] int e_sh = 0;
+        if constexpr (kRelW) e_sh = pose_rel_shift(pk_self);
         // (interior-point mode) the QP this lane solved in the previous veto pass of this sub-step: rows that did not change
         // need no second solve.  a, h1, h2 depend on the lane's own pre-step state only, so (rows, h0, h3) identify the QP.
         double qc_h0 = 0.0, qc_h3 = 0.0, qc_d = 0.0;
@@ -2323,7 +2377,9 @@ __global__ __launch_bounds__(MM_STEP_BLOCK, (SPLIT ? MM_SPLIT_WAVES : step_min_w
             o_first = !i_first && p_rank < 99;
             other = ((opk >> 8) & 1) != 0;
             }
-            const Rel r = relate<kHBits && kMailbox>(v.x, v.y, pk_self, other, ox, oy, oh, opk);
+            Rel r;
+            if constexpr (kRelW) r = relate_word(v.x, v.y, pk_self, other, ox, oy, opk, e_sh);
+            else r = relate<kHBits && kMailbox>(v.x, v.y, pk_self, other, ox, oy, oh, opk);
             if constexpr (count5) s_cold[kColdB + m - 1][tid] = r.key;
             // running "first in sorted order" per class: smaller key, ties by creation index (selects, no branches)
             // (the slot's flags ride in the index word -- bit 4: that partner steps before me, bit 5: its corner
