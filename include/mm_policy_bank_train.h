@@ -24,8 +24,8 @@
  * rows = T, row_len = E * N, obs_stride = S, col_start = the env prefix times N.
  *
  * Exported by libmm_hip.so only (marl-mass_amd/csrc/mm_policy_bank_train.hip); no oracle twin, not part of include/mm_abi.h's
- * symbol list or version.  Out of scope: hidden 512, shared actor-critic members, the chunked and rank-sharded forms, per-member
- * hyperparameters.
+ * symbol list or version.  Shared actor-critic members are include/mm_policy_gi_bank_train.h's.  Out of scope: hidden 512, the
+ * chunked and rank-sharded forms, per-member hyperparameters.
  */
 #ifndef MM_POLICY_BANK_TRAIN_H
 #define MM_POLICY_BANK_TRAIN_H

@@ -93,6 +93,8 @@ PT_FORM = {"reference": 0, "per_sample": 1}  # MM_PT_FORM_* (include/mm_policy_b
 # the scratch figures of mm_policy_bank_train_scratch_bytes (MM_PBT_*_BYTES): header, per member, per padded sample, per tile,
 # per partial block
 PBT_HEADER_BYTES, PBT_MEMBER_BYTES, PBT_SAMPLE_BYTES, PBT_TILE_BYTES, PBT_PARTIAL_BYTES = 1024, 131072, 2240, 32, 107584
+# the same figures of mm_policy_gi_bank_train_scratch_bytes (MM_GBT_*_BYTES, include/mm_policy_gi_bank_train.h)
+GBT_HEADER_BYTES, GBT_MEMBER_BYTES, GBT_SAMPLE_BYTES, GBT_TILE_BYTES, GBT_PARTIAL_BYTES = 1024, 81920, 2496, 40, 111808
 
 
 OPT_RMSPROP, OPT_ADAM, OPT_BLEND = 0, 1, 2  # MM_OPT_* (include/mm_opt_step.h)
@@ -450,6 +452,22 @@ class CLib(object):
             lib.mm_policy_bank_train.restype = i32
             lib.mm_opt_step_bank.argtypes = [C.POINTER(MMOptGroup), i32, i32, u64, vp]
             lib.mm_opt_step_bank.restype = i32
+        # the training half of the bank of shared actor-critics: K shared networks on the K column groups of one batch
+        # (include/mm_policy_gi_bank_train.h); its optimiser tail is mm_opt_step_bank.  Also libmm_hip.so only
+        self.has_policy_gi_bank_train = self.has_policy_gi_train and self.has_policy_gi_bank and all(
+            hasattr(lib, s) for s in ("mm_policy_gi_bank_eval", "mm_policy_gi_bank_train", "mm_policy_gi_bank_train_scratch_bytes",
+                                      "mm_opt_step_bank"))
+        if self.has_policy_gi_bank_train:
+            f32, pg, pi64 = C.c_float, C.POINTER(MMGiParams), C.POINTER(i64)
+            lib.mm_policy_gi_bank_eval.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, pg, i32, pi64, i32, i32, vp, vp, vp]
+            lib.mm_policy_gi_bank_eval.restype = i32
+            lib.mm_policy_gi_bank_train_scratch_bytes.argtypes = [i64, i64, i32, pi64, C.POINTER(u64)]
+            lib.mm_policy_gi_bank_train_scratch_bytes.restype = i32
+            lib.mm_policy_gi_bank_train.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, i64, vp, vp, pg, i32, pi64, i32, i32, f32, i32,
+                                                    i32, vp, pg, vp, vp, vp, vp, vp, vp, u64, vp]
+            lib.mm_policy_gi_bank_train.restype = i32
+            lib.mm_opt_step_bank.argtypes = [C.POINTER(MMOptGroup), i32, i32, u64, vp]
+            lib.mm_opt_step_bank.restype = i32
         # per-env cbf_eta / cbf_tau / HEADWAY_TIME planes (include/mm_env_params.h), also libmm_hip.so only
         self.has_env_params = hasattr(lib, "mm_set_env_params")
         if self.has_env_params:
@@ -640,9 +658,23 @@ class CLib(object):
         self.check(self.lib.mm_policy_bank_train_scratch_bytes(rows, row_len, len(col_start) - 1, cs, C.byref(b)))
         return b.value
 
+    def require_policy_gi_bank_train(self):
+        if not self.has_policy_gi_bank_train:
+            raise NotImplementedError("%s does not export mm_policy_gi_bank_train: training the bank's shared actor-critic members "
+                                      "in one launch set needs the HIP library" % os.path.basename(self.path))
+
+    def policy_gi_bank_train_scratch_bytes(self, rows, row_len, col_start):
+        """Bytes of scratch mm_policy_gi_bank_train needs (include/mm_policy_gi_bank_train.h); col_start: the K + 1 column prefix."""
+        self.require_policy_gi_bank_train()
+        b = C.c_uint64()
+        cs = (C.c_int64 * len(col_start))(*col_start)
+        self.check(self.lib.mm_policy_gi_bank_train_scratch_bytes(rows, row_len, len(col_start) - 1, cs, C.byref(b)))
+        return b.value
+
     def opt_step_bank(self, groups, K, soft_mask, stream):
         """mm_opt_step_bank on a sequence of prototype MMOptGroup (include/mm_opt_step.h)."""
-        self.require_policy_bank_train()
+        if not self.has_policy_gi_bank_train:
+            self.require_policy_bank_train()
         arr = (MMOptGroup * len(groups))(*groups)
         self.check(self.lib.mm_opt_step_bank(arr, len(groups), K, soft_mask, stream))
 

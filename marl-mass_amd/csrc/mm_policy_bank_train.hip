@@ -18,6 +18,7 @@
 //   kernel C  grid (elements, K): member k folds its own partial blocks in workgroup order, the last workgroup its loss tree.
 // The tables ride in the by-value argument blocks (uniform lookups: scalar loads from the kernel-argument segment).
 #include "mm_policy_sample.h"  // kernel A; mm_policy_mfma.h
+#include "mm_policy_bank_tables.h"  // Tables, group_of, sample_of, the statistics, plan: shared with mm_policy_gi_bank_train.hip
 #include "../../include/mm_policy_bank_train.h"
 
 namespace mm {
@@ -27,34 +28,11 @@ using namespace mfma;
 constexpr int kWavesA = MM_BANK_WAVES;  // kernel A's 8 waves, as policy_bank_kernel's: mm_policy_bank_grid splits the workgroups
 static_assert(kThreadsA == 64 * kWavesA, "kernel A's workgroup");
 constexpr int kThreadsB = 320;
-constexpr int kG = MM_BANK_MAX_GROUPS;
 constexpr long long kFrag = 4 * 4 * 4 * 64 * 4;  // W2^T fragments of one network, in floats
 typedef PartialBlock<4> Part;
 static_assert(MM_BANK_TILE == 32, "one wave per 32 samples: the MFMA tile");
 static_assert(2 * kFrag * 4 == MM_PBT_MEMBER_BYTES && Part::kSize * 4 == MM_PBT_PARTIAL_BYTES, "the header's scratch figures");
 static_assert((4 * kHidden + kDh + kXs) * 4 == MM_PBT_SAMPLE_BYTES && MM_PBT_HEADER_BYTES == 4 * 4 * kG, "the header's scratch figures");
-
-// The group tables of a call; entries past K repeat the last one.
-struct Tables {
-  int col_start[kG + 1];    // member k owns columns [col_start[k], col_start[k + 1]) of every row
-  int tile_start[kG + 1];   // prefix of the groups' 32-sample tiles: scratch rows of group k start at 32 tile_start[k]
-  int slice_start[kG + 1];  // prefix of the groups' kernel-B slices = partial blocks
-  int block_start[kG + 1];  // prefix of kernel A's workgroups
-  int rows, row_len;
-};
-
-MM_DEV int group_of(const int (&start)[kG + 1], int b) {
-  int g = 0;
-#pragma unroll
-  for (int k = 1; k < kG; k++) g += start[k] <= b ? 1 : 0;
-  return g;
-}
-
-// member-local sample i of a group of width w starting at column c0 -> the batch's sample index
-MM_DEV unsigned sample_of(unsigned i, unsigned w, unsigned c0, unsigned row_len) {
-  const unsigned r = i / w;
-  return r * row_len + c0 + (i - r * w);
-}
 
 // ---- frag: W2[:, :128]^T fragments of member blockIdx.y's given networks
 __global__ __launch_bounds__(256) void bank_frag_kernel(const float *__restrict__ W2a, const float *__restrict__ W2c, int k2c,
@@ -66,62 +44,14 @@ __global__ __launch_bounds__(256) void bank_frag_kernel(const float *__restrict_
   if (W2) frag[(long long)k * 2 * 4096 + t] = w2t_fragment(W2 + (long long)k * kHidden * k2, k2, t & 4095);
 }
 
-struct StatArgs {
-  const uint8_t *valid;
-  const float *advantages, *target_value, *returns;
-  long long ret_stride;
-  int sums;  // reference form with actors: S+ / S- are wanted
-  double *stats;
-};
-
-// ---- stats: one wave per tile, lanes 0..31 one sample each
+// ---- stats: one wave per tile, lanes 0..31 one sample each; stats_fold: one workgroup per group (mm_policy_bank_tables.h)
 __global__ __launch_bounds__(256) void bank_stats_kernel(const StatArgs p, const Tables tb, int total_tiles) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int t = blockIdx.x * 4 + wave; t < total_tiles; t += gridDim.x * 4) {
-    const int g = group_of(tb.tile_start, t);
-    const unsigned c0 = tb.col_start[g], w = tb.col_start[g + 1] - c0;
-    const long long ng = (long long)w * tb.rows;
-    const long long local = (long long)(t - tb.tile_start[g]) * 32 + lane;
-    double cnt = 0.0, sp = 0.0, sn = 0.0;
-    if (lane < 32 && local < ng) {
-      const unsigned gj = sample_of((unsigned)local, w, c0, (unsigned)tb.row_len);
-      if (!p.valid || p.valid[gj] != 0) {
-        cnt = 1.0;
-        if (p.sums) {
-          const float adv = p.advantages ? p.advantages[gj] : p.returns[gj * p.ret_stride] - p.target_value[gj];
-          if (adv >= 0.0f) sp = (double)adv;
-          else if (adv < 0.0f) sn = (double)adv;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) {
-      cnt += __shfl_xor(cnt, o, 64);
-      sp += __shfl_xor(sp, o, 64);
-      sn += __shfl_xor(sn, o, 64);
-    }
-    if (lane == 0) {
-      p.stats[3ll * t + 0] = cnt;
-      p.stats[3ll * t + 1] = sp;
-      p.stats[3ll * t + 2] = sn;
-    }
-  }
+  stats_tiles(p, tb, total_tiles);
 }
 
 __global__ __launch_bounds__(256) void bank_stats_fold_kernel(const double *__restrict__ stats, const Tables tb, int *__restrict__ count,
                                                               float *__restrict__ sums, float *__restrict__ sums_out) {
-  __shared__ double s[3][256];
-  const int k = blockIdx.x;
-  loss_tree<3>(stats + 3ll * tb.tile_start[k], tb.tile_start[k + 1] - tb.tile_start[k], s);
-  if (threadIdx.x == 0) {
-    count[k] = (int)s[0][0];
-    sums[2 * k] = (float)s[1][0];
-    sums[2 * k + 1] = (float)s[2][0];
-    if (sums_out) {
-      sums_out[2 * k] = (float)s[1][0];
-      sums_out[2 * k + 1] = (float)s[2][0];
-    }
-  }
+  stats_fold(stats, tb, count, sums, sums_out);
 }
 
 struct SampleArgs {
@@ -229,51 +159,6 @@ __global__ __launch_bounds__(256) void bank_fold_kernel(const float *__restrict_
 }
 
 // ---- host side
-struct Plan {
-  Tables tb;
-  long long total_tiles, total_slices, cap_slices;  // cap_slices: the partial blocks the scratch query reserves
-  long long n;
-};
-
-// checks rows / row_len / K / col_start and fills the tables; false: refused
-static bool plan(int64_t rows, int64_t row_len, int32_t K, const int64_t *col_start, bool with_grid, Plan &P) {
-  if (rows < 0 || row_len < 0 || !col_start || K < 1 || K > kG || col_start[0] != 0) return false;
-  for (int k = 0; k < K; k++)
-    if (col_start[k + 1] < col_start[k]) return false;
-  if (col_start[K] != row_len) return false;
-  if (row_len > 0 && rows > 0x7FFFFFFFll / row_len) return false;
-  P.n = rows * row_len;
-  int64_t size_start[kG + 1];
-  Tables &tb = P.tb;
-  tb.rows = (int)rows; tb.row_len = (int)row_len;
-  tb.tile_start[0] = tb.slice_start[0] = 0;
-  size_start[0] = 0;
-  P.cap_slices = 0;
-  for (int k = 0; k < K; k++) {
-    const long long nk = (col_start[k + 1] - col_start[k]) * rows, nt = (nk + 31) / 32;
-    const long long per = tiles_per_slice(nt);
-    const long long cap = (nt + 1) / 2 < kMaxSlices ? (nt + 1) / 2 : kMaxSlices;
-    tb.col_start[k] = (int)col_start[k];
-    tb.tile_start[k + 1] = tb.tile_start[k] + (int)nt;
-    tb.slice_start[k + 1] = tb.slice_start[k] + (int)((nt + per - 1) / per);
-    size_start[k + 1] = size_start[k] + nk;
-    P.cap_slices += cap;
-  }
-  for (int k = K; k <= kG; k++) {
-    tb.col_start[k] = (int)row_len;
-    tb.tile_start[k] = tb.tile_start[K];
-    tb.slice_start[k] = tb.slice_start[K];
-  }
-  P.total_tiles = tb.tile_start[K];
-  P.total_slices = tb.slice_start[K];
-  for (int k = 0; k <= kG; k++) tb.block_start[k] = 0;
-  if (with_grid && P.n > 0) {
-    if (mm_policy_bank_grid(K, size_start, tb.block_start) != MM_OK) return false;
-    for (int k = K + 1; k <= kG; k++) tb.block_start[k] = tb.block_start[K];
-  }
-  return true;
-}
-
 // the scratch, offsets in floats
 struct Scratch {
   long long count, sums, frag, h1, dz1, h2, dz2, dh, xs, lossp, stats, part, total;

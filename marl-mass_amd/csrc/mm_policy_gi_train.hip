@@ -1,7 +1,8 @@
 // mm_policy_gi_train.hip -- loss and parameter gradient of MAPPO_GI's shared actor-critic (include/mm_policy_gi_train.h).
 //
 // The forward is policy_gi_kernel's (mm_policy_gi.hip), in the layout and from the pieces of mm_policy_mfma.h; the split gather
-// of layer 1 is restated here.
+// of layer 1 is restated in kernel A, whose text is gi_sample_body of mm_policy_gi_sample.h, shared with the bank's training half
+// (mm_policy_gi_bank_train.hip).
 //
 //   prep      W2^T in MFMA A-fragment order into the scratch (80 KB), and B = the number of valid samples.
 //   kernel A  per sample: forward, heads, log-softmax, ratio, the loss terms, dlogit / dvalue (VALU tail);
@@ -20,14 +21,14 @@
 //   kernel C  every parameter's gradient = the partial blocks summed in workgroup order (fp64 running sum), written in
 //             torch layout; the loss partials folded by one workgroup in a fixed tree.
 #include "mm_policy_chunked.h"  // PassArgs and the launch helpers' declarations; mm_policy_mfma.h and the public header
+#include "mm_policy_gi_sample.h"  // kernel A
 
 namespace mm {
 namespace gi_train {
 
 using namespace mfma;
-constexpr int kCat = 160;
-constexpr int kL1Steps = 3 + 4 * 5;
-constexpr int kThreadsA = 512;  // 8 waves = 2 per SIMD, as policy_gi_kernel
+constexpr int kCat = kGiCat;
+constexpr int kThreadsA = kGiThreadsA;  // 8 waves = 2 per SIMD, as policy_gi_kernel
 constexpr int kThreadsB = 320;  // 5 waves
 
 constexpr long long kFrag = 5 * 4 * 4 * 64 * 4;  // W2^T fragments, in floats: [out tile 5][k chunk 4][group 4][lane 64] float4
@@ -43,7 +44,45 @@ __global__ __launch_bounds__(256) void gi_train_prep_kernel(const float *__restr
   count_valid(valid, n, t, count);
 }
 
-// ---- kernel A
+// ---- kernel A: gi_sample_body of mm_policy_gi_sample.h on the one network and the contiguous samples of the kernel's arguments
+struct FlatArgs {
+  const float *__restrict__ obs;
+  long long obs_stride, n;
+  const int32_t *__restrict__ actions;
+  long long act_stride;
+  const float *__restrict__ returns;
+  long long ret_stride;
+  const float *__restrict__ old_logp;
+  const uint8_t *__restrict__ valid;
+  MMGiParams w;
+  int n_a;
+  float clip_param;
+  int huber;
+  const float *__restrict__ adv_sums;
+  const int *__restrict__ count;
+  const float4 *__restrict__ frag;
+  float *s_h1;
+  float *__restrict__ s_dz1, *__restrict__ s_h2, *__restrict__ s_dz2, *__restrict__ s_dh, *__restrict__ s_xs;
+  double *__restrict__ lossp;
+  float *__restrict__ logp_out, *__restrict__ value_out, *__restrict__ ratio_out;
+};
+
+struct Flat {
+  const FlatArgs &p;
+  MM_DEV explicit Flat(const FlatArgs &a) : p(a) {}
+  MM_DEV MMGiParams net() const { return p.w; }
+  MM_DEV long long n() const { return p.n; }
+  MM_DEV int count() const { return *p.count; }
+  MM_DEV const float *adv_sums() const { return p.adv_sums; }
+  MM_DEV bool ref_form() const { return p.adv_sums != nullptr; }
+  MM_DEV const float4 *frag() const { return p.frag; }
+  MM_DEV double *lossp() const { return p.lossp; }
+  MM_DEV long long first_tile(int wave) const { return (long long)blockIdx.x * (kThreadsA / 64) + wave; }
+  MM_DEV long long tile_stride() const { return (long long)gridDim.x * (kThreadsA / 64); }
+  MM_DEV long long sample(long long i, bool) const { return i; }
+  MM_DEV long long row(long long i) const { return i; }
+};
+
 __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
     const float *__restrict__ obs, long long obs_stride, long long n, const int32_t *__restrict__ actions, long long act_stride,
     const float *__restrict__ returns, long long ret_stride, const float *__restrict__ old_logp, const uint8_t *__restrict__ valid,
@@ -51,210 +90,9 @@ __global__ __launch_bounds__(kThreadsA) void policy_gi_train_sample_kernel(
     const float4 *__restrict__ frag, float *s_h1, float *__restrict__ s_dz1, float *__restrict__ s_h2,
     float *__restrict__ s_dz2, float *__restrict__ s_dh, float *__restrict__ s_xs, double *__restrict__ lossp,
     float *__restrict__ logp_out, float *__restrict__ value_out, float *__restrict__ ratio_out) {
-  __shared__ float sW1[kL1Steps][64];   // [fragment][lane]: 5.75 KB
-  __shared__ float4 sW2[4][20][64];     // [out tile][k-step / 4][lane]: 80 KB
-  __shared__ __attribute__((aligned(16))) float sWh[9][kHidden];  // actor_linear rows 0..7 (zero past n_a), critic_linear row 8: 4.5 KB
-  __shared__ float sB1[kCat], sB2[kHidden], sBh[9];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 31, h = lane >> 5;
-  for (int t = tid; t < kL1Steps * 64; t += kThreadsA) {
-    const int l = t & 63, q = t >> 6;
-    int m, s;
-    l1_step(q, m, s);
-    const int k = 2 * s + (l >> 5);
-    float v;
-    if (m == 0) v = k < 5 ? w.W11[(l & 31) * 5 + k] : 0.0f;
-    else if (m <= 2) v = w.W12[(32 * (m - 1) + (l & 31)) * 10 + k];
-    else v = w.W13[(32 * (m - 3) + (l & 31)) * 10 + k];
-    sW1[q][l] = v;
-  }
-  stage_w2<20, kThreadsA>(sW2, w.W2, kCat);
-  for (int t = tid; t < 9 * kHidden; t += kThreadsA) {
-    const int o = t / kHidden, c = t % kHidden;
-    sWh[o][c] = o == 8 ? w.Wc[c] : (o < n_a ? w.Wa[o * kHidden + c] : 0.0f);
-  }
-  if (tid < 32) sB1[tid] = w.b11[tid];
-  else if (tid < 96) sB1[tid] = w.b12[tid - 32];
-  else if (tid < kCat) sB1[tid] = w.b13[tid - 96];
-  if (tid < kHidden) sB2[tid] = w.b2[tid];
-  if (tid < 9) sBh[tid] = tid == 8 ? w.bc[0] : (tid < n_a ? w.ba[tid] : 0.0f);
-  __syncthreads();
-  const int nb = *count;
-  const float inv_b = nb > 0 ? 1.0f / (float)nb : 0.0f;
-  const bool ref_form = adv_sums != nullptr;
-  const double sp_d = ref_form ? (double)adv_sums[0] : 0.0, sn_d = ref_form ? (double)adv_sums[1] : 0.0;
-  const RefWeights ref_w = ref_weights(sp_d, sn_d, nb);
-  const float lo = 1.0f - clip_param, hi = 1.0f + clip_param;
-  const long long ntiles = (n + 31) / 32;
-  constexpr int kWaves = kThreadsA / 64;
-  for (long long tile = (long long)blockIdx.x * kWaves + wave; tile < ntiles; tile += (long long)gridDim.x * kWaves) {
-    asm volatile("" ::: "memory");  // keep the tile-invariant LDS reads inside the persistent loop (mm_policy_mfma.h)
-    const long long ag = tile * 32 + j;
-    bool live = ag < n;
-    if (live && valid) live = valid[ag] != 0;
-    const float *row = obs + (live ? ag : 0) * obs_stride;
-    float x1[3], x2[5], x3[5];
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const int k = 2 * s + h;
-      x1[s] = (live && k < 5) ? row[5 * k] : 0.0f;
-    }
-#pragma unroll
-    for (int s = 0; s < 5; s++) {
-      const int k = 2 * s + h;
-      x2[s] = live ? row[5 * (k >> 1) + 1 + (k & 1)] : 0.0f;
-      x3[s] = live ? row[5 * (k >> 1) + 3 + (k & 1)] : 0.0f;
-    }
-    // x row of the scratch: columns 16 h .. 16 h + 15 (0..24 kept), zeros for a masked sample
-    {
-      float4 *dst = reinterpret_cast<float4 *>(s_xs + ag * kXs + 16 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int c = 16 * h + 4 * g + u;
-          v[u] = (live && c < 25) ? row[c] : 0.0f;
-        }
-        dst[g] = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-    f32x16 h1[5], h2[4];
-#pragma unroll
-    for (int m = 0; m < 5; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[r] = sB1[32 * m + frag_row(r, h)];
-      if (m == 0) {
-#pragma unroll
-        for (int s = 0; s < 3; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW1[s][lane], x1[s], acc, 0, 0, 0);
-      } else {
-        const int q0 = 3 + 5 * (m - 1);
-#pragma unroll
-        for (int s = 0; s < 5; s++)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW1[q0 + s][lane], m <= 2 ? x2[s] : x3[s], acc, 0, 0, 0);
-      }
-      h1[m] = relu(acc);
-      store_tile(s_h1 + ag * kCat + 32 * m + 4 * h, h1[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[r] = sB2[32 * m + frag_row(r, h)];
-      h2[m] = relu(fc2_tile<5>(sW2[m], h1, lane, acc));
-      store_tile(s_h2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- heads
-    float logit[8];
-#pragma unroll
-    for (int o = 0; o < 8; o++) {
-      const float p = head_dot(h2, sWh[o], h, o < n_a);
-      logit[o] = o < n_a ? p + sBh[o] : -INFINITY;
-    }
-    float v = 0.0f;
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) v = fmaf(h2[m][r], sWh[8][32 * m + frag_row(r, h)], v);
-    v = v + __shfl_xor(v, 32, 64) + sBh[8];
-    const float mx = max8(logit);
-    float se = 0.0f;
-#pragma unroll
-    for (int o = 0; o < 8; o++) se += exp_shifted(logit[o], mx, o < n_a);
-    const float lse = mx + logf(se);
-    // ---- the objective's per-sample terms (both lane halves compute the same numbers)
-    int act = live ? actions[ag * act_stride] : 0;
-    act = act < 0 ? 0 : (act > n_a - 1 ? n_a - 1 : act);
-    const float ret = live ? returns[ag * ret_stride] : 0.0f;
-    const float olp = live ? old_logp[ag] : 0.0f;
-    const float lp_a = logp_taken(logit, lse, act);
-    const float r = expf(lp_a - olp);
-    const float adv = ret - v;
-    const float c = fminf(fmaxf(r, lo), hi);
-    double t_actor;
-    float wsel;
-    if (ref_form) ppo_clip_ref(sp_d, sn_d, ref_w, lo, hi, r, c, t_actor, wsel);
-    else ppo_clip_flat(adv, lo, hi, r, c, t_actor, wsel);
-    const float dldr = -inv_b * wsel;
-    const float d = v - ret;
-    float t_critic, dv;
-    critic_term(d, huber, t_critic, dv);
-    dv = live ? dv * inv_b : 0.0f;
-    float dlogit[8];
-    const float g_lp = live ? dldr * r : 0.0f;  // d loss / d logp_taken
-#pragma unroll
-    for (int o = 0; o < 8; o++) dlogit[o] = (o < n_a) ? mfma::dlogit(g_lp, logit[o], lse, o == act) : 0.0f;
-    {
-      float4 *dst = reinterpret_cast<float4 *>(s_dh + ag * kDh + 8 * h);
-      if (h == 0) {
-        dst[0] = make_float4(dlogit[0], dlogit[1], dlogit[2], dlogit[3]);
-        dst[1] = make_float4(dlogit[4], dlogit[5], dlogit[6], dlogit[7]);
-      } else {
-        dst[0] = make_float4(dv, 0.0f, 0.0f, 0.0f);
-        dst[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      }
-    }
-    if (h == 0 && ag < n) {
-      if (logp_out) logp_out[ag] = live ? lp_a : 0.0f;
-      if (value_out) value_out[ag] = live ? v : 0.0f;
-      if (ratio_out) ratio_out[ag] = live ? r : 0.0f;
-    }
-    // loss partial of this tile: lanes of half 0, fixed butterfly
-    {
-      double pa = (live && h == 0) ? t_actor : 0.0, pc = (live && h == 0) ? (double)t_critic : 0.0;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) {
-        pa += __shfl_xor(pa, o, 64);
-        pc += __shfl_xor(pc, o, 64);
-      }
-      if (lane == 0) {
-        lossp[2 * tile] = pa;
-        lossp[2 * tile + 1] = pc;
-      }
-    }
-    // ---- dz2 = (Wa^T dlogit + Wc^T dvalue) . [h2 > 0], in accumulator form (reuses h2's registers)
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        // the lane's features 32 m + 8 g + 4 h .. + 3 are contiguous in a head row: one ds_read_b128 per row.  Rows past
-        // n_a are zero in sWh and their dlogit is zero, so all 9 rows are summed without a branch.
-        const int f = 32 * m + 8 * g + 4 * h;
-        const float4 wc = *reinterpret_cast<const float4 *>(&sWh[8][f]);
-        float s0 = dv * wc.x, s1 = dv * wc.y, s2 = dv * wc.z, s3 = dv * wc.w;
-#pragma unroll
-        for (int o = 0; o < 8; o++) {
-          const float4 wa = *reinterpret_cast<const float4 *>(&sWh[o][f]);
-          s0 = fmaf(dlogit[o], wa.x, s0);
-          s1 = fmaf(dlogit[o], wa.y, s1);
-          s2 = fmaf(dlogit[o], wa.z, s2);
-          s3 = fmaf(dlogit[o], wa.w, s3);
-        }
-        h2[m][4 * g + 0] = h2[m][4 * g + 0] > 0.0f ? s0 : 0.0f;
-        h2[m][4 * g + 1] = h2[m][4 * g + 1] > 0.0f ? s1 : 0.0f;
-        h2[m][4 * g + 2] = h2[m][4 * g + 2] > 0.0f ? s2 : 0.0f;
-        h2[m][4 * g + 3] = h2[m][4 * g + 3] > 0.0f ? s3 : 0.0f;
-      }
-      store_tile(s_dz2 + ag * kHidden + 32 * m + 4 * h, h2[m]);
-    }
-    // ---- dz1 = (W2^T dz2) . [h1 > 0]: 5 output tiles x 64 k-steps, A fragments from global memory
-    const unsigned vlane = opaque_lane(lane);
-#pragma unroll
-    for (int mt = 0; mt < 5; mt++) {
-      const f32x16 acc = dz1_tile(frag, mt, vlane, h2);
-      // the ReLU mask of layer 1 is read back from this lane's own h1 stores (L2 / L1 hot) instead of holding h1's 80
-      // registers across the heads and the second contraction
-      const float4 *msk = reinterpret_cast<const float4 *>(s_h1 + ag * kCat + 32 * mt + 4 * h);
-      float4 *dst = reinterpret_cast<float4 *>(s_dz1 + ag * kCat + 32 * mt + 4 * h);
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const float4 a = msk[2 * g];
-        dst[2 * g] = make_float4(a.x > 0.0f ? acc[4 * g] : 0.0f, a.y > 0.0f ? acc[4 * g + 1] : 0.0f,
-                                 a.z > 0.0f ? acc[4 * g + 2] : 0.0f, a.w > 0.0f ? acc[4 * g + 3] : 0.0f);
-      }
-    }
-  }
+  const FlatArgs a = {obs, obs_stride, n, actions, act_stride, returns, ret_stride, old_logp, valid, w, n_a, clip_param, huber, adv_sums,
+                      count, frag, s_h1, s_dz1, s_h2, s_dz2, s_dh, s_xs, lossp, logp_out, value_out, ratio_out};
+  gi_sample_body<true>(Flat(a));
 }
 
 // ---- kernel B: one workgroup = one slice of samples [row0, row1), rows are whole 32-sample tiles inside n_pad

@@ -39,7 +39,9 @@ learner there wants `scratch_budget_bytes`.  Limit: a sharded train() is not gra
 
 `BankPPOLearner` (at the end) is K `PPOLearner(fused_step=True)`s of one shape as one learner, for the K env groups of a bank-mode
 `DeviceRollout`: stacked storage that the member modules alias, and per agent step one `mm_policy_bank_eval`, one
-`mm_policy_bank_train` (include/mm_policy_bank_train.h) and one `mm_opt_step_bank` whatever K is.
+`mm_policy_bank_train` (include/mm_policy_bank_train.h) and one `mm_opt_step_bank` whatever K is.  `SharedBankPPOLearner` is
+the same for K `SharedPPOLearner(fused_step=True)`s -- the `*-shared` configurations -- on `mm_policy_gi_bank_eval` /
+`mm_policy_gi_bank_train` (include/mm_policy_gi_bank_train.h).
 """
 import copy
 import ctypes as C
@@ -909,8 +911,8 @@ class BankPPOLearner(_DeviceLearner):
     `mm_policy_bank_train` (include/mm_policy_bank_train.h) fed the critic targets' values, and one `mm_opt_step_bank`
     (include/mm_opt_step.h).  Member k's parameters, targets and optimiser state are bit for bit those of a K = 1 learner on its
     slice.  Against `PPOLearner` the one difference is the reference form's S+ / S-: torch's float32 sums there, one fp64
-    accumulation rounded once here.  Out of scope: hidden 512, ActorCriticNetwork members, scratch budgets and shard groups,
-    per-member hyperparameters."""
+    accumulation rounded once here.  ActorCriticNetwork members (MAPPO_GI's shared network) are SharedBankPPOLearner's.  Out of
+    scope: hidden 512, scratch budgets and shard groups, per-member hyperparameters."""
 
     def __init__(self, actors, critics, clib, group_envs, actor_lr=1e-4, critic_lr=1e-4, optimizer_type="rmsprop", clip_param=0.2,
                  critic_loss="mse", max_grad_norm=0.5, target_tau=1.0, target_update_steps=5, soft_update_every="train"):
@@ -921,8 +923,8 @@ class BankPPOLearner(_DeviceLearner):
         if K > abi.BANK_MAX_GROUPS:
             raise ValueError("a policy bank has at most %d members, got %d" % (abi.BANK_MAX_GROUPS, K))
         if any(isinstance(m, ActorCriticNetwork) for m in actors + critics):
-            raise ValueError("BankPPOLearner does not train ActorCriticNetwork members (MAPPO_GI's shared network): use one "
-                             "SharedPPOLearner per member")
+            raise ValueError("BankPPOLearner does not train ActorCriticNetwork members (MAPPO_GI's shared network): use "
+                             "SharedBankPPOLearner")
         if any(type(a) is not ActorNetwork for a in actors) or any(type(c) is not CriticNetwork for c in critics):
             raise ValueError("BankPPOLearner needs rollout.ActorNetwork and rollout.CriticNetwork members")
         shapes = [tuple(tuple(p.shape) for p in _mlp_params(a) + _mlp_params(c)) for a, c in zip(actors, critics)]
@@ -1148,4 +1150,243 @@ class BankPPOLearner(_DeviceLearner):
             old, value = self.evaluate(obs, act, rows, col_start=cols, valid=v)
             losses.append(self.loss_and_grad(obs, act, ret, old, rows, col_start=cols, valid=v, form=form, target_value=value))
             self.step(mask if (every or i == len(passes) - 1) else 0)
+        return losses
+
+
+class SharedBankPPOLearner(_DeviceLearner):
+    """Bank mode's training half for MAPPO_GI's shared network: K `SharedPPOLearner(fused_step=True)`s as ONE learner whose
+    launches do not multiply with K.  `members` are K rollout.ActorCriticNetwork(state_split=True) of one shape, hidden 128,
+    float32, on the device -- typically the members a `DeviceRollout(env, members, group_envs=...)` acts with; `group_envs` are
+    that rollout's env counts (member k trains on `batch[:, roll.group_slice(k)]`).  The hyperparameters are SharedPPOLearner's
+    and are shared by the members; the optimiser step is always the fused one.
+
+    The learner owns STACKED storage, member k at index k of the leading axis: the twelve parameter tensors, their gradients,
+    optimiser state and targets (deep copies at construction) and the per-member Adam steps.  At construction every member
+    module's `param.data` and `.grad` are re-pointed at views of the stacks, so the modules -- and a DeviceRollout /
+    SharedPolicyBank built on them, at its next refresh -- see every update.
+
+    Per agent step train() in form "reference" issues one `mm_policy_gi_bank_eval` on the stacked targets (the old
+    log-probabilities), one on the live stacks (the values behind S+ / S-), one `mm_policy_gi_bank_train`
+    (include/mm_policy_gi_bank_train.h) and one `mm_opt_step_bank` (include/mm_opt_step.h); form "flat" does the same once on all
+    agents' samples, without the value pass.  Member k's parameters, targets and optimiser state are bit for bit those of a
+    K = 1 learner on its slice, and in form "flat" those of a `SharedPPOLearner(fused_step=True)` on it.  Against
+    `SharedPPOLearner` the one difference is the reference form's S+ / S-: torch's float32 sums there, one fp64 accumulation
+    rounded once here.  Out of scope: hidden 512, scratch budgets and shard groups, per-member hyperparameters."""
+
+    def __init__(self, members, clib, group_envs, lr=1e-4, optimizer_type="rmsprop", clip_param=0.2, critic_loss="mse",
+                 max_grad_norm=0.5, target_tau=1.0, target_update_steps=5):
+        members = list(members)
+        K = len(members)
+        if K < 1:
+            raise ValueError("SharedBankPPOLearner needs at least one member")
+        if K > abi.BANK_MAX_GROUPS:
+            raise ValueError("a policy bank has at most %d members, got %d" % (abi.BANK_MAX_GROUPS, K))
+        if any(type(m) is not ActorCriticNetwork or not m.state_split or m.fc2.weight.shape[0] != 128 for m in members):
+            raise ValueError("SharedBankPPOLearner needs rollout.ActorCriticNetwork(state_split=True) members with hidden size 128")
+        shapes = [tuple(tuple(p.shape) for p in _params(m)) for m in members]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("the members of a bank learner must have one shape, got %d different ones" % len(set(shapes)))
+        n_a = members[0].actor_linear.weight.shape[0]
+        if shapes[0] != ((32, 5), (32,), (64, 10), (64,), (64, 10), (64,), (128, 160), (128,), (n_a, 128), (n_a,), (1, 128), (1,)):
+            raise ValueError("SharedBankPPOLearner needs the state-split network of 25 split columns and one critic output")
+        if not 1 <= n_a <= 8:
+            raise ValueError("SharedBankPPOLearner supports 1..8 actions, got %d" % n_a)
+        for m in members:
+            for p in m.parameters():
+                if p.dtype != torch.float32 or p.device.type != "cuda":
+                    raise ValueError("SharedBankPPOLearner needs float32 networks on the device")
+        if critic_loss not in abi.GI_CRITIC_LOSS:
+            raise ValueError("critic_loss must be 'mse' or 'huber', got %r" % (critic_loss,))
+        _optimizer_class(optimizer_type)
+        group_envs = [int(e) for e in group_envs]
+        if len(group_envs) != K or min(group_envs) < 0:
+            raise ValueError("group_envs must hold one non-negative env count per member (%d)" % K)
+        clib.require_policy_gi_bank_train()
+        _DeviceLearner.__init__(self, clib, members[0].fc2.weight.device, None)
+        self.members, self.K, self.group_envs = members, K, group_envs
+        self.env_start = [sum(group_envs[:k]) for k in range(K + 1)]
+        self.n_a, self.hidden = n_a, 128
+        self.optimizer_type, self.lr = optimizer_type, float(lr)
+        self.clip_param, self.critic_loss, self.max_grad_norm = float(clip_param), critic_loss, max_grad_norm
+        self.target_tau, self.target_update_steps, self.fused_step = float(target_tau), int(target_update_steps), True
+        # the stacks: twelve [K, ...] tensors each, in MMGiParams' order
+        self.params = [torch.stack([_params(m)[i].detach() for m in members]).contiguous() for i in range(12)]
+        self.grads = [torch.zeros_like(t) for t in self.params]
+        self.targets = [t.clone() for t in self.params]
+        self.state1 = [torch.zeros_like(t) for t in self.params]
+        self.state2 = [torch.zeros_like(t) for t in self.params] if optimizer_type == "adam" else None
+        self.steps = torch.zeros(K, dtype=torch.int32, device=self.device)
+        self._grad_norm = torch.zeros(K, dtype=torch.float32, device=self.device)
+        for k, m in enumerate(members):
+            for i, p in enumerate(_params(m)):
+                p.data = self.params[i][k]
+                p.grad = self.grads[i][k]
+        struct = lambda ts: abi.MMGiParams(*[t.data_ptr() for t in ts])  # noqa: E731
+        self._W, self._G, self._T = struct(self.params), struct(self.grads), struct(self.targets)
+        g = self._group = abi.MMOptGroup()
+        g.algo, g.n_tensors = OPT_ALGO[optimizer_type], 12
+        for i in range(12):
+            g.count[i] = self.params[i][0].numel()
+            g.param[i], g.grad[i] = self.params[i].data_ptr(), self.grads[i].data_ptr()
+            g.target[i], g.state1[i] = self.targets[i].data_ptr(), self.state1[i].data_ptr()
+            if self.state2 is not None:
+                g.state2[i] = self.state2[i].data_ptr()
+        g.step, g.grad_norm = self.steps.data_ptr(), self._grad_norm.data_ptr()
+
+    # -- plumbing ----------------------------------------------------------------------------
+    def _torch_optimizer(self, k):
+        """A torch optimiser over member k: the home of the hyperparameters in torch's format (it never steps)."""
+        return _optimizer_class(self.optimizer_type)(self.members[k].parameters(), lr=self.lr)
+
+    def _cols(self, col_start, row_len):
+        cols = [int(c) for c in (self.env_start if col_start is None else col_start)]
+        if len(cols) != self.K + 1 or cols[0] != 0 or cols[-1] != row_len or any(b < a for a, b in zip(cols, cols[1:])):
+            raise ValueError("group_envs %s do not match the batch: the column prefix %s must run from 0 to the row length %d"
+                             % (self.group_envs, cols, row_len))
+        return cols, (C.c_int64 * (self.K + 1))(*cols)
+
+    def _samples(self, obs, actions, rows):
+        n, S = obs.shape
+        if obs.dtype != torch.float32 or (n and obs.stride(1) != 1) or not 25 <= S <= 32:
+            raise ValueError("obs must be float32 [n, 25..32] with contiguous rows")
+        if actions.dtype != torch.int32 or actions.dim() != 1 or actions.shape[0] != n:
+            raise ValueError("actions must be int32 [n]")
+        rows = int(rows)
+        row_len = n // rows if rows > 0 else self.env_start[-1]
+        if rows < 0 or rows * row_len != n:
+            raise ValueError("%d samples are not %d rows" % (n, rows))
+        return n, S, rows, row_len
+
+    def evaluate(self, obs, actions, rows, col_start=None, valid=None, targets=True, logp=True, value=True):
+        """The bare mm_policy_gi_bank_eval: (logp_taken, value), float32 [n] each (None for an output that is not asked for), of
+        every sample's own member -- the stacked targets, or with targets=False the live stacks.  obs [n, S] with any row
+        stride, actions int32 [n] with any stride, n = rows * row_len; col_start: the K + 1 column prefix (None: group_envs')."""
+        n, S, rows, row_len = self._samples(obs, actions, rows)
+        _, cs = self._cols(col_start, row_len)
+        if not logp and not value:
+            raise ValueError("evaluate needs at least one of logp and value")
+        if valid is not None:
+            valid = valid.reshape(-1).to(torch.uint8).contiguous()
+        out_l = torch.empty(n, dtype=torch.float32, device=self.device) if logp else None
+        out_v = torch.empty(n, dtype=torch.float32, device=self.device) if value else None
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_gi_bank_eval(
+            obs.data_ptr(), obs.stride(0) if n else S, rows, row_len, S, actions.data_ptr(), actions.stride(0) if n else 1, opt(valid),
+            C.byref(self._T if targets else self._W), self.K, cs, self.hidden, self.n_a, opt(out_l), opt(out_v), self._stream()))
+        return out_l, out_v
+
+    def loss_and_grad(self, obs, actions, returns, old_logp, rows, col_start=None, valid=None, form="reference", value_now=None,
+                      diagnostics=False):
+        """The bare mm_policy_gi_bank_train: writes every member's gradients into the stacked gradients (the modules' .grad) and
+        returns the float32 [K, 3] losses (actor, critic, sum); with diagnostics also the [K, 2] (S+, S-) that were used and
+        (logp_taken, value, ratio) [n].  Inputs as SharedPPOLearner.loss_and_grad's, n = rows * row_len; form "reference" needs
+        value_now (float32 [n], the live members' values), form "flat" takes none.  Only enqueues work."""
+        n, S, rows, row_len = self._samples(obs, actions, rows)
+        cols, cs = self._cols(col_start, row_len)
+        if form not in ("reference", "flat"):
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        if (form == "reference") != (value_now is not None):
+            raise ValueError("form 'reference' needs value_now, form 'flat' takes none")
+        if returns.dtype != torch.float32 or returns.dim() != 1 or returns.shape[0] != n or old_logp.shape[0] != n:
+            raise ValueError("returns must be float32 [n] and old_logp [n]")
+        flat32 = lambda t: None if t is None else t.reshape(-1).to(torch.float32).contiguous()  # noqa: E731
+        old_logp, value_now = flat32(old_logp), flat32(value_now)
+        if value_now is not None and value_now.shape[0] != n:
+            raise ValueError("value_now must be float32 [n]")
+        if valid is not None:
+            valid = valid.reshape(-1).to(torch.uint8).contiguous()
+        loss = torch.empty(self.K, 3, dtype=torch.float32, device=self.device)
+        sums = torch.empty(self.K, 2, dtype=torch.float32, device=self.device) if diagnostics else None
+        diag = [torch.empty(n, dtype=torch.float32, device=self.device) if diagnostics else None for _ in range(3)]
+        scratch = self._grow(self.clib.policy_gi_bank_train_scratch_bytes(rows, row_len, cols))
+        opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self.clib.check(self.clib.lib.mm_policy_gi_bank_train(
+            obs.data_ptr(), obs.stride(0) if n else S, rows, row_len, S, actions.data_ptr(), actions.stride(0) if n else 1,
+            returns.data_ptr(), returns.stride(0) if n else 1, old_logp.data_ptr(), opt(valid), C.byref(self._W), self.K, cs,
+            self.hidden, self.n_a, self.clip_param, abi.GI_CRITIC_LOSS[self.critic_loss],
+            abi.PT_FORM["reference" if form == "reference" else "per_sample"], opt(value_now), C.byref(self._G), loss.data_ptr(),
+            opt(sums), opt(diag[0]), opt(diag[1]), opt(diag[2]), scratch.data_ptr(), scratch.numel(), self._stream()))
+        return (loss, sums, tuple(diag)) if diagnostics else loss
+
+    def _fill(self):
+        g = self._group
+        g.lr, g.eps = self.lr, 1e-8  # (torch's default eps of both optimisers)
+        g.alpha_or_beta1, g.beta2 = (0.9, 0.999) if self.optimizer_type == "adam" else (0.99, 0.0)
+        g.max_grad_norm = -1.0 if self.max_grad_norm is None else self.max_grad_norm
+        g.tau = self.target_tau
+        return [g]
+
+    def step(self, soft_mask=0):
+        """clip + optimiser step of all K networks, and the soft update of the members whose bit is set: one launch."""
+        self.clib.opt_step_bank(self._fill(), self.K, int(soft_mask), self._stream())
+
+    def last_grad_norm(self):
+        """The total gradient norms before clipping of the last step, float32 [K] on the device."""
+        return self._grad_norm
+
+    def optimizer_state_dict(self, k):
+        """Member k's optimiser state in torch.optim's state_dict() format: it loads into a SharedPPOLearner (either path) and
+        into torch.optim.  Reads the member's step count: synchronises."""
+        s2 = None if self.state2 is None else [t[k] for t in self.state2]
+        return optimizer_state_to_torch(self.optimizer_type, self._torch_optimizer(k).state_dict()["param_groups"],
+                                        int(self.steps[k].item()), [t[k] for t in self.state1], s2)
+
+    def load_optimizer_state_dict(self, k, state_dict):
+        """The reverse, in place.  The state dict's hyperparameters are not taken: the members share the learner's."""
+        step, s1, s2 = optimizer_state_from_torch(state_dict, self.optimizer_type, 12)
+        for mine, theirs in ((self.state1, s1), (self.state2, s2)):
+            if mine is not None:
+                for m, t in zip(mine, theirs):
+                    m[k].zero_() if t is None else m[k].copy_(t)
+        self.steps[k] = step
+
+    def _soft_mask(self, n_episodes):
+        eps = [int(n_episodes)] * self.K if isinstance(n_episodes, int) else [int(e) for e in n_episodes]
+        if len(eps) != self.K:
+            raise ValueError("n_episodes must be an int or one int per member (%d)" % self.K)
+        return sum(1 << k for k, e in enumerate(eps) if e % self.target_update_steps == 0 and e > 0)
+
+    @torch.no_grad()
+    def train(self, states, actions=None, returns=None, n_episodes=0, form="reference", valid=None):
+        """SharedPPOLearner.train() for every member on its env group at once.  states [T, E, N, S] (or [T * E, N, S]),
+        E = sum(group_envs), actions and returns [T, E, N], or `DeviceRollout.interact()`'s dict.  n_episodes: an int or K
+        ints; member k's targets are blended after every optimiser step of this call when
+        n_episodes[k] % target_update_steps == 0 and n_episodes[k] > 0 (SharedPPOLearner's rule).  Returns the list of float32
+        [K, 3] loss tensors, one per agent step (one in all, form "flat"); nothing is synchronised."""
+        if isinstance(states, dict):
+            states, actions, returns = states["states"], states["actions"], states["returns"]
+        if form not in ("reference", "flat"):
+            raise ValueError("form must be 'reference' or 'flat', got %r" % (form,))
+        N, S, E = states.shape[-2], states.shape[-1], self.env_start[-1]
+        if states.dim() == 4 and states.shape[1] == E:
+            rows = states.shape[0]
+        elif states.dim() == 3 and E > 0 and states.shape[0] % E == 0:
+            rows = states.shape[0] // E
+        else:
+            raise ValueError("group_envs %s do not match the batch: states %s must be [T, %d, N, S] or [T * %d, N, S]"
+                             % (self.group_envs, tuple(states.shape), E, E))
+        if actions.numel() != rows * E * N or returns.numel() != rows * E * N:
+            raise ValueError("actions and returns must hold one entry per state row")
+        states = states.reshape(rows, E, N, S).to(torch.float32).contiguous()
+        actions = actions.reshape(rows, E, N).to(torch.int32).contiguous()
+        returns = returns.reshape(rows, E, N).to(torch.float32).contiguous()
+        if valid is not None:
+            valid = valid.reshape(rows, E, N).to(torch.uint8)
+        mask = self._soft_mask(n_episodes)
+        losses = []
+        if form == "reference":
+            for a in range(N):
+                obs, act, ret = states.view(rows * E, N, S)[:, a, :], actions.view(rows * E, N)[:, a], returns.view(rows * E, N)[:, a]
+                v = None if valid is None else valid[:, :, a].reshape(-1).contiguous()
+                old, _ = self.evaluate(obs, act, rows, valid=v, value=False)
+                _, now = self.evaluate(obs, act, rows, valid=v, targets=False, logp=False)
+                losses.append(self.loss_and_grad(obs, act, ret, old, rows, valid=v, form=form, value_now=now))
+                self.step(mask)
+        else:
+            obs, act, ret = states.view(rows * E * N, S), actions.view(-1), returns.view(-1)
+            v = None if valid is None else valid.reshape(-1)
+            cols = [e * N for e in self.env_start]
+            old, _ = self.evaluate(obs, act, rows, col_start=cols, valid=v, value=False)
+            losses.append(self.loss_and_grad(obs, act, ret, old, rows, col_start=cols, valid=v, form=form))
+            self.step(mask)
         return losses
